@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- wideband I/Q Msamples/s (+ HFDL frames/s) of the MI355X HFDL front end at a fixed channel count.
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg4] [--shard streams|channels]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg4] [--shard streams|channels] [--dump-outputs DIR] [--full]
 
 One "step" = one block of `input_size` wideband cf32 samples through the WHOLE hot path: overlap assembly, forward
 FFT, per-channel fold + inverse FFT + NCO (fastddc), per-channel demodulator, burst decoder, PDU read-back.
@@ -10,19 +10,26 @@ rank per GPU; with --shard streams (default) every rank owns an independent wide
 (BASELINE.json configs[4], weak scaling); with --shard channels all ranks ingest the SAME stream and each decodes a
 round-robin subset of its channels (SURVEY.md 8e, strong scaling).  No data-path collective either way.
 
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the timed path handed back
+in its last step (dump_outputs).  Every figure that takes a run of its own -- the legs marked [--full] below -- is measured only with
+--full (and there still subject to --no-extra-legs / --no-cpu-baseline).
+
 The JSON line carries, next to the driver's contract fields:
+  block_to_pdus_latency_ms  [--full] one block pushed into an idle pipeline until its PDUs are on the host (median of five)
   roofline        the fold kernel (spectrum x per-channel filter, >99% of the block's algorithmic bytes), timed with
-                  HIP events on the front end's own stream; bytes = SURVEY.md section 8(d) canonical model
-  host_ram_input  the same workload fed from page-locked HOST memory (SURVEY.md 8(d) "input pre-loaded in host RAM"):
+                  HIP events on the front end's own stream; bytes = SURVEY.md section 8(d) canonical model; its
+                  hbm.stream_read_GBs (a read-only probe of the laboratory build, a run of its own) only with --full
+  host_ram_input  [--full] the same workload fed from page-locked HOST memory (SURVEY.md 8(d) "input pre-loaded in host RAM"):
                   PCIe-inclusive, never `value`
-  host_path       the same workload through the C host library (file input -> block graph -> GPU front end ->
+  host_path       [--full] the same workload through the C host library (file input -> block graph -> GPU front end ->
                   pdu_decoder_queue_push), i.e. what a dumphfdl user gets (dumphfdl_amd/hfdl_replay --bench)
   pdus_*          every PDU of the timed region is checked against the sent traffic: payload + mode, on-device header FCS,
                   and the device's LPDU walk (every announced LPDU found with a good FCS; the traffic carries real LPDU lists)
-  fec             trellis steps/s: demanded by the run, and the burst decoder's own capacity on a resident batch
-  parity          same-run gate: the channels the CPU baseline decodes, decoded by the GPU from the same blocks --
+  fec             [--full] the burst decoder's own capacity on a resident batch, in trellis steps/s (what the run demanded:
+                  trellis_steps_per_s_in_run, in every run)
+  parity          [--full] same-run gate: the channels the CPU baseline decodes, decoded by the GPU from the same blocks --
                   channelizer error RMS / signal RMS and the (freq, sample_index, mode, octets) multisets
-  cpu_baseline    the plain-C oracle built with the reference's release flags, timed on this box's host cores on a
+  cpu_baseline    [--full] the plain-C oracle built with the reference's release flags, timed on the host's own cores on a
                   bounded sample of the same workload (rank 0, N = 1 only)
 """
 import argparse
@@ -731,14 +738,47 @@ def pruned_fold_leg(torch, hf, F, w, freqs, x, dev_index, steps, warmup, ref_pdu
                 detection_sample_max_abs_diff=(max([abs(p["sample_index"] - q["sample_index"]) for p, q in zip(a, b)] or [0]) if same else None))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, buf, n, prefix="", max_bytes=DUMP_MAX_BYTES):
+    """What the timed path handed its caller in its last step -- the hfdl_gpu_pdu structs of the draining collection that ends the
+    timed region -- as one .npy per field, float64 (float32 for the fields the device computes in float32), rows sorted by
+    (freq, sample_index, mode) so that two builds compare row for row whatever order the device ring filled in.  Octets are
+    zero-padded to PDU_MAX_OCTETS per row.  Above `max_bytes` in all, a fixed seeded sample of the rows is written."""
+    from dumphfdl_amd import frontend as F
+    os.makedirs(out_dir, exist_ok=True)
+    rows = sorted(range(n), key=lambda i: (buf[i].freq, buf[i].sample_index, buf[i].mode))
+    row_bytes = 8 * 17 + 4 * 3 + 4 * F.PDU_MAX_OCTETS
+    room = max_bytes - (64 << 10)                    # the .npy headers
+    if len(rows) * row_bytes > room:
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), room // row_bytes, replace=False))
+        rows = [rows[i] for i in keep]
+    p = [buf[i] for i in rows]
+    f64 = lambda v: np.array(v, np.float64)
+    arrays = dict(
+        pdu_channel=f64([q.channel for q in p]), pdu_freq_hz=f64([q.freq for q in p]), pdu_mode=f64([q.mode for q in p]),
+        pdu_bit_rate=f64([q.bit_rate for q in p]), pdu_len=f64([q.len for q in p]), pdu_sample_index=f64([q.sample_index for q in p]),
+        pdu_slot=f64([ord(q.slot) for q in p]), pdu_fcs_status=f64([q.fcs_status for q in p]), pdu_kind=f64([q.pdu_kind for q in p]),
+        pdu_hdr_len=f64([q.hdr_len for q in p]), pdu_train_bits_bad=f64([q.train_bits_bad for q in p]),
+        pdu_train_bits_total=f64([q.train_bits_total for q in p]),
+        pdu_lpdus=f64([(q.lpdus_processed, q.lpdus_good, q.lpdus_bad_fcs, q.lpdus_too_short, q.lpdus_truncated) for q in p]).reshape(-1, 5),
+        pdu_freq_err_hz=np.array([q.freq_err_hz for q in p], np.float32), pdu_rssi_db=np.array([q.rssi_db for q in p], np.float32),
+        pdu_noise_floor_db=np.array([q.noise_floor_db for q in p], np.float32),
+        pdu_octets=np.array([list(q.octets[:q.len]) + [0] * (F.PDU_MAX_OCTETS - q.len) for q in p], np.float32).reshape(-1, F.PDU_MAX_OCTETS))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    return len(p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256, help="timed blocks (one step = one block of input_size samples through the whole path); 256 blocks of the 40 Msps geometry = 0.75 s")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline and the same-run parity gate")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip host_ram_input / host_path / fec / cfg2 (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and the same-run parity gate")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip host_ram_input / host_path / fec / cfg2 / pruned_fold")
     ap.add_argument("--host-input", action="store_true",
                     help="feed the TIMED blocks from page-locked HOST memory (PCIe-inclusive rate; then `value` is not the headline figure)")
     ap.add_argument("--sample-format", default="cf32", choices=["cf32", "cs16"], help="with --host-input: raw format pushed over PCIe")
@@ -747,6 +787,12 @@ def main():
     ap.add_argument("--shard", default="streams", choices=["streams", "channels"],
                     help="N > 1: independent stream per rank (weak scaling, BASELINE configs[4]) or ONE stream with its channels split round-robin over the ranks (strong scaling, SURVEY 8e)")
     ap.add_argument("--dump-pdus", default=None, help="write this rank's PDU keys (freq, sample_index, mode, octets) to PATH.rankR.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the PDUs the timed path handed back in its last step to DIR/<name>.npy (rank 0; rank R > 0: "
+                         "DIR/rankR_<name>.npy), float32/float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: latency, host-RAM input, FEC capacity, stream-read probe, C host path, "
+                         "cfg2, pruned fold (unless --no-extra-legs), same-run parity gate and CPU baseline (unless --no-cpu-baseline)")
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
 
@@ -867,11 +913,13 @@ def main():
                                          npdus, good, g.channels, t_create, t_gen], use_dist, device=red_device)
     if args.dump_pdus:
         json.dump(sorted(pdu_key(p) for p in pdus), open("%s.rank%d.json" % (args.dump_pdus, rank), "w"))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *raw[-1], prefix="" if rank == 0 else "rank%d_" % rank, max_bytes=DUMP_MAX_BYTES // world)
 
-    # ---- extra legs (untimed with respect to `value`; rank 0 at N = 1)
+    # ---- extra legs (untimed with respect to `value`; rank 0 at N = 1; --full only)
     extra = {}
     solo = world == 1 and rank == 0
-    if solo:
+    if solo and args.full:
         # a live receiver's latency: ONE block pushed into an idle pipeline until its PDUs are on the host (forward FFT, a one-block
         # fold in the four-column form, inverse FFT, demodulator, burst decoder, collection): the median of five
         lat = []
@@ -882,9 +930,9 @@ def main():
             lat.append((time.perf_counter() - t0) * 1e3)
         extra["block_to_pdus_latency_ms"] = sorted(lat)[2]
         fe.reset_timers(False)
-    if solo and not args.no_extra_legs and not args.host_input:
+    if solo and args.full and not args.no_extra_legs and not args.host_input:
         hbuf, extra["host_ram_input"] = host_ram_leg(torch, hf, F, fe, x, g, nblocks, args.steps)
-    if solo and not args.no_extra_legs:
+    if solo and args.full and not args.no_extra_legs:
         extra["fec"] = fec_capacity(hf, dev_index)
     geom = dict(channels=g.channels, fft_size=g.fft_size, fft_inv_size=g.fft_inv_size, input_size=g.input_size)
     demod_batch = g.demod_batch
@@ -901,7 +949,7 @@ def main():
     del dev
     if hbuf:
         hf.host_free(hbuf)
-    stream_gbs = stream_read_leg(w, freqs, dev_index) if rank == 0 else None       # after the timed regions: the board's own read ceiling
+    stream_gbs = stream_read_leg(w, freqs, dev_index) if rank == 0 and args.full else None       # after the timed regions: the board's own read ceiling
 
     if rank == 0:
         samples = total_samples
@@ -995,7 +1043,7 @@ def main():
             "setup_s": {"frontend_create": round(t_create, 2), "input_synthesis": round(t_gen, 2)},
         }
         out.update(extra)
-        if solo and not args.no_extra_legs:
+        if solo and args.full and not args.no_extra_legs:
             out["host_path"] = host_path_leg(w, x, all_freqs, "CF32", dev_index)
             if args.workload != "cfg2" and not args.host_input:
                 try:
@@ -1007,7 +1055,7 @@ def main():
                     out["pruned_fold"] = pruned_fold_leg(torch, hf, F, w, freqs, x, dev_index, args.steps, args.warmup, pdus)
                 except Exception as e:                  # noqa: BLE001
                     out["pruned_fold"] = dict(error="%s: %s" % (type(e).__name__, e))
-        if solo and not args.no_cpu_baseline:
+        if solo and args.full and not args.no_cpu_baseline:
             cores = max(1, min(os.cpu_count() or 1, 64))
             out["parity"] = parity_gate(w, x, geom["input_size"], hf, dev_index, cores)
             out["cpu_baseline"] = cpu_baseline(w, x, geom["input_size"])

@@ -38,6 +38,19 @@ def viterbi_vectors():
     np.savez_compressed(os.path.join(HERE, "viterbi_ref.npz"), **out)
 
 
+def viterbi_live_vectors():
+    """The random soft inputs of tests/test_oracle_cpu.py::test_viterbi_live_reference (same seed, same order) and what the
+    reference's libfec decodes from them: the test compares the oracle with these where oracle/_ref is not built."""
+    rng = np.random.default_rng(2)
+    out = {}
+    for nbits in (540, 1260, 3240, 7560):
+        for i in range(3):
+            soft = rng.integers(0, 256, 2 * nbits).astype(np.uint8)
+            out["n%d_c%d_soft" % (nbits, i)] = soft
+            out["n%d_c%d_out" % (nbits, i)] = np.frombuffer(bytes(O.ref_viterbi27(soft, nbits)), np.uint8)
+    np.savez_compressed(os.path.join(HERE, "viterbi_live_ref.npz"), **out)
+
+
 def crc_vectors():
     rng = np.random.default_rng(7)
     vec = []
@@ -83,6 +96,7 @@ def nco_vectors():
 
 if __name__ == "__main__":
     viterbi_vectors()
+    viterbi_live_vectors()
     crc_vectors()
     nco_vectors()
     print("golden vectors written to", HERE)

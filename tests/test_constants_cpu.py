@@ -133,22 +133,24 @@ def check_tables_struct(t, K):
 # ---- the tests ----
 
 def test_golden_file_is_what_the_reference_says(K):
-    """container only: re-parse the reference and compare with the committed file (the GPU box has no reference: skipped there)"""
-    if not os.path.exists(REF):
-        pytest.skip("no /root/reference here")
-    import importlib.util
-    import tempfile
-    spec = importlib.util.spec_from_file_location("make_constants", os.path.join(GOLD, "make_constants.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    with tempfile.TemporaryDirectory() as d:
-        mod.HERE = d
-        mod.main()
-        assert json.load(open(os.path.join(d, "hfdl_constants.json"))) == K
-    # sanity of the parse itself: lengths and a few values no parser bug could fake
+    """The committed file is a sound parse (lengths and values no parser bug could fake) -- everywhere; where the reference tree
+    is available, re-parsing its text gives the committed file exactly."""
     assert len(K["matched_filter"]) == 19 and K["matched_filter"] == K["matched_filter"][::-1] and abs(sum(K["matched_filter"]) - 1.0) < 0.05
     assert sum(K["M1_bits"]) == 64 and len(K["M1_bits"]) == 127          # an m-sequence of length 127 has 64 ones
+    # ... and every cyclic shift but the trivial one agrees with it in 63 of 127 places (two-valued autocorrelation)
+    m1 = np.array(K["M1_bits"])
+    assert all(int((m1 == np.roll(m1, s)).sum()) == 63 for s in range(1, 127))
     assert K["defines"]["SINGLE_SLOT_FRAME_LEN"] == 448 + 531 + 72 * 45
+    if os.path.exists(REF):
+        import importlib.util
+        import tempfile
+        spec = importlib.util.spec_from_file_location("make_constants", os.path.join(GOLD, "make_constants.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        with tempfile.TemporaryDirectory() as d:
+            mod.HERE = d
+            mod.main()
+            assert json.load(open(os.path.join(d, "hfdl_constants.json"))) == K
 
 
 def test_product_constants_match_the_reference_text(sim, K):

@@ -2,6 +2,7 @@
 by _Static_asserts (tests/abi/hfdl_host_abi.c, every number derived from the reference line it cites) in BOTH builds of the host
 program -- default and WITH_SOAPYSDR (src/input-common.h:8-15: INPUT_TYPE_FILE is 1 or 2) -- and the one library binary serves both
 numberings at run time."""
+import json
 import os
 import re
 import subprocess
@@ -30,14 +31,34 @@ def test_static_asserts_bite(tmp_path):
     assert out.returncode != 0 and "INPUT_TYPE_FILE != 1" in out.stderr
 
 
+def input_type_enumerators(txt):
+    """[(enumerator, #ifdef guard or None), ...] of the `typedef enum {...} input_type;` in a C header's text."""
+    m = re.search(r"typedef enum \{([^}]*)\} input_type;", txt)
+    assert m, "no input_type enum"
+    out, guard = [], None
+    for line in m.group(1).splitlines():
+        line = line.strip()
+        if line.startswith("#ifdef"):
+            guard = line.split()[1]
+        elif line.startswith("#endif"):
+            guard = None
+        elif line:
+            out.append([line.rstrip(",").split("=")[0].strip(), guard])
+    return out
+
+
 def test_reference_enum_text_if_present():
-    """Where the reference tree is available (the build container), its own text says what the pins say."""
+    """The reference's input_type enum as tests/golden/input_type_enum.json records it (enumerators in order, the one under
+    WITH_SOAPYSDR marked) is what include/hfdl_host.h declares; where the reference tree is available, its own text says the same."""
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "input_type_enum.json")))["enumerators"]
+    assert gold[0] == ["INPUT_TYPE_UNDEF", None] and ["INPUT_TYPE_SOAPYSDR", "WITH_SOAPYSDR"] in gold
+    assert input_type_enumerators(open(os.path.join(ROOT, "include", "hfdl_host.h")).read()) == gold
     path = "/root/reference/src/input-common.h"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
-    txt = open(path).read()
-    m = re.search(r"typedef enum \{\s*INPUT_TYPE_UNDEF,\s*#ifdef WITH_SOAPYSDR\s*INPUT_TYPE_SOAPYSDR,\s*#endif\s*INPUT_TYPE_FILE,\s*INPUT_TYPE_MAX\s*\} input_type;", txt)
-    assert m, "the reference's input_type enum changed shape"
+    if os.path.exists(path):
+        txt = open(path).read()
+        m = re.search(r"typedef enum \{\s*INPUT_TYPE_UNDEF,\s*#ifdef WITH_SOAPYSDR\s*INPUT_TYPE_SOAPYSDR,\s*#endif\s*INPUT_TYPE_FILE,\s*INPUT_TYPE_MAX\s*\} input_type;", txt)
+        assert m, "the reference's input_type enum changed shape"
+        assert input_type_enumerators(txt) == gold
 
 
 @pytest.fixture(scope="module")
