@@ -43,12 +43,17 @@ __device__ __forceinline__ void store_out(float2 *out, const FftOutLayout &lay, 
 // The last `split` samples of the block are the next block's history: they are written to `hist_next` (a second buffer,
 // never the one being read) as they pass through, so no separate copy runs.
 template <int FMT>
-__global__ __launch_bounds__(FFT_THREADS) void fft_pass1(const float2 *__restrict__ hist, const void *__restrict__ fresh,
+__global__ __launch_bounds__(FFT_THREADS) void fft_pass1(const float2 *__restrict__ hist, FftInputs in,
 		int split, float2 *__restrict__ hist_next, float2 *__restrict__ out, FftPlan p, NcoJob job, int riders)
 {
 	// rider workgroups come FIRST in the grid: dispatched at once, they run beside the whole pass (at the end of the grid they would start when the pass is nearly over)
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
 	const int bid = (int)blockIdx.x - riders;
+	const int rx = (int)blockIdx.y;                // receiver (kernels.h FftInputs)
+	const void *__restrict__ fresh = in.fresh[rx];
+	if (hist != nullptr) hist += rx * in.hist_stride;
+	if (hist_next != nullptr) hist_next += rx * in.hist_stride;
+	out += (size_t)rx * (size_t)p.n;
 	extern __shared__ float2 sm[];
 	const int cs = p.n >> p.l1;            // R2*R3 columns
 	const int c0 = bid * FFT_TILE;
@@ -82,8 +87,9 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass1(const float2 *__restric
 __global__ __launch_bounds__(FFT_THREADS) void fft_pass2(float2 *__restrict__ buf, FftPlan p, NcoJob job, int riders)
 {
 	// rider workgroups come FIRST in the grid: dispatched at once, they run beside the whole pass (at the end of the grid they would start when the pass is nearly over)
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
 	const int bid = (int)blockIdx.x - riders;
+	buf += (size_t)blockIdx.y * (size_t)p.n;       // receiver
 	extern __shared__ float2 sm[];
 	const int r23 = p.n >> p.l1, ncol = p.r1 * p.r3;
 	const int cc0 = bid * FFT_TILE;
@@ -116,11 +122,13 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass2(float2 *__restrict__ bu
 // pass 3: for each (k1,k2): contiguous R3-point FFT; X[k1 + R1 k2 + R1 R2 k3] stored at (k + n/2) mod n
 // when `shifted` (fft_swap_sides as an index remap).  A tile is 16 adjacent k1 so stores stay 128-byte runs.
 __global__ __launch_bounds__(FFT_THREADS) void fft_pass3(const float2 *__restrict__ in, float2 *__restrict__ out, FftPlan p, int shifted,
-		FftOutLayout lay, NcoJob job, int riders)
+		FftOutLayout lay, NcoJob job, int riders, int64_t out_rx_stride)
 {
 	// rider workgroups come FIRST in the grid: dispatched at once, they run beside the whole pass (at the end of the grid they would start when the pass is nearly over)
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * FFT_THREADS + (int)threadIdx.x); return; }
 	const int bid = (int)blockIdx.x - riders;
+	in += (size_t)blockIdx.y * (size_t)p.n;        // receiver
+	out += blockIdx.y * out_rx_stride;
 	extern __shared__ float2 sm[];
 	const int r23 = p.n >> p.l1, ncol = p.r1 * p.r2;
 	const int cc0 = bid * FFT_TILE;
@@ -161,11 +169,16 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass3(const float2 *__restric
 // a CU, and without the look-ahead their load -> transform -> store phases ran one after the other (pass 3: 97 us in the pipeline
 // against 35 us alone, profiles/r05_experiments.md).
 template <int B, int FMT, bool AHEAD>
-__global__ __launch_bounds__(16 * B) void fft_rpass1(const float2 *__restrict__ hist, const void *__restrict__ fresh,
+__global__ __launch_bounds__(16 * B) void fft_rpass1(const float2 *__restrict__ hist, FftInputs in,
 		int split, float2 *__restrict__ hist_next, float2 *__restrict__ out, FftPlan p, NcoJob job, int riders, int tpw)
 {
 	constexpr int NT = 16 * B;
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	const int rx = (int)blockIdx.y;                // receiver (kernels.h FftInputs)
+	const void *__restrict__ fresh = in.fresh[rx];
+	if (hist != nullptr) hist += rx * in.hist_stride;
+	if (hist_next != nullptr) hist_next += rx * in.hist_stride;
+	out += (size_t)rx * (size_t)p.n;
 	__shared__ float2 ex[B * FR_PITCH];
 	__shared__ float2 ltw[16 * B];
 	const int bid = ((int)blockIdx.x - riders) * tpw, tid = (int)threadIdx.x;
@@ -217,7 +230,8 @@ template <int B, bool AHEAD>
 __global__ __launch_bounds__(16 * B) void fft_rpass2(float2 *__restrict__ buf, FftPlan p, NcoJob job, int riders, int tpw)
 {
 	constexpr int NT = 16 * B;
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	buf += (size_t)blockIdx.y * (size_t)p.n;       // receiver
 	__shared__ float2 ex[B * FR_PITCH];
 	__shared__ float2 ltw[16 * B];
 	const int bid = ((int)blockIdx.x - riders) * tpw, tid = (int)threadIdx.x;
@@ -263,10 +277,12 @@ __global__ __launch_bounds__(16 * B) void fft_rpass2(float2 *__restrict__ buf, F
 // sixteen points of a thread come out of LDS, and X[k1 + R1 k2 + R1 R2 k3] goes to (k + n/2) mod n when `shifted`
 template <int B>
 __global__ __launch_bounds__(16 * B) void fft_rpass3(const float2 *__restrict__ in, float2 *__restrict__ out, FftPlan p, int shifted,
-		FftOutLayout lay, NcoJob job, int riders, int tpw)
+		FftOutLayout lay, NcoJob job, int riders, int tpw, int64_t out_rx_stride)
 {
 	constexpr int NT = 16 * B, R = 16 * B;
-	if ((int)blockIdx.x < riders) { nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
+	in += (size_t)blockIdx.y * (size_t)p.n;        // receiver
+	out += blockIdx.y * out_rx_stride;
 	__shared__ float2 ex[B * FR_PITCH];                      // first the skewed input tile (R x 16 <= B x 272), then the exchange buffer
 	__shared__ float2 ltw[16 * B];
 	const int bid = ((int)blockIdx.x - riders) * tpw, tid = (int)threadIdx.x;
@@ -325,21 +341,24 @@ __global__ __launch_bounds__(16 * B) void fft_rpass3(const float2 *__restrict__ 
 }
 
 template <int B>
-static void launch_rpass1(int fmt, int grid, hipStream_t st, hipEvent_t start, hipEvent_t input_read, const float2 *hist, const void *fresh, int split, float2 *hist_next,
+static void launch_rpass1(int fmt, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t input_read, const float2 *hist, const FftInputs &in, int split, float2 *hist_next,
 		float2 *work, const FftPlan &p, const NcoJob &nco, int riders, int tpw)
 {
 	const dim3 blk(16 * B);
-	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CS16, false>), dim3(grid), blk, 0, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders, tpw);
-	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CU8, false>), dim3(grid), blk, 0, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders, tpw);
-	else hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CF32, false>), dim3(grid), blk, 0, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders, tpw);
+	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CS16, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
+	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CU8, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
+	else hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CF32, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
 }
 
 // the register-resident passes take radices 64 / 128 / 256 (N = 2^18 .. 2^24); smaller transforms keep the LDS radix-4 passes
 static bool fast_plan(const FftPlan &p) { return p.l1 >= 6 && p.l1 <= 8 && p.l2 >= 6 && p.l2 <= 8 && p.l3 >= 6 && p.l3 <= 8; }
 
-void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh, int fmt, int split, float2 *hist_next,
+// one three-pass sequence for all in.nrx receivers: grid dimension y = receiver (work holds nrx transforms, n apart)
+void launch_fft_forward(const FftPlan &p, const float2 *hist, const FftInputs &in, int fmt, int split, float2 *hist_next,
 		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay, hipEvent_t done, NcoJob nco, hipEvent_t input_read, hipEvent_t start)
 {
+	const unsigned nrx = (unsigned)in.nrx;
+	const int64_t ors = in.out_stride;
 	const int c1 = (p.n >> p.l1), c2 = p.r1 * p.r3, c3 = p.r1 * p.r2;
 	const int g1 = (c1 + FFT_TILE - 1) / FFT_TILE, g2 = (c2 + FFT_TILE - 1) / FFT_TILE, g3 = (c3 + FFT_TILE - 1) / FFT_TILE;
 	nco.nseg = 3;
@@ -354,21 +373,21 @@ void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh,
 		const int t1 = 1, t2 = 1, t3 = tpw_of(g3);
 		nco.seg = 0;
 		switch (p.l1) {
-		case 6: launch_rpass1<4>(fmt, g1 / t1 + rd1, st, start, input_read, hist, fresh, split, hist_next, work, p, nco, rd1, t1); break;
-		case 7: launch_rpass1<8>(fmt, g1 / t1 + rd1, st, start, input_read, hist, fresh, split, hist_next, work, p, nco, rd1, t1); break;
-		default: launch_rpass1<16>(fmt, g1 / t1 + rd1, st, start, input_read, hist, fresh, split, hist_next, work, p, nco, rd1, t1); break;
+		case 6: launch_rpass1<4>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
+		case 7: launch_rpass1<8>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
+		default: launch_rpass1<16>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
 		}
 		nco.seg = 1;
 		switch (p.l2) {
-		case 6: hipLaunchKernelGGL((fft_rpass2<4, false>), dim3(g2 / t2 + rd2), dim3(64), 0, st, work, p, nco, rd2, t2); break;
-		case 7: hipLaunchKernelGGL((fft_rpass2<8, false>), dim3(g2 / t2 + rd2), dim3(128), 0, st, work, p, nco, rd2, t2); break;
-		default: hipLaunchKernelGGL((fft_rpass2<16, false>), dim3(g2 / t2 + rd2), dim3(256), 0, st, work, p, nco, rd2, t2); break;
+		case 6: hipLaunchKernelGGL((fft_rpass2<4, false>), dim3(g2 / t2 + rd2, nrx), dim3(64), 0, st, work, p, nco, rd2, t2); break;
+		case 7: hipLaunchKernelGGL((fft_rpass2<8, false>), dim3(g2 / t2 + rd2, nrx), dim3(128), 0, st, work, p, nco, rd2, t2); break;
+		default: hipLaunchKernelGGL((fft_rpass2<16, false>), dim3(g2 / t2 + rd2, nrx), dim3(256), 0, st, work, p, nco, rd2, t2); break;
 		}
 		nco.seg = 2;
 		switch (p.l3) {
-		case 6: hipExtLaunchKernelGGL(fft_rpass3<4>, dim3(g3 / t3 + rd3), dim3(64), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3); break;
-		case 7: hipExtLaunchKernelGGL(fft_rpass3<8>, dim3(g3 / t3 + rd3), dim3(128), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3); break;
-		default: hipExtLaunchKernelGGL(fft_rpass3<16>, dim3(g3 / t3 + rd3), dim3(256), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3); break;
+		case 6: hipExtLaunchKernelGGL(fft_rpass3<4>, dim3(g3 / t3 + rd3, nrx), dim3(64), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
+		case 7: hipExtLaunchKernelGGL(fft_rpass3<8>, dim3(g3 / t3 + rd3, nrx), dim3(128), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
+		default: hipExtLaunchKernelGGL(fft_rpass3<16>, dim3(g3 / t3 + rd3, nrx), dim3(256), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
 		}
 		return;
 	}
@@ -377,14 +396,14 @@ void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh,
 	// tile + the radix's twiddle table
 	const size_t l1 = (size_t)p.r1 * (FFT_TILE + 1) * sizeof(float2), l2 = (size_t)p.r2 * (FFT_TILE + 1) * sizeof(float2);
 	nco.seg = 0;
-	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL(fft_pass1<SFMT_CS16>, dim3(g1 + riders), blk, l1, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders);
-	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL(fft_pass1<SFMT_CU8>, dim3(g1 + riders), blk, l1, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders);
-	else hipExtLaunchKernelGGL(fft_pass1<SFMT_CF32>, dim3(g1 + riders), blk, l1, st, start, input_read, 0, hist, fresh, split, hist_next, work, p, nco, riders);
+	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL(fft_pass1<SFMT_CS16>, dim3(g1 + riders, nrx), blk, l1, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders);
+	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL(fft_pass1<SFMT_CU8>, dim3(g1 + riders, nrx), blk, l1, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders);
+	else hipExtLaunchKernelGGL(fft_pass1<SFMT_CF32>, dim3(g1 + riders, nrx), blk, l1, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders);
 	nco.seg = 1;
-	hipLaunchKernelGGL(fft_pass2, dim3(g2 + riders), blk, l2, st, work, p, nco, riders);
+	hipLaunchKernelGGL(fft_pass2, dim3(g2 + riders, nrx), blk, l2, st, work, p, nco, riders);
 	nco.seg = 2;
-	hipExtLaunchKernelGGL(fft_pass3, dim3(g3 + riders), blk, (size_t)p.r3 * (FFT_TILE + 1) * sizeof(float2), st, nullptr, done, 0,
-			(const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, riders);
+	hipExtLaunchKernelGGL(fft_pass3, dim3(g3 + riders, nrx), blk, (size_t)p.r3 * (FFT_TILE + 1) * sizeof(float2), st, nullptr, done, 0,
+			(const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, riders, ors);
 }
 
 }  // namespace hfdl

@@ -43,11 +43,25 @@ __device__ __forceinline__ void cmac_quad(float2 &a, const float2 *h, const floa
 	for (int k = 0; k < n; k++) { a.x = __builtin_fmaf(-h[k].y, x[k].y, a.x); a.y = __builtin_fmaf(h[k].x, x[k].y, a.y); }
 }
 
-// reference / fallback: one thread per (channel, slice, bin), either tap layout, any geometry, `nb` blocks one after the other
+// the receiver of channel c (kernels.h Geometry::rx_tab; wave-uniform)
+__device__ __forceinline__ int rx_of_channel(const int4 *__restrict__ rx_tab, int nrx, int c)
+{
+	int r = 0;
+	while (r + 1 < nrx && c >= rx_tab[r + 1].z) r++;
+	return r;
+}
+
+// reference / fallback: one thread per (channel, slice, bin), either tap layout, any geometry, `nb` blocks one after the other; the
+// taps of channel c sit in its padded slot, the spectrum is its receiver's
 __global__ __launch_bounds__(FOLD_THREADS) void fold_ref_kernel(const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
-		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int layout, int nb)
+		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int layout, int nb,
+		const int4 *__restrict__ rx_tab, int nrx, size_t spec_rx_stride)
 {
 	const int s = blockIdx.x % slices, c = blockIdx.x / slices;
+	const int rxi = rx_of_channel(rx_tab, nrx, c);
+	const int4 rt = rx_tab[rxi];
+	const int slot = rt.x + (c - rt.z);
+	spec += (size_t)rxi * spec_rx_stride;
 	for (int b0 = 0; b0 < nb; b0 += 4)              // four blocks per pass over the taps
 		for (int j = threadIdx.x; j < m; j += FOLD_THREADS) {
 			const float2 *sp = spec + (size_t)b0 * spec_stride + (size_t)s * rows * (size_t)m + j;
@@ -55,7 +69,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_ref_kernel(const float *__r
 			for (int r = 0; r < rows; r += 4) {
 				const int n = rows - r < 4 ? rows - r : 4;
 				float2 h[4], x[4];
-				for (int k = 0; k < n; k++) h[k] = tap_at(taps, row_stride_f, m, layout, c, s * rows + r + k, j);
+				for (int k = 0; k < n; k++) h[k] = tap_at(taps, row_stride_f, m, layout, slot, s * rows + r + k, j);
 #pragma unroll
 				for (int b = 0; b < 4; b++)
 					if (b0 + b < nb) {
@@ -130,8 +144,8 @@ constexpr int fold16_waves(int p, int w, int d, bool small = false, int cg = 1)
 template <int P, int W, int D, bool WIN = false, bool SMALL = false, int CG = 1>
 __device__ __forceinline__ void fold_mfma16_body(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
-		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int octet_base, int nch, int nb,
-		const int2 *__restrict__ win)
+		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
 {
 	static_assert(!WIN || W == 1, "windows are per wave: no spectrum tile is shared");
 	static_assert(D == 2 || D == 4, "the LDS stage of a trip is a compile-time constant for even D");
@@ -173,12 +187,18 @@ __device__ __forceinline__ void fold_mfma16_body(
 	const int g = tile_id % ngrp, s = tile_id / ngrp;
 	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
 	const int n = lane & 15, k = lane >> 4;
-	const int octet0 = octet_base + (grp * W + wave) * P;
+	// The channel group of this workgroup (kernels.h FoldGroup, one scalar load): its first octet, its receiver -- whose spectrum it folds --
+	// and how its padded slots map to channels: slot c holds channel c + to_chan when c < slot_end (the slots past it carry zero taps and
+	// are not stored).  No group straddles two receivers.
+	const int4 ge = grp_tab[grp];
+	const int octet0 = __builtin_amdgcn_readfirstlane(ge.x) + wave * P;
+	const int slot_end = __builtin_amdgcn_readfirstlane(ge.z), to_chan = __builtin_amdgcn_readfirstlane(ge.w);
+	spec += (size_t)__builtin_amdgcn_readfirstlane(ge.y) * spec_rx_stride;
 	const int sign_mask = (lane & 1) ? 0 : (int)0x80000000;
 	const int quads = rows >> 2;
 	int next_quad = 0, trips = quads;                         // WIN: the next quad to ask for (circular), quads in the window
 	if constexpr (WIN) {
-		const int2 wn = win[(octet0 - octet_base) / P];
+		const int2 wn = win[octet0 / P];                      // one receiver: octet0 counts from 0
 		next_quad = __builtin_amdgcn_readfirstlane(wn.x);
 		trips = __builtin_amdgcn_readfirstlane(wn.y);
 	}
@@ -316,8 +336,9 @@ __device__ __forceinline__ void fold_mfma16_body(
 			for (int p = 0; p < P; p++)
 #pragma unroll
 				for (int cp = 0; cp < 2; cp++) {
-					const int c = 8 * (octet0 + p) + 2 * cpq + cp;
-					if (c >= nch) continue;
+					const int sl = 8 * (octet0 + p) + 2 * cpq + cp;
+					if (sl >= slot_end) continue;
+					const int c = sl + to_chan;
 					float2 *po = partial + (size_t)j * partial_stride + ((size_t)c * slices + s) * (size_t)m + g * 16 + k;
 #pragma unroll
 					for (int q = 0; q < 4; q++) po[4 * q] = make_float2(acc[p][q][2 * cp], acc[p][q][2 * cp + 1]);
@@ -335,8 +356,9 @@ __device__ __forceinline__ void fold_mfma16_body(
 			for (int p = 0; p < P; p++)
 #pragma unroll
 				for (int cp = 0; cp < 2; cp++) {
-					const int c = 8 * (octet0 + p) + 2 * k + cp;
-					if (c >= nch) continue;
+					const int sl = 8 * (octet0 + p) + 2 * k + cp;
+					if (sl >= slot_end) continue;
+					const int c = sl + to_chan;
 					const v4f *a = acc[p * CG + cg];
 					float2 *po = partial + (size_t)blk * partial_stride + ((size_t)c * slices + s) * (size_t)m + g * 16;
 #pragma unroll
@@ -359,10 +381,10 @@ __device__ __forceinline__ void fold_mfma16_body(
 template <int P, int W, int D, bool WIN = false, bool SMALL = false, int CG = 1>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(fold16_waves(P, W, D, SMALL, CG), fold16_waves(P, W, D, SMALL, CG)))) void fold_mfma16_kernel(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
-		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int octet_base, int nch, int nb,
-		const int2 *__restrict__ win)
+		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
 {
-	fold_mfma16_body<P, W, D, WIN, SMALL, CG>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, octet_base, nch, nb, win);
+	fold_mfma16_body<P, W, D, WIN, SMALL, CG>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride);
 }
 
 #ifdef HFDL_LAB
@@ -371,10 +393,10 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(fold16_w
 // (104 + 104); the compiler keeps the loop free of scratch at that (one 8-byte spill before the loop, reloaded after it).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) __attribute__((amdgpu_num_vgpr(104))) void fold32_two_waves_kernel(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
-		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int octet_base, int nch, int nb,
-		const int2 *__restrict__ win)
+		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
 {
-	fold_mfma16_body<1, 8, 2, false, false, 2>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, octet_base, nch, nb, win);
+	fold_mfma16_body<1, 8, 2, false, false, 2>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride);
 }
 #endif
 
@@ -438,6 +460,17 @@ struct FoldArgs {
 	float2 *partial;
 	size_t rs_f, ss, ps;
 	int m, slices, rows, nch, ngroups, nb;            // ngroups: channel groups of the tap layout (octets / pairs) the buffer holds
+	const int4 *grp_tab, *rx_host;                    // receivers (kernels.h Geometry::grp_tab / rx_host): each pads its channels to whole groups
+	int nrx;
+	size_t spec_rx_stride;
+	// workgroups of `pw` octets over all receivers, and the octets left over (no workgroup straddles two receivers); the table of their
+	// FoldGroup entries: the full groups, then the left-over octets
+	void split(int pw, int &groups, int &rest) const
+	{
+		groups = rest = 0;
+		for (int r = 0; r < nrx; r++) { const int noct = rx_host[r].y >> 3; groups += noct / pw; rest += noct % pw; }
+	}
+	const int4 *table(int pw) const { return grp_tab + (size_t)(pw - 1) * (size_t)(ngroups); }
 	hipStream_t st;
 	hipEvent_t start, stop;
 };
@@ -446,19 +479,21 @@ struct FoldArgs {
 template <int P, int W, int D, bool SMALL = false, int CG = 1>
 static int fold16_go(const FoldArgs &a)
 {
+	static_assert(P * W <= FOLD_GROUP_MAX, "the group tables of the front end go up to FOLD_GROUP_MAX octets per workgroup");
 	const int ntile = (a.m >> 4) * a.slices;
-	const int groups = a.ngroups / (P * W), rest = a.ngroups - groups * P * W;
+	int groups, rest;
+	a.split(P * W, groups, rest);
 	int launches = 0;
 	if (groups > 0) {
 		hipExtLaunchKernelGGL((fold_mfma16_kernel<P, W, D, false, SMALL, CG>), dim3((unsigned)(groups * ntile)), dim3(64 * W), 0, a.st, a.start, rest ? nullptr : a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, 0, a.nch, a.nb, (const int2 *)nullptr);
+			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(P * W), a.spec_rx_stride);
 		launches++;
 	}
 	if (rest > 0) {
 		// (a single wave fetches the whole spectrum tile itself: two quads in flight keep that within its registers when the tile is 32 blocks wide)
 		constexpr int DR = CG > 1 ? 2 : D;
 		hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, DR, false, SMALL, CG>), dim3((unsigned)(rest * ntile)), dim3(64), 0, a.st, groups > 0 ? nullptr : a.start, a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, groups * P * W, a.nch, a.nb, (const int2 *)nullptr);
+			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(P * W) + groups, a.spec_rx_stride);
 		launches++;
 	}
 	return launches;
@@ -468,16 +503,17 @@ static int fold16_go(const FoldArgs &a)
 static int fold32_two_waves_go(const FoldArgs &a)
 {
 	const int ntile = (a.m >> 4) * a.slices;
-	const int groups = a.ngroups / 8, rest = a.ngroups - groups * 8;
+	int groups, rest;
+	a.split(8, groups, rest);
 	int launches = 0;
 	if (groups > 0) {
 		hipExtLaunchKernelGGL(fold32_two_waves_kernel, dim3((unsigned)(groups * ntile)), dim3(512), 0, a.st, a.start, rest ? nullptr : a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, 0, a.nch, a.nb, (const int2 *)nullptr);
+			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(8), a.spec_rx_stride);
 		launches++;
 	}
 	if (rest > 0) {
 		hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, 2, false, false, 2>), dim3((unsigned)(rest * ntile)), dim3(64), 0, a.st, groups > 0 ? nullptr : a.start, a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, groups * 8, a.nch, a.nb, (const int2 *)nullptr);
+			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(8) + groups, a.spec_rx_stride);
 		launches++;
 	}
 	return launches;
@@ -490,7 +526,7 @@ static int fold16_go_win(const FoldArgs &a, const int2 *win)
 {
 	const int ntile = a.m >> 4;
 	hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, D, true>), dim3((unsigned)(a.ngroups * ntile)), dim3(64), 0, a.st, a.start, a.stop, 0,
-		a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, 1, a.rows, 0, a.nch, a.nb, win);
+		a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, 1, a.rows, a.nb, win, a.table(1), a.spec_rx_stride);
 	return 1;
 }
 
@@ -556,6 +592,7 @@ static FoldArgs fold_args(const Geometry &g, const float2 *taps, const float2 *s
 	a.taps = (const float *)taps; a.spec = spectrum; a.partial = partial;
 	a.rs_f = (size_t)g.tap_row_stride * 2; a.ss = spec_stride; a.ps = partial_stride;
 	a.m = g.m; a.slices = g.slices; a.rows = g.rows_per_slice; a.nch = g.nch; a.ngroups = g.nch_pad / tap_layout_group(g.tap_layout); a.nb = nb;
+	a.grp_tab = g.grp_tab; a.rx_host = g.rx_host; a.nrx = g.nrx; a.spec_rx_stride = (size_t)g.spec_rx_stride;
 	a.st = st; a.start = start; a.stop = stop;
 	return a;
 }
@@ -564,7 +601,8 @@ static void launch_fold_ref(const Geometry &g, const float2 *taps, const float2 
 		int nb, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
 	hipExtLaunchKernelGGL(fold_ref_kernel, dim3((unsigned)(g.nch * g.slices)), dim3(FOLD_THREADS), 0, st, start, stop, 0,
-		(const float *)taps, spectrum, partial, (size_t)g.tap_row_stride * 2, spec_stride, partial_stride, g.m, g.slices, g.rows_per_slice, g.tap_layout, nb);
+		(const float *)taps, spectrum, partial, (size_t)g.tap_row_stride * 2, spec_stride, partial_stride, g.m, g.slices, g.rows_per_slice, g.tap_layout, nb,
+		g.rx_tab, g.nrx, (size_t)g.spec_rx_stride);
 }
 
 int launch_fold_variant(int v, const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial,
@@ -618,7 +656,7 @@ void launch_tap_row_energy(const float2 *taps, const Geometry &g, float *energy,
 	hipLaunchKernelGGL(tap_row_energy_kernel, dim3((unsigned)((g.pre >> 2) * noct)), dim3(FOLD_THREADS), 0, st, (const float *)taps, energy, (size_t)g.tap_row_stride * 2, g.m, noct, g.nch_pad);
 }
 
-// filter taps of one channel back in plain order (HFDL_GPU_TAP_FILTER): dst[N] cf32
+// filter taps of one padded slot back in plain order (HFDL_GPU_TAP_FILTER): dst[N] cf32
 __global__ __launch_bounds__(FOLD_THREADS) void tap_extract_kernel(const float *__restrict__ taps, float2 *__restrict__ dst, size_t row_stride_f, int m, int pre, int layout, int c)
 {
 	const size_t n = (size_t)m * pre;
@@ -626,9 +664,9 @@ __global__ __launch_bounds__(FOLD_THREADS) void tap_extract_kernel(const float *
 		dst[e] = tap_at(taps, row_stride_f, m, layout, c, (int)(e / m), (int)(e % m));
 }
 
-void launch_tap_extract(const float2 *taps, const Geometry &g, int channel, float2 *dst, hipStream_t st)
+void launch_tap_extract(const float2 *taps, const Geometry &g, int slot, float2 *dst, hipStream_t st)
 {
-	hipLaunchKernelGGL(tap_extract_kernel, dim3(1024), dim3(FOLD_THREADS), 0, st, (const float *)taps, dst, (size_t)g.tap_row_stride * 2, g.m, g.pre, g.tap_layout, channel);
+	hipLaunchKernelGGL(tap_extract_kernel, dim3(1024), dim3(FOLD_THREADS), 0, st, (const float *)taps, dst, (size_t)g.tap_row_stride * 2, g.m, g.pre, g.tap_layout, slot);
 }
 
 // ---- inverse FFT + scrap + NCO/decimate : one workgroup per channel, M bins in LDS ----

@@ -144,12 +144,22 @@ struct hfdl_gpu_frontend {
 	uint64_t host_pushed = 0;           // ... of which this many have been pushed (or cancelled): the rest wait in the prefetch queue, oldest first
 	const void *pf_ptr[MAX_STAGE] = {}; // prefetch queue entry of host block j at [j % n_stage]: the host pointer ...
 	int pf_fmt[MAX_STAGE] = {};         // ... and its sample format
-	int32_t sample_rate = 0, centerfreq = 0, decimation = 0;
+	int32_t sample_rate = 0, decimation = 0;
 	float tbw = 0;
 	Plan plan{};                       // shift = 0 geometry (src/fft.c:70-86)
 	Geometry geo{};
 	HostFftPlan fft;
 	std::vector<int32_t> freqs;
+	// Receivers (hfdl_gpu_frontend_create_multi): one stream of input_size samples per receiver and step, channels receiver-major.  Every
+	// per-block buffer of the forward FFT holds one transform per receiver: overlap history [2][nrx][overlap], work [nrx][N], spectra
+	// [set][block][nrx][N], staging buffers [nrx][input_size]; from the fold on, everything is per channel as with one receiver.
+	int nrx = 1;
+	std::vector<int32_t> rx_center;     // [nrx] centre frequencies
+	std::vector<int32_t> rx_of;         // [nch] receiver of each channel
+	std::vector<RxSpan> rx_span;        // [nrx] padded tap slots and channels of each receiver (planner.h plan_receiver_slots)
+	std::vector<int4> rx_host;          // the same as the kernels read it (Geometry::rx_tab / rx_host)
+	int4 *d_rx = nullptr, *d_grp = nullptr;      // device copies: receiver table, fold group tables (kernels.h Geometry::grp_tab)
+	int slot_of(int c) const { return receiver_slot(rx_span[(size_t)rx_of[(size_t)c]], c); }
 	std::vector<ChanConst> cc;
 	float2 *d_hist[2] = { nullptr, nullptr }, *d_work = nullptr, *d_spec = nullptr, *d_taps = nullptr, *d_partial = nullptr;
 	float2 *d_tw_m = nullptr, *d_stage[MAX_STAGE] = {};
@@ -175,7 +185,8 @@ struct hfdl_gpu_frontend {
 	// spectra, NCO phasor tables and carried-state snapshots of a half: two sets (the forward FFTs of half k+1 fill one while the fold
 	// and inverse FFTs of half k read the other); `set` = cur_half of the half they belong to
 	int last_set = 0;                   // set of the newest channelized half: what the taps read
-	float2 *spec_slot(int set, int i) const { return d_spec + ((size_t)set * (size_t)half_blocks + (size_t)i) * (size_t)geo.n; }
+	float2 *spec_slot(int set, int i) const { return d_spec + ((size_t)set * (size_t)half_blocks + (size_t)i) * spec_stride(); }
+	size_t spec_stride() const { return (size_t)nrx * (size_t)geo.n; }     // between the spectra of consecutive blocks (receiver r at + r N)
 	float2 *ph_slot(int set, int i) const { return d_ph + ((size_t)set * (size_t)half_blocks + (size_t)i) * ph_stride(); }
 	NcoState *snap_slot(int set, int i) const { return d_nco_snap + ((size_t)set * (size_t)half_blocks + (size_t)i) * (size_t)geo.nch; }
 	size_t partial_stride() const { return (size_t)geo.nch * (size_t)geo.slices * (size_t)geo.m; }
@@ -249,7 +260,7 @@ static void frontend_free(hfdl_gpu_frontend *fe)
 	fe->demod.release();
 	fe->fft.release();
 	void *ptrs[] = { fe->d_hist[0], fe->d_hist[1], fe->d_work, fe->d_spec, fe->d_taps, fe->d_partial, fe->d_chan_all, fe->d_tw_m,
-		fe->d_cc, fe->d_nco, fe->d_nco_snap, fe->d_ph, fe->d_ph_cont, fe->d_cnt_all, fe->d_win };
+		fe->d_cc, fe->d_nco, fe->d_nco_snap, fe->d_ph, fe->d_ph_cont, fe->d_cnt_all, fe->d_win, fe->d_rx, fe->d_grp };
 	for (void *p : ptrs) if (p) (void)hipFree(p);
 	for (float2 *p : fe->d_stage) if (p) (void)hipFree(p);
 	if (fe->stream) (void)hipStreamDestroy(fe->stream);
@@ -414,8 +425,8 @@ static int build_taps(hfdl_gpu_frontend *fe)
 		for (;;) {
 			int c = next.fetch_add(1);
 			if (c >= nch) break;
-			// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency
-			float shift = (float)(fe->centerfreq - (fe->freqs[c] + 1440)) / (float)fe->sample_rate;
+			// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency -- from the centre of ITS receiver
+			float shift = (float)(fe->rx_center[(size_t)fe->rx_of[(size_t)c]] - (fe->freqs[c] + 1440)) / (float)fe->sample_rate;
 			Plan cp;
 			if (!plan_block(cp, fe->tbw, fe->decimation, shift)) { bad++; continue; }
 			ChanConst k{};
@@ -438,15 +449,16 @@ static int build_taps(hfdl_gpu_frontend *fe)
 	HIP_TRY(pad.alloc(sizeof(float2) * n));
 	float2 *d_pad = pad.as<float2>();
 	HIP_TRY(hipMemsetAsync(d_pad, 0, sizeof(float2) * n, fe->stream));
-	if (fe->geo.nch_pad > nch)          // the channels that fill the last group of the interleaved layout up: all-zero taps
+	if (fe->geo.nch_pad > nch)          // the slots that fill each receiver's last group of the interleaved layout up: all-zero taps
 		HIP_TRY(hipMemsetAsync(fe->d_taps, 0, sizeof(float2) * n * (size_t)fe->geo.nch_pad, fe->stream));
 	for (int c = 0; c < nch; c++) {
 		HIP_TRY(hipMemcpyAsync(d_pad, host.data() + (size_t)c * pl.taps_length, sizeof(float2) * (size_t)pl.taps_length,
 				hipMemcpyHostToDevice, fe->stream));
-		// the last pass writes the channel's filter straight into the matrix-operand layout (kernels.h tap_index_f)
+		// the last pass writes the channel's filter straight into the matrix-operand layout (kernels.h tap_index_f), at its padded slot
+		const int slot = fe->slot_of(c);
 		FftOutLayout lay = fe->tap_layout;
-		lay.chan = c;
-		float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)c * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
+		lay.chan = slot;
+		float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
 		launch_fft_forward(fe->fft.p, nullptr, d_pad, SFMT_CF32, 0, nullptr, fe->d_work, dst, true, fe->stream, lay);
 	}
 	HIP_TRY(hipStreamSynchronize(fe->stream));
@@ -454,27 +466,49 @@ static int build_taps(hfdl_gpu_frontend *fe)
 	return 0;
 }
 
+// Every argument is checked here, before a device is selected (the checks need no GPU)
+static int check_create_args(hfdl_gpu_frontend **out, int32_t sample_rate, int32_t nrx, const int32_t *centerfreqs, const int32_t *freqs,
+		const int32_t *nch_per_rx)
+{
+	if (!out || !centerfreqs || !freqs || !nch_per_rx) return fail(HFDL_GPU_EINVAL, "bad arguments: null pointer");
+	*out = nullptr;
+	if (nrx < 1 || nrx > HFDL_GPU_RECEIVERS_MAX) return fail(HFDL_GPU_EINVAL, "bad arguments: %d receivers (1 .. %d)", nrx, HFDL_GPU_RECEIVERS_MAX);
+	for (int r = 0; r < nrx; r++)
+		if (nch_per_rx[r] <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments: receiver %d has %d channels", r, nch_per_rx[r]);
+	if (sample_rate < 5400) return fail(HFDL_GPU_EINVAL, "sample rate must be >= 5400 (src/main.c:638-641)");
+	for (int r = 0, c = 0; r < nrx; r++)
+		for (int i = 0; i < nch_per_rx[r]; i++, c++)
+			// span check of src/main.c:214-226, against the channel's own receiver
+			if (std::abs((int64_t)centerfreqs[r] - freqs[c]) >= sample_rate / 2)
+				return nrx == 1 ? fail(HFDL_GPU_EINVAL, "channel %d Hz outside +-fs/2 of centre %d", freqs[c], centerfreqs[r])
+				                : fail(HFDL_GPU_EINVAL, "channel %d (%d Hz) outside +-fs/2 of the centre %d of its receiver %d", c, freqs[c], centerfreqs[r], r);
+	return 0;
+}
+
 extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t centerfreq,
 		const int32_t *freqs, int32_t nch)
 {
 	if (!out || !freqs || nch <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	*out = nullptr;
-	if (sample_rate < 5400) return fail(HFDL_GPU_EINVAL, "sample rate must be >= 5400 (src/main.c:638-641)");
-	int rc = select_device(device);
+	return hfdl_gpu_frontend_create_multi(out, device, sample_rate, 1, &centerfreq, freqs, &nch);
+}
+
+extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx,
+		const int32_t *centerfreqs, const int32_t *freqs, const int32_t *nch_per_rx)
+{
+	int rc = check_create_args(out, sample_rate, nrx, centerfreqs, freqs, nch_per_rx);
 	if (rc) return rc;
+	int32_t nch = 0;
+	for (int r = 0; r < nrx; r++) nch += nch_per_rx[r];
+	if ((rc = select_device(device))) return rc;
 	auto *fe = new hfdl_gpu_frontend();
 	fe->device = device;
-	fe->sample_rate = sample_rate; fe->centerfreq = centerfreq;
+	fe->sample_rate = sample_rate;
 	fe->decimation = fft_decimation_rate(sample_rate, 1800 * 3);
 	fe->tbw = relative_transition_bw(sample_rate, 250);
 	fe->freqs.assign(freqs, freqs + nch);
-	for (int32_t f : fe->freqs) {
-		// span check of src/main.c:214-226
-		if (std::abs((int64_t)centerfreq - f) >= sample_rate / 2) {
-			delete fe;
-			return fail(HFDL_GPU_EINVAL, "channel %d Hz outside +-fs/2 of centre %d", f, centerfreq);
-		}
-	}
+	fe->nrx = nrx;
+	fe->rx_center.assign(centerfreqs, centerfreqs + nrx);
+	for (int r = 0; r < nrx; r++) fe->rx_of.insert(fe->rx_of.end(), (size_t)nch_per_rx[r], r);
 	if (!plan_block(fe->plan, fe->tbw, fe->decimation, 0.f)) { delete fe; return fail(HFDL_GPU_EINVAL, "fastddc planning failed"); }
 	const Plan &pl = fe->plan;
 	Geometry &g = fe->geo;
@@ -485,10 +519,12 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 	// channels, which walk the rows together, stream through a few moving windows of HBM instead of nch windows 8N bytes
 	// apart (fold kernel 2.58 -> 2.48 ms on cfg3 and a tighter run-to-run spread, profiles/r01_experiments.md)
 	g.tap_layout = (pl.m % 16) == 0 && (pl.pre % 8) == 0 ? TAPL_OCTET : TAPL_PLAIN;       // the matrix-pipe fold walks the alias rows four at a time, two such quads in flight
-	{
-		const int grp = tap_layout_group(g.tap_layout);
-		g.nch_pad = (nch + grp - 1) / grp * grp;
-	}
+	// each receiver's channels padded to whole groups of the layout on their own (one receiver: nch rounded up, as always)
+	g.nch_pad = plan_receiver_slots(nch_per_rx, nrx, tap_layout_group(g.tap_layout), fe->rx_span);
+	for (const RxSpan &r : fe->rx_span) fe->rx_host.push_back(make_int4(r.slot0, r.slots, r.chan0, r.nch));
+	g.nrx = nrx;
+	g.spec_rx_stride = pl.n;
+	g.rx_host = fe->rx_host.data();
 	g.tap_chan_stride = pl.m; g.tap_row_stride = (int64_t)g.nch_pad * pl.m;
 	fe->tap_layout.kind = g.tap_layout;
 	fe->tap_layout.row_log = ilog2(pl.m); fe->tap_layout.row_stride = g.tap_row_stride;
@@ -502,7 +538,8 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 		if (sl > 0 && (sl & (sl - 1)) == 0 && pl.pre % sl == 0 && pl.pre / sl >= 16) g.slices = sl;
 	}
 #endif
-	fe->prune_tol = g.tap_layout == TAPL_OCTET ? env_double("HFDL_GPU_FOLD_PRUNE", 1e-12, 1e-3, 0.0) : 0.0;
+	// (the pruned fold's windows are per octet of ONE receiver's taps: off with several receivers)
+	fe->prune_tol = g.tap_layout == TAPL_OCTET && nrx == 1 ? env_double("HFDL_GPU_FOLD_PRUNE", 1e-12, 1e-3, 0.0) : 0.0;
 	if (fe->prune_tol > 0) g.slices = 1;
 	g.rows_per_slice = pl.pre / g.slices;
 	if (pl.m > 8192 || pl.m < 16) { delete fe; return fail(HFDL_GPU_ERANGE, "inverse FFT size %d unsupported", pl.m); }
@@ -570,11 +607,22 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 	}
 	if ((rc = fe->fft.build(pl.n))) { frontend_free(fe); return rc; }
 	const size_t n = (size_t)pl.n;
-	for (int i = 0; i < 2; i++) {      // overlap history, ping-pong: block k reads [k&1] and leaves the next one in [(k+1)&1]
-		FE_TRY(hipMalloc(&fe->d_hist[i], sizeof(float2) * (size_t)pl.overlap));
-		FE_TRY(hipMemsetAsync(fe->d_hist[i], 0, sizeof(float2) * (size_t)pl.overlap, fe->stream));   // calloc'ed history, src/fft.c:79
+	const size_t K = (size_t)nrx;
+	for (int i = 0; i < 2; i++) {      // overlap history, ping-pong: block k reads [k&1] and leaves the next one in [(k+1)&1]; one per receiver
+		FE_TRY(hipMalloc(&fe->d_hist[i], sizeof(float2) * (size_t)pl.overlap * K));
+		FE_TRY(hipMemsetAsync(fe->d_hist[i], 0, sizeof(float2) * (size_t)pl.overlap * K, fe->stream));   // calloc'ed history, src/fft.c:79
 	}
-	FE_TRY(hipMalloc(&fe->d_work, sizeof(float2) * n));
+	FE_TRY(hipMalloc(&fe->d_work, sizeof(float2) * n * K));
+	FE_TRY(hipMalloc(&fe->d_rx, sizeof(int4) * K));
+	FE_TRY(hipMemcpy(fe->d_rx, fe->rx_host.data(), sizeof(int4) * K, hipMemcpyHostToDevice));
+	g.rx_tab = fe->d_rx;
+	if (g.tap_layout == TAPL_OCTET) {
+		static_assert(sizeof(FoldGroup) == sizeof(int4), "a FoldGroup entry is what the fold kernels load as an int4");
+		const std::vector<FoldGroup> t = fold_group_tables(fe->rx_span, g.nch_pad / 8, FOLD_GROUP_MAX);
+		FE_TRY(hipMalloc(&fe->d_grp, sizeof(int4) * t.size()));
+		FE_TRY(hipMemcpy(fe->d_grp, t.data(), sizeof(int4) * t.size(), hipMemcpyHostToDevice));
+		g.grp_tab = fe->d_grp;
+	}
 	FE_TRY(hipMalloc(&fe->d_taps, sizeof(float2) * n * (size_t)g.nch_pad));
 	FE_TRY(hipMalloc(&fe->d_nco, sizeof(NcoState) * (size_t)nch));
 	FE_TRY(hipMemsetAsync(fe->d_nco, 0, sizeof(NcoState) * (size_t)nch, fe->stream));
@@ -596,6 +644,17 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 	float resamp_rate = (float)(1800 * 3) / ((float)sample_rate / (float)fe->decimation);
 	fe->fold_nb = pick_fold_batch(fe);
 	int want_batch = Demod::fit_batch(g.outs, resamp_rate, pick_demod_batch(fe));       // what fits the demodulator's LDS
+	if (nrx > 1) {
+		// The per-block buffers of the forward FFT scale with the receivers (spectra: two sets x half x K x N cf32; staging ring, overlap
+		// history, work): a half holds at most 32 x 2^23 / (K N) blocks -- the single-receiver cfg3 footprint (32 blocks of 2^23 bins),
+		// known to fit.  Where that binds, the fold batch (and with it the half and the staging ring) shrinks, never below one block, and
+		// the demodulator batch is clamped to the half.
+		const int64_t cap = std::max<int64_t>(1, ((int64_t)32 << 23) / ((int64_t)nrx * (int64_t)pl.n));
+		if (cap < std::max(fe->fold_nb, want_batch)) {
+			fe->fold_nb = (int)std::min<int64_t>(fe->fold_nb, cap);
+			want_batch = std::min(want_batch, fe->fold_nb);
+		}
+	}
 	if (!getenv("HFDL_GPU_DEMOD_BATCH") && want_batch < fe->fold_nb) {
 		// even launches: a half of 8 blocks at up to 7 per launch is two launches of 4, not 7 + 1 (cfg2: 5.5 against 5.8 Gsamples/s); an
 		// explicit HFDL_GPU_DEMOD_BATCH is taken as it is
@@ -616,7 +675,7 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 		FE_TRY(hipEventCreateWithFlags(&fe->ev_stage_free[i], hipEventDisableTiming));
 	}
 	const size_t hb = (size_t)fe->half_blocks;
-	FE_TRY(hipMalloc(&fe->d_spec, sizeof(float2) * n * 2 * hb));
+	FE_TRY(hipMalloc(&fe->d_spec, sizeof(float2) * fe->spec_stride() * 2 * hb));
 	FE_TRY(hipMalloc(&fe->d_partial, sizeof(float2) * fe->partial_stride() * hb));
 	FE_TRY(hipMalloc(&fe->d_ph, sizeof(float2) * fe->ph_stride() * 2 * hb));
 	FE_TRY(hipMalloc(&fe->d_nco_snap, sizeof(NcoState) * (size_t)nch * 2 * hb));
@@ -703,40 +762,49 @@ extern "C" void *hfdl_gpu_frontend_stream(hfdl_gpu_frontend *fe) { return fe ? (
 
 static size_t sample_bytes(int fmt) { return fmt == SFMT_CS16 ? 4 : fmt == SFMT_CU8 ? 2 : 8; }
 
-// queue the host -> device copy of the next host block on stream C into staging buffer host_blocks % n_stage
-static int queue_input_copy(hfdl_gpu_frontend *fe, const void *iq, size_t nsamples, int fmt, int *sb_out)
+// queue the host -> device copy of the next host block -- one block of every receiver, iq[0 .. nrx - 1] -- on stream C into staging
+// buffer host_blocks % n_stage (receiver r at r * nsamples samples)
+static int queue_input_copy(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int fmt, int *sb_out)
 {
 	// buffer j % n_stage is freed by the forward FFT of host block j - n_stage: that block must have been pushed
 	if (fe->host_blocks - fe->host_pushed >= (uint64_t)fe->n_stage)
 		return fail(HFDL_GPU_ERANGE, "%d uploads are queued ahead of their blocks: push the oldest first", fe->n_stage);
 	const uint64_t j = fe->host_blocks;
 	const int sb = (int)(j % (uint64_t)fe->n_stage);
-	if (fe->stage_cap[sb] < nsamples) {
+	const size_t need = nsamples * (size_t)fe->nrx;
+	if (fe->stage_cap[sb] < need) {
 		HIP_TRY(hipStreamSynchronize(fe->stream_c));
 		HIP_TRY(hipStreamSynchronize(fe->stream_f));
 		if (fe->d_stage[sb]) (void)hipFree(fe->d_stage[sb]);
 		fe->d_stage[sb] = nullptr; fe->stage_cap[sb] = 0;
-		HIP_TRY(hipMalloc(&fe->d_stage[sb], sizeof(float2) * nsamples));
-		fe->stage_cap[sb] = nsamples;
+		HIP_TRY(hipMalloc(&fe->d_stage[sb], sizeof(float2) * need));
+		fe->stage_cap[sb] = need;
 	}
 	HIP_TRY(hipStreamWaitEvent(fe->stream_c, fe->ev_stage_free[sb], 0));     // the forward FFT that read this buffer last is past its first pass
 	// (one hipMemcpyAsync per block: cutting a block in 2 or 4 pieces on as many streams was measured and is slower, profiles/r03_experiments.md)
-	HIP_TRY(hipMemcpyAsync(fe->d_stage[sb], iq, sample_bytes(fmt) * nsamples, hipMemcpyHostToDevice, fe->stream_c));
+	const size_t bytes = sample_bytes(fmt) * nsamples;
+	bool pinned = true;
+	for (int r = 0; r < fe->nrx; r++) {
+		HIP_TRY(hipMemcpyAsync((char *)fe->d_stage[sb] + (size_t)r * bytes, iq[r], bytes, hipMemcpyHostToDevice, fe->stream_c));
+		pinned = pinned && is_library_pinned(iq[r], bytes);
+	}
 	HIP_TRY(hipEventRecord(fe->ev_stage_ready[sb], fe->stream_c));
 	fe->host_blocks = j + 1;
 	// a buffer this library did not allocate may be reused by the caller as soon as we return (include/hfdl_gpu.h): do not
 	// rely on the runtime staging pageable memory synchronously -- wait for the copy (the kernels of the previous block keep running)
-	if (!is_library_pinned(iq, sample_bytes(fmt) * nsamples)) HIP_TRY(hipStreamSynchronize(fe->stream_c));
+	if (!pinned) HIP_TRY(hipStreamSynchronize(fe->stream_c));
 	*sb_out = sb;
 	return 0;
 }
 
 // Host input is staged in HBM: the copies (stream C) run up to a whole half ahead of the blocks that compute (stream A).
+// iq[0 .. nrx - 1]: one block of every receiver; in.fresh[] receives where the forward FFT reads them.
 // *stage_idx = staging buffer used (-1 for device input): the forward FFT's first pass signals ev_stage_free when it has read it.
-static int stage_input(hfdl_gpu_frontend *fe, const void *iq, size_t nsamples, int fmt, int on_device, const void **dev, int *stage_idx)
+static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int fmt, int on_device, FftInputs &in, int *stage_idx)
 {
 	*stage_idx = -1;
 	if (!fe || !iq) return fail(HFDL_GPU_EINVAL, "null argument");
+	for (int r = 0; r < fe->nrx; r++) if (!iq[r]) return fail(HFDL_GPU_EINVAL, "null argument: the block of receiver %d", r);
 	if (fmt != SFMT_CF32 && fmt != SFMT_CS16 && fmt != SFMT_CU8) return fail(HFDL_GPU_EINVAL, "unknown sample format %d", fmt);
 	if (nsamples != (size_t)fe->plan.input_size)
 		return fail(HFDL_GPU_EINVAL, "a block is exactly %d samples (got %zu)", fe->plan.input_size, nsamples);
@@ -745,22 +813,30 @@ static int stage_input(hfdl_gpu_frontend *fe, const void *iq, size_t nsamples, i
 	if (on_device) {
 		// the prefetched host blocks are numbered and staged: a device block slipped in front of them would be processed out of order
 		if (queued) return fail(HFDL_GPU_EINVAL, "a prefetched block is pending: push it or call hfdl_gpu_frontend_prefetch_cancel()");
-		*dev = iq;
+		for (int r = 0; r < fe->nrx; r++) in.fresh[r] = iq[r];
 		return 0;
 	}
 	int sb;
 	if (queued) {
-		// the copy of this block was queued ahead by hfdl_gpu_frontend_prefetch_block_raw(): blocks are pushed in the order they were prefetched
+		// the copy of this block was queued ahead by hfdl_gpu_frontend_prefetch_block_raw() (one receiver only): blocks are pushed in the order they were prefetched
 		sb = (int)(fe->host_pushed % (uint64_t)fe->n_stage);
-		if (fe->pf_ptr[sb] != iq || fe->pf_fmt[sb] != fmt) return fail(HFDL_GPU_EINVAL, "the block pushed after a prefetch must be the (oldest) prefetched one");
+		if (fe->pf_ptr[sb] != iq[0] || fe->pf_fmt[sb] != fmt) return fail(HFDL_GPU_EINVAL, "the block pushed after a prefetch must be the (oldest) prefetched one");
 	} else {
 		int rc = queue_input_copy(fe, iq, nsamples, fmt, &sb);
 		if (rc) return rc;
 	}
 	fe->host_pushed++;
 	HIP_TRY(hipStreamWaitEvent(fe->stream_f, fe->ev_stage_ready[sb], 0));
-	*dev = fe->d_stage[sb];
+	for (int r = 0; r < fe->nrx; r++) in.fresh[r] = (const char *)fe->d_stage[sb] + (size_t)r * sample_bytes(fmt) * nsamples;
 	*stage_idx = sb;
+	return 0;
+}
+
+// the entry points that take ONE stream's block: a front end of several receivers needs a block of every receiver per step
+static int single_receiver_only(const hfdl_gpu_frontend *fe, const char *what)
+{
+	if (fe && fe->nrx > 1)
+		return fail(HFDL_GPU_EINVAL, "%s: this front end has %d receivers -- push a block of every receiver with hfdl_gpu_frontend_push_blocks_raw()", what, fe->nrx);
 	return 0;
 }
 
@@ -816,7 +892,7 @@ static int flush_pending_demod(hfdl_gpu_frontend *fe, bool after_fft)
 
 // Stream A, when a block is pushed: its forward FFT into the next spectrum slot of the half being filled (the block's NCO phasor
 // table and carried state ride on the three pass launches).  Nothing else happens until the half is closed.
-static int enqueue_fft(hfdl_gpu_frontend *fe, const void *fresh, int fmt, int stage_idx)
+static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_idx)
 {
 	const Geometry &g = fe->geo;
 	const int i = fe->batch_fill, set = fe->cur_half;
@@ -840,7 +916,9 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, const void *fresh, int fmt, int st
 		fe->ev_fftt.push_back(e);
 	}
 	if (pend) fe->ev_fft_cur = fft_done;
-	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], fresh, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, fe->stream_f,
+	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
+	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
+	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, fe->stream_f,
 			FftOutLayout(), fft_done, job,
 			stage_idx >= 0 ? fe->ev_stage_free[stage_idx] : nullptr,        // input consumed once pass 1 is done: the copy stream may refill the buffer
 			fft_start);
@@ -876,11 +954,11 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 		if (fe->timing) {
 			std::pair<hipEvent_t, hipEvent_t> e;
 			if (!take_timer_pair(fe, e)) return fail(HFDL_GPU_EHIP, "hipEventCreate: %s", hipGetErrorString(hipGetLastError()));
-			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), (size_t)g.n, pp, fe->partial_stride(), take, fe->fold_nb, fe->stream, e.first, e.second);
+			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), fe->spec_stride(), pp, fe->partial_stride(), take, fe->fold_nb, fe->stream, e.first, e.second);
 			fe->ev.push_back(e);
 			fe->ev_blocks.push_back(take);
 		} else {
-			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), (size_t)g.n, pp, fe->partial_stride(), take, fe->fold_nb, fe->stream);
+			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), fe->spec_stride(), pp, fe->partial_stride(), take, fe->fold_nb, fe->stream);
 		}
 	}
 	// this half is free once the demodulator launches that read it last (two halves ago) are done
@@ -922,13 +1000,15 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 
 extern "C" int hfdl_gpu_frontend_channelize_block(hfdl_gpu_frontend *fe, const float *iq, size_t nsamples, int on_device)
 {
-	const void *fresh = nullptr;
+	FftInputs in;
 	int sidx = -1;
-	int rc = stage_input(fe, iq, nsamples, SFMT_CF32, on_device, &fresh, &sidx);
+	int rc = single_receiver_only(fe, "hfdl_gpu_frontend_channelize_block");
 	if (rc) return rc;
+	const void *one[1] = { iq };
+	if ((rc = stage_input(fe, one, nsamples, SFMT_CF32, on_device, in, &sidx))) return rc;
 	if ((rc = flush_pending_demod(fe, false))) return rc;
 	if ((rc = close_half(fe, true))) return rc;             // blocks pushed for the demodulator and not yet handed to it
-	if ((rc = enqueue_fft(fe, fresh, SFMT_CF32, sidx))) return rc;
+	if ((rc = enqueue_fft(fe, in, SFMT_CF32, sidx))) return rc;
 	return close_half(fe, false, false);                    // this block is never demodulated
 }
 
@@ -955,13 +1035,14 @@ extern "C" int hfdl_gpu_frontend_push_baseband(hfdl_gpu_frontend *fe, const floa
 	return launch_demod(fe, half, 1, false);
 }
 
-static int push_any(hfdl_gpu_frontend *fe, const void *raw, size_t nsamples, int fmt, int on_device)
+// one step: raw[0 .. nrx - 1] = a block of every receiver
+static int push_any(hfdl_gpu_frontend *fe, const void *const *raw, size_t nsamples, int fmt, int on_device)
 {
-	const void *fresh = nullptr;
+	FftInputs in;
 	int sidx = -1;
-	int rc = stage_input(fe, raw, nsamples, fmt, on_device, &fresh, &sidx);
+	int rc = stage_input(fe, raw, nsamples, fmt, on_device, in, &sidx);
 	if (rc) return rc;
-	if ((rc = enqueue_fft(fe, fresh, fmt, sidx))) return rc;
+	if ((rc = enqueue_fft(fe, in, fmt, sidx))) return rc;
 	if (fe->batch_fill < fe->half_target) return 0;         // the half is still filling
 	// demodulator-bound geometry (few channels): the fold is short, there is nothing to place the demodulator under, and
 	// holding it back until the NEXT half's forward FFTs would put those blocks' host -> device copies on the demodulator's
@@ -973,12 +1054,31 @@ static int push_any(hfdl_gpu_frontend *fe, const void *raw, size_t nsamples, int
 
 extern "C" int hfdl_gpu_frontend_push_block(hfdl_gpu_frontend *fe, const float *iq, size_t nsamples, int on_device)
 {
-	return push_any(fe, iq, nsamples, SFMT_CF32, on_device);
+	if (int rc = single_receiver_only(fe, "hfdl_gpu_frontend_push_block")) return rc;
+	const void *one[1] = { iq };
+	return push_any(fe, one, nsamples, SFMT_CF32, on_device);
 }
 
 extern "C" int hfdl_gpu_frontend_push_block_raw(hfdl_gpu_frontend *fe, const void *raw, size_t nsamples, int sample_format, int on_device)
 {
+	if (int rc = single_receiver_only(fe, "hfdl_gpu_frontend_push_block_raw")) return rc;
+	const void *one[1] = { raw };
+	return push_any(fe, one, nsamples, sample_format, on_device);
+}
+
+extern "C" int hfdl_gpu_frontend_push_blocks_raw(hfdl_gpu_frontend *fe, const void *const *raw, size_t nsamples, int sample_format, int on_device)
+{
+	if (!fe || !raw) return fail(HFDL_GPU_EINVAL, "null argument");
 	return push_any(fe, raw, nsamples, sample_format, on_device);
+}
+
+extern "C" int hfdl_gpu_frontend_channel_receiver(const hfdl_gpu_frontend *fe, int32_t channel, int32_t *rx, int32_t *centerfreq)
+{
+	if (!fe || !rx || !centerfreq) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (channel < 0 || channel >= fe->geo.nch) return fail(HFDL_GPU_EINVAL, "channel %d out of range (%d channels)", channel, fe->geo.nch);
+	*rx = fe->rx_of[(size_t)channel];
+	*centerfreq = fe->rx_center[(size_t)*rx];
+	return 0;
 }
 
 static int drain_events(hfdl_gpu_frontend *fe)
@@ -1083,6 +1183,7 @@ extern "C" int hfdl_gpu_frontend_input_copied(hfdl_gpu_frontend *fe, uint64_t ho
 extern "C" int hfdl_gpu_frontend_prefetch_block_raw(hfdl_gpu_frontend *fe, const void *raw, size_t nsamples, int sample_format)
 {
 	if (!fe || !raw) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (int rc = single_receiver_only(fe, "hfdl_gpu_frontend_prefetch_block_raw")) return rc;
 	if (sample_format != SFMT_CF32 && sample_format != SFMT_CS16 && sample_format != SFMT_CU8) return fail(HFDL_GPU_EINVAL, "unknown sample format %d", sample_format);
 	if (nsamples != (size_t)fe->plan.input_size)
 		return fail(HFDL_GPU_EINVAL, "a block is exactly %d samples (got %zu)", fe->plan.input_size, nsamples);
@@ -1091,7 +1192,8 @@ extern "C" int hfdl_gpu_frontend_prefetch_block_raw(hfdl_gpu_frontend *fe, const
 	if (!is_library_pinned(raw, sample_bytes(sample_format) * nsamples)) return fail(HFDL_GPU_EINVAL, "only buffers from hfdl_gpu_host_alloc() can be prefetched");
 	HIP_TRY(hipSetDevice(fe->device));
 	int sb = -1;
-	int rc = queue_input_copy(fe, raw, nsamples, sample_format, &sb);
+	const void *one[1] = { raw };
+	int rc = queue_input_copy(fe, one, nsamples, sample_format, &sb);
 	if (rc) return rc;
 	fe->pf_ptr[sb] = raw; fe->pf_fmt[sb] = sample_format;
 	return 0;
@@ -1100,6 +1202,7 @@ extern "C" int hfdl_gpu_frontend_prefetch_block_raw(hfdl_gpu_frontend *fe, const
 extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 {
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (int rc = single_receiver_only(fe, "hfdl_gpu_frontend_prefetch_cancel")) return rc;
 	if (fe->host_pushed == fe->host_blocks) return 0;
 	HIP_TRY(hipSetDevice(fe->device));
 	// the copies are in flight on stream C: let them finish (the caller gets its buffers back), then forget the blocks.  They keep
@@ -1297,17 +1400,21 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 	if (back && what != HFDL_GPU_TAP_SPECTRUM && what != HFDL_GPU_TAP_CHAN_OUT && what != HFDL_GPU_TAP_NCO_PHASORS)
 		return fail(HFDL_GPU_EINVAL, "tap %d holds the last launch only", what);
 	const int slot = fe->last_slot - back, index = fe->last_index - back;
-	if (what != HFDL_GPU_TAP_SPECTRUM && (channel < 0 || channel >= g.nch)) return fail(HFDL_GPU_EINVAL, "channel out of range");
+	// (the spectrum tap of a one-receiver front end ignores `channel`; with several receivers it selects the channel's receiver)
+	if ((what != HFDL_GPU_TAP_SPECTRUM || fe->nrx > 1) && (channel < 0 || channel >= g.nch)) return fail(HFDL_GPU_EINVAL, "channel out of range");
 	const void *src = nullptr;
 	size_t nf = 0;
 	switch (what) {
-	case HFDL_GPU_TAP_SPECTRUM: src = fe->spec_slot(fe->last_set, index); nf = 2 * (size_t)g.n; break;
+	case HFDL_GPU_TAP_SPECTRUM:
+		src = fe->spec_slot(fe->last_set, index) + (fe->nrx > 1 ? (size_t)fe->rx_of[(size_t)channel] * (size_t)g.n : 0);
+		nf = 2 * (size_t)g.n;
+		break;
 	case HFDL_GPU_TAP_FILTER: {
 		// the taps lie in matrix-operand order (kernels.h tap_index_f): a kernel gathers the channel into plain cf32[N]
 		if (2 * (size_t)g.n > cap) return fail(HFDL_GPU_ERANGE, "tap needs %zu floats, buffer holds %zu", 2 * (size_t)g.n, cap);
 		DevBuf plain;
 		HIP_TRY(plain.alloc(sizeof(float2) * (size_t)g.n));
-		launch_tap_extract(fe->d_taps, g, channel, plain.as<float2>(), fe->stream);
+		launch_tap_extract(fe->d_taps, g, fe->slot_of(channel), plain.as<float2>(), fe->stream);
 		HIP_TRY(hipStreamSynchronize(fe->stream));
 		HIP_TRY(hipMemcpy(dst, plain.p, sizeof(float2) * (size_t)g.n, hipMemcpyDeviceToHost));
 		*n_floats = 2 * (size_t)g.n;
@@ -1545,7 +1652,7 @@ extern "C" int hfdl_gpu_lab_fold_variant_probe(hfdl_gpu_frontend *fe, int varian
 	HIP_TRY(hipMemsetAsync(fe->d_partial, 0xff, sizeof(float2) * fe->partial_stride() * (size_t)nb, fe->stream));    // nothing left over from another kernel counts
 	double sum = 0, best = 1e30;
 	for (int i = 0; i < reps + 1; i++) {
-		if (launch_fold_variant(variant, g, fe->d_taps, fe->spec_slot(fe->last_set, 0), (size_t)g.n, fe->d_partial, fe->partial_stride(), nb, fe->stream, e0, e1) < 0) {
+		if (launch_fold_variant(variant, g, fe->d_taps, fe->spec_slot(fe->last_set, 0), fe->spec_stride(), fe->d_partial, fe->partial_stride(), nb, fe->stream, e0, e1) < 0) {
 			(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
 			return fail(HFDL_GPU_ERANGE, "fold variant %d does not fit this geometry (M = %d, %d rows per slice) or block count %d", variant, g.m, g.rows_per_slice, nb);
 		}

@@ -45,7 +45,19 @@ struct Geometry {
 	// Null: every row is folded.  With windows the geometry has one slice.
 	const int2 *fold_win = nullptr;
 	int32_t fold_tile = -1;            // laboratory (HFDL_GPU_FOLD_TILE): index of the tiling to use instead of the first that fits
+	// Receivers (hfdl_gpu_frontend_create_multi): each pads its own channels to whole groups of the tap layout (planner.h
+	// plan_receiver_slots), so no group -- and no fold workgroup -- holds channels of two receivers.  rx_tab[r] / rx_host[r] = { first
+	// padded slot, padded slots, first channel, channels } of receiver r (device / host copy); the spectrum of receiver r lies
+	// spec_rx_stride cf32 after receiver r - 1's.  One receiver: { 0, nch_pad, 0, nch }.
+	const int4 *rx_tab = nullptr, *rx_host = nullptr;
+	int32_t nrx = 1;
+	int64_t spec_rx_stride = 0;
+	// TAPL_OCTET: the fold workgroups' FoldGroup entries, one table per workgroup width pw = 1 .. FOLD_GROUP_MAX octets at
+	// grp_tab + (pw - 1) * (nch_pad / 8): per receiver its nch_r / pw full groups, receiver after receiver, then the octets left over
+	const int4 *grp_tab = nullptr;
 };
+// an entry (planner.h FoldGroup, read as an int4): first octet of the group, its receiver, the end of that receiver's channel slots, channel - slot
+constexpr int FOLD_GROUP_MAX = 16;          // octets one fold workgroup takes at most (P x W of the widest compiled tiling)
 
 // Filter-tap layouts.  The fold runs on the fp32 matrix pipe -- v_mfma_f32_16x16x4_f32: D (16 x 16) += A (16 x 4) . B (4 x 16) with
 // the 16 rows = Re / Im of eight channels, the 4 inner indices = four consecutive alias rows, the 16 columns = sixteen blocks, for ONE
@@ -85,6 +97,17 @@ struct NcoJob {
 	int32_t seg = 0, nseg = 3;
 };
 
+// The receivers of one forward-FFT step (hfdl_gpu_frontend_push_blocks_raw): ONE three-pass sequence transforms them all, grid
+// dimension y = receiver.  Receiver r reads fresh[r] (by value in the kernel arguments: device-resident inputs need no gather copy),
+// its overlap history at hist + r * hist_stride (the next one goes to hist_next + r * hist_stride), its transform in the work buffer
+// at r * n and leaves its spectrum at out + r * out_stride.  The NCO rider workgroups run once per step, in row y = 0.
+constexpr int RECEIVERS_MAX = 64;
+struct FftInputs {
+	const void *fresh[RECEIVERS_MAX] = {};
+	int64_t hist_stride = 0, out_stride = 0;
+	int32_t nrx = 1;
+};
+
 // owning device allocation for the one-shot stage entry points (freed on every exit path)
 struct DevBuf {
 	void *p = nullptr;
@@ -103,12 +126,22 @@ enum { SFMT_CF32 = 0, SFMT_CS16 = 1, SFMT_CU8 = 2 };
 // kind != TAPL_PLAIN: the transform is the filter of channel `chan`, `out` is the tap buffer, and element (row i >> row_log, bin) goes
 // to tap_index_f(kind, 2^row_log, 2 * row_stride, chan, row, bin, comp) floats
 struct FftOutLayout { int row_log = 0; int64_t row_stride = 0; int kind = 0; int chan = 0; };
-void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh, int fmt, int split, float2 *hist_next,
+void launch_fft_forward(const FftPlan &p, const float2 *hist, const FftInputs &in, int fmt, int split, float2 *hist_next,
 		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay = FftOutLayout(), hipEvent_t done = nullptr,
 		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr);
-		// input_read: signalled when the first pass has consumed `fresh`; start: rides on the first pass' dispatch (timing)
+		// input_read: signalled when the first pass has consumed the inputs; start: rides on the first pass' dispatch (timing)
+// one transform (one receiver)
+inline void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh, int fmt, int split, float2 *hist_next,
+		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay = FftOutLayout(), hipEvent_t done = nullptr,
+		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr)
+{
+	FftInputs in;
+	in.fresh[0] = fresh;
+	launch_fft_forward(p, hist, in, fmt, split, hist_next, work, out, shifted, st, lay, done, nco, input_read, start);
+}
 // optional events ride on the kernel dispatches themselves (hipExtLaunchKernelGGL): no separate barrier packets in the queue
-// `nb` consecutive blocks: spectra `spec_stride` cf32 apart, partial sums `partial_stride` apart; launches of at most `nb_max` blocks
+// `nb` consecutive blocks: spectra `spec_stride` cf32 apart (each block's receivers g.spec_rx_stride apart inside that), partial sums
+// `partial_stride` apart, indexed by CHANNEL (padding slots are skipped); launches of at most `nb_max` blocks
 // sharing one pass over the taps.  Returns the number of kernel launches made.
 int launch_fold(const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial, size_t partial_stride,
 		int nb, int nb_max, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
@@ -118,7 +151,7 @@ int fold_variant_count();
 int fold_variant_describe(int variant, int desc[6]);            // P, Q, W, D, max blocks, 0
 int launch_fold_variant(int variant, const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial,
 		size_t partial_stride, int nb, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-void launch_tap_extract(const float2 *taps, const Geometry &g, int channel, float2 *dst, hipStream_t st);      // one channel's taps back in plain order
+void launch_tap_extract(const float2 *taps, const Geometry &g, int slot, float2 *dst, hipStream_t st);      // the taps of one padded slot back in plain order
 // energy[row * nch_pad + c] += sum over the row's M bins of |H_c|^2 (TAPL_OCTET; `energy` zeroed by the caller): what the pruned fold's
 // row windows are chosen from
 void launch_tap_row_energy(const float2 *taps, const Geometry &g, float *energy, hipStream_t st);

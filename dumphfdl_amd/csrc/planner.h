@@ -109,4 +109,44 @@ inline void design_bandpass(std::complex<float> *out, int32_t length, float lowc
 	}
 }
 
+// The padded channel layout of a front end of several receivers (hfdl_gpu_frontend_create_multi): the channels of receiver r are the
+// global channels chan0 .. chan0 + nch - 1 (receiver-major), and in the filter-tap buffer they take the slots slot0 .. slot0 + nch - 1 of a
+// run of `slots` = nch rounded up to a whole group of the tap layout (`group` = 8 for the octet layout, 1 for the plain one): no group of
+// slots -- and so no fold workgroup, which takes whole groups -- holds channels of two receivers; the slots past nch carry zero taps.
+// Returns the total number of slots (Geometry::nch_pad).
+struct RxSpan { int32_t slot0, slots, chan0, nch; };
+inline int32_t plan_receiver_slots(const int32_t *nch_per_rx, int32_t nrx, int32_t group, std::vector<RxSpan> &out)
+{
+	out.assign((size_t)nrx, RxSpan{});
+	int32_t slot = 0, chan = 0;
+	for (int32_t r = 0; r < nrx; r++) {
+		const int32_t n = nch_per_rx[r];
+		out[(size_t)r] = RxSpan{ slot, (n + group - 1) / group * group, chan, n };
+		slot += out[(size_t)r].slots;
+		chan += n;
+	}
+	return slot;
+}
+inline int32_t receiver_slot(const RxSpan &r, int32_t channel) { return r.slot0 + (channel - r.chan0); }
+
+// The fold's workgroup tables (the octet layout; kernels.h Geometry::grp_tab): for every workgroup width pw = 1 .. pw_max octets, at
+// (pw - 1) * noct, the full groups of pw octets of every receiver, receiver after receiver, then the octets each receiver has left over
+// -- the order the fold launchers hand them out in.  An entry: first octet, receiver, end of the receiver's channel slots, channel - slot.
+struct FoldGroup { int32_t octet, rx, slot_end, to_chan; };
+inline std::vector<FoldGroup> fold_group_tables(const std::vector<RxSpan> &rx, int32_t noct, int32_t pw_max)
+{
+	std::vector<FoldGroup> t((size_t)pw_max * (size_t)noct, FoldGroup{});
+	for (int32_t pw = 1; pw <= pw_max; pw++) {
+		FoldGroup *e = t.data() + (size_t)(pw - 1) * (size_t)noct;
+		for (int rest = 0; rest < 2; rest++)
+			for (size_t r = 0; r < rx.size(); r++) {
+				const int32_t no = rx[r].slots / 8, first = rx[r].slot0 / 8;
+				const FoldGroup v{ 0, (int32_t)r, rx[r].slot0 + rx[r].nch, rx[r].chan0 - rx[r].slot0 };
+				if (!rest) for (int32_t gi = 0; gi < no / pw; gi++) { *e = v; e->octet = first + gi * pw; e++; }
+				else for (int32_t o = no / pw * pw; o < no; o++) { *e = v; e->octet = first + o; e++; }
+			}
+	}
+	return t;
+}
+
 }  // namespace hfdl

@@ -72,10 +72,12 @@ EXPORTS = [
     "hfdl_gpu_frontend_fold_blocks", "hfdl_gpu_frontend_fold_launch_shapes", "hfdl_gpu_frontend_stage_times", "hfdl_gpu_frontend_read_tap_block", "hfdl_gpu_frontend_push_baseband", "hfdl_gpu_frontend_input_copied",
     "hfdl_gpu_fft_forward", "hfdl_gpu_viterbi27", "hfdl_gpu_burst_decode", "hfdl_gpu_nco_decimate", "hfdl_gpu_crc16_ccitt", "hfdl_gpu_pdu_triage", "hfdl_gpu_lpdu_walk", "hfdl_gpu_frontend_prefetch_block_raw", "hfdl_gpu_frontend_prefetch_cancel", "hfdl_gpu_psk_slice",
     "hfdl_gpu_last_error", "hfdl_gpu_device_count",
+    "hfdl_gpu_frontend_create_multi", "hfdl_gpu_frontend_push_blocks_raw", "hfdl_gpu_frontend_channel_receiver",
 ]
 
 
 FOLD_BATCH_MAX = 32        # HFDL_GPU_FOLD_BATCH_MAX of include/hfdl_gpu.h
+RECEIVERS_MAX = 64         # HFDL_GPU_RECEIVERS_MAX
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
@@ -177,6 +179,9 @@ def _bind(L):
     L.hfdl_gpu_psk_slice.argtypes = [C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.hfdl_gpu_frontend_prefetch_block_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.hfdl_gpu_frontend_prefetch_cancel.argtypes = [C.c_void_p]
+    L.hfdl_gpu_frontend_create_multi.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hfdl_gpu_frontend_push_blocks_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+    L.hfdl_gpu_frontend_channel_receiver.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return L
 
 
@@ -424,6 +429,70 @@ class Frontend:
             self.close()
         except Exception:
             pass
+
+
+class MultiFrontend(Frontend):
+    """Several receivers' I/Q streams at one sample rate in ONE front end (hfdl_gpu_frontend_create_multi): receivers =
+    [(centerfreq, [freqs...]), ...].  Channel indices are global, receiver-major (receiver 0's channels first); every step takes a
+    block of every receiver (push_blocks / push_blocks_raw).  Polls, stats, taps, timers and the lab probe are Frontend's."""
+
+    def __init__(self, sample_rate, receivers, device=0, lib=None):
+        L = self._L = lib or load()
+        self.receivers = [(int(c), [int(f) for f in fs]) for c, fs in receivers]
+        centres = np.ascontiguousarray([c for c, _ in self.receivers], dtype=np.int32)
+        counts = np.ascontiguousarray([len(fs) for _, fs in self.receivers], dtype=np.int32)
+        fr = np.ascontiguousarray([f for _, fs in self.receivers for f in fs], dtype=np.int32)
+        self._h = C.c_void_p()
+        _check(L.hfdl_gpu_frontend_create_multi(C.byref(self._h), device, sample_rate, len(self.receivers), _p(centres), _p(fr), _p(counts)), L)
+        self.geometry = Geometry()
+        _check(L.hfdl_gpu_frontend_geometry(self._h, C.byref(self.geometry)), L)
+        self.freqs = [int(f) for f in fr]
+        self._rx_of = [r for r, (_, fs) in enumerate(self.receivers) for _ in fs]
+
+    @property
+    def nrx(self):
+        return len(self.receivers)
+
+    def receiver_of(self, channel):
+        """(receiver index, its centre frequency) of a global channel index."""
+        rx, cf = C.c_int32(0), C.c_int32(0)
+        _check(self._L.hfdl_gpu_frontend_channel_receiver(self._h, channel, C.byref(rx), C.byref(cf)), self._L)
+        return rx.value, cf.value
+
+    def push_blocks_raw(self, blocks, sample_format, on_device=False, nsamples=None):
+        """blocks[r]: receiver r's block -- an int16 / uint8 / float32 numpy array of 2*input_size interleaved I,Q values, or (on_device)
+        an int device pointer (nsamples: input_size unless given).  One call = one step = one host block."""
+        dt = {SFMT_CF32: np.float32, SFMT_CS16: np.int16, SFMT_CU8: np.uint8}[sample_format]
+        keep = []
+        ptrs = (C.c_void_p * max(1, len(blocks)))()
+        for r, b in enumerate(blocks):
+            if isinstance(b, int):
+                ptrs[r] = b
+            else:
+                a = np.ascontiguousarray(b, dtype=dt)
+                keep.append(a)
+                ptrs[r] = a.ctypes.data
+        if keep:
+            lens = {len(a) // 2 for a in keep}
+            if len(lens) != 1:
+                raise ValueError("the receivers' blocks differ in length: %s" % sorted(lens))
+            nsamples = lens.pop() if nsamples is None else nsamples
+        n = self.geometry.input_size if nsamples is None else nsamples
+        _check(self._L.hfdl_gpu_frontend_push_blocks_raw(self._h, ptrs, n, sample_format, int(on_device)), self._L)
+
+    def push_blocks(self, blocks):
+        """blocks[r]: complex64 numpy array of input_size samples of receiver r (host), or an int device pointer to one; all of one kind."""
+        dev = all(isinstance(b, int) for b in blocks) and len(blocks) > 0
+        if dev:
+            self.push_blocks_raw(list(blocks), SFMT_CF32, on_device=True)
+        else:
+            self.push_blocks_raw([np.ascontiguousarray(b, dtype=np.complex64).view(np.float32) for b in blocks], SFMT_CF32)
+
+    def pdus_to_dicts(self, buf, n):
+        out = Frontend.pdus_to_dicts(buf, n)
+        for d in out:
+            d["receiver"] = self._rx_of[d["channel"]]
+        return out
 
 
 def fft_forward(x, shifted=False, device=0):

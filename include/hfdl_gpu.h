@@ -103,7 +103,8 @@ typedef struct {
  *                                pre_decimation): the channelizer output moves by ~tol relative RMS and the fold's time by the ratio of the
  *                                rows.  The stored taps carry the rounding noise of the fp32 transform that made them (2.1e-7 of their energy
  *                                as an amplitude ratio at N = 2^23) in EVERY row: a tolerance below that keeps every row.  Off, every row is
- *                                folded -- the reference's sum, term for term
+ *                                folded -- the reference's sum, term for term.  Ignored by a front end of several receivers
+ *                                (hfdl_gpu_frontend_create_multi with nrx > 1): there geometry.fold_rows = pre_decimation
  * The A/B switches of the measurement scripts (stream placement, tiling sweeps, probes) are in the laboratory build only:
  * include/hfdl_gpu_lab.h, libhfdl_gpu_lab.so. */
 
@@ -147,6 +148,39 @@ void hfdl_gpu_host_free(void *ptr);
 int  hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t centerfreq,
 		const int32_t *freqs, int32_t nch);
 void hfdl_gpu_frontend_destroy(hfdl_gpu_frontend *fe);
+
+/* ---- several receivers in one front end ----
+ * nrx receivers at one sample rate: receiver r is centred on centerfreqs[r] and carries nch_per_rx[r] channels.
+ * freqs[] lists them receiver-major (receiver 0's channels first), so a channel index -- hfdl_gpu_pdu.channel, the
+ * channel argument of stats / taps -- is global over the front end.  Each channel must lie within +-fs/2 of ITS receiver's centre.
+ * One pipeline carries them all: per step ONE batched forward-FFT sequence transforms every receiver's block, one fold launch (per
+ * tiling, as for one receiver) multiplies every channel of every receiver against one pass over the filter taps, and one inverse-FFT /
+ * NCO, demodulator and burst-decoder launch covers all channels.  hfdl_gpu_frontend_create(..) IS this call with nrx = 1 (the same
+ * code path, the same results).
+ * Rules:
+ *   - every argument is checked before a device is selected: null pointers, nrx outside 1 .. HFDL_GPU_RECEIVERS_MAX, a channel count
+ *     <= 0, the span of each channel against its own receiver's centre, the sample rate (HFDL_GPU_EINVAL)
+ *   - with nrx > 1, hfdl_gpu_frontend_push_block, _push_block_raw, _channelize_block, _prefetch_block_raw and _prefetch_cancel return
+ *     HFDL_GPU_EINVAL and enqueue nothing: a step takes a block of every receiver (hfdl_gpu_frontend_push_blocks_raw); prefetching is
+ *     for one receiver only
+ *   - host blocks (hfdl_gpu_frontend_input_done_upto / _input_copied) count steps: one hfdl_gpu_frontend_push_blocks_raw call = one host block
+ *   - HFDL_GPU_TAP_SPECTRUM (read_tap / read_tap_block): with nrx > 1 `channel` selects the spectrum of that channel's receiver and
+ *     must be in range; with nrx = 1 it is ignored
+ *   - geometry.channels = all channels of all receivers; fold_batch, demod_batch and prefetch_depth report what was chosen: the
+ *     per-block buffers of the forward FFT scale with nrx, and a front end of nrx > 1 receivers keeps nrx x (blocks per half) x fft_size
+ *     <= 32 x 2^23 (spectra, staging ring, history): where that binds, fold_batch shrinks (never below one block) and demod_batch
+ *     with it.  A create that still cannot allocate fails with HFDL_GPU_ENOMEM and leaks nothing
+ *   - HFDL_GPU_FOLD_PRUNE is ignored with nrx > 1 (geometry.fold_rows = pre_decimation)
+ *   - the receivers are assumed to be clocked alike (one sample rate); pacing, drift and dropouts of live sources are the caller's business */
+#define HFDL_GPU_RECEIVERS_MAX 64
+int  hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx,
+		const int32_t *centerfreqs, const int32_t *freqs, const int32_t *nch_per_rx);
+/* One block of EVERY receiver: raw[r] holds geometry.input_size samples of receiver r, all in one sample format (HFDL_GPU_SFMT_*);
+ * on_device / host-buffer rules as hfdl_gpu_frontend_push_block_raw (page-locked buffers reusable after input_done / sync / poll).
+ * Works on any front end, nrx = 1 included. */
+int  hfdl_gpu_frontend_push_blocks_raw(hfdl_gpu_frontend *fe, const void *const *raw, size_t nsamples, int sample_format, int on_device);
+/* receiver and centre frequency of a channel */
+int  hfdl_gpu_frontend_channel_receiver(const hfdl_gpu_frontend *fe, int32_t channel, int32_t *rx, int32_t *centerfreq);
 int  hfdl_gpu_frontend_geometry(const hfdl_gpu_frontend *fe, hfdl_gpu_geometry *g);
 
 /* Enqueue one block: exactly geometry.input_size new complex samples (interleaved I,Q float32).  Asynchronous: the block's forward

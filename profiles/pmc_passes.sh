@@ -7,13 +7,13 @@
 # runs (32).
 WL=${1:-cfg3}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-OUT=${2:-/root/repo/gpurun_out/pmc_$WL}
+OUT=${2:?usage: profiles/pmc_passes.sh <workload> <outdir> [commit]}
 COMMIT=${3:-unknown}
 # fold launches of the profiled command in launch order: the warm-up's 8 blocks (closed by a poll), then the 68 timed ones: 16 + 32 +
 # (16 + 4) (cfg3 / cfg4: the fold bounds the block) or halves of 8 (cfg2: the demodulator does), then the five one-block launches of the
 # bench's latency leg (block_to_pdus_latency_ms)
 if [ "$WL" = "cfg2" ]; then SHAPES=8,8,8,8,8,8,8,8,8,4,1,1,1,1,1; else SHAPES=8,16,32,16,4,1,1,1,1,1; fi
-mkdir -p $OUT
+mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd)          # absolute: the passes below run from /tmp
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_${WL}_*
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT"; do
@@ -26,7 +26,7 @@ DBS=$(find /tmp/pmc_${WL}_* -name "*.db" | sort)
 	echo
 	echo "Per-dispatch averages. FETCH_SIZE / WRITE_SIZE in KB; on gfx950 reads = 2 x FETCH_SIZE for wide coalesced streaming reads (calibrated in the same run on stream_read_kernel, which reads a known byte count). SQ_* count quad-cycles summed over the dispatch's waves."
 	echo
-	python /root/repo/profiles/pmc_summary.py $DBS
+	python "$ROOT/profiles/pmc_summary.py" $DBS
 } > $OUT/${WL}_pmc_counters.md
-python /root/repo/profiles/fold_traffic.py $WL $COMMIT $SHAPES $DBS > $OUT/fold_traffic_${WL}.json || { echo "fold_traffic refused"; rm -f $OUT/fold_traffic_${WL}.json; }
+python "$ROOT/profiles/fold_traffic.py" $WL $COMMIT $SHAPES $DBS > $OUT/fold_traffic_${WL}.json || { echo "fold_traffic refused"; rm -f $OUT/fold_traffic_${WL}.json; }
 cat $OUT/fold_traffic_${WL}.json
