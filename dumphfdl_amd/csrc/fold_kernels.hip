@@ -530,7 +530,8 @@ static int fold16_go_win(const FoldArgs &a, const int2 *win)
 	return 1;
 }
 
-// P octets per wave, W waves per workgroup, D quads of loads in flight; a tiling takes any block count up to 16
+// P octets per wave, W waves per workgroup, D quads of loads in flight; a tiling takes any block count up to its 4 Q columns (columns
+// past the last block are computed and dropped)
 struct FoldVariant { int layout, p, q, w, d; int (*go)(const FoldArgs &); };
 #define F16(P, W, D) { TAPL_OCTET, P, 4, W, D, fold16_go<P, W, D> }
 #define F4(P, W, D) { TAPL_OCTET, P, 1, W, D, fold16_go<P, W, D, true> }        // the four-column form: at most four blocks
@@ -585,6 +586,18 @@ static const FoldVariant *pick_variant(const Geometry &g, int nb)
 	return nullptr;
 }
 
+int fold_launch_blocks(const Geometry &g, int remaining, int nb_max)
+{
+	int take = remaining < nb_max ? remaining : nb_max;
+	if (take > FOLD_MAX_BLOCKS) take = FOLD_MAX_BLOCKS;
+	if (take > 16 && g.fold_win && g.tap_layout == TAPL_OCTET) take = 16;         // the pruned fold has the sixteen-column form only
+	// 17 .. 20 blocks: sixteen columns, then the four-column form for the rest (3.9 + 2.7 ms) -- thirty-two columns cost their 6.8 ms
+	// whatever the block count
+	if (take > 16 && take <= 20) take = 16;
+	if (take > 16 && !pick_variant(g, take)) take = 16;                          // no thirty-two-column tiling fits this geometry
+	return take;
+}
+
 static FoldArgs fold_args(const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial, size_t partial_stride,
 		int nb, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
@@ -614,25 +627,14 @@ int launch_fold_variant(int v, const Geometry &g, const float2 *taps, const floa
 }
 
 int launch_fold(const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial, size_t partial_stride,
-		int nb, int nb_max, hipStream_t st, hipEvent_t start, hipEvent_t stop)
+		int nb, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
-	int launches = 0;
-	if (nb_max > FOLD_MAX_BLOCKS) nb_max = FOLD_MAX_BLOCKS;
-	// one launch per nb_max blocks: a launch takes ANY block count up to 16 (columns past the last block are computed and dropped)
-	if (g.fold_win && g.tap_layout == TAPL_OCTET && nb_max > 16) nb_max = 16;      // the pruned fold has the sixteen-column form only
-	for (int done = 0; done < nb;) {
-		int take = nb - done < nb_max ? nb - done : nb_max;
-		if (take > 16 && !pick_variant(g, take)) take = 16;                       // no thirty-two-column tiling fits this geometry
-		const bool first = done == 0, last = done + take >= nb;
-		const float2 *sp = spectrum + (size_t)done * spec_stride;
-		float2 *pp = partial + (size_t)done * partial_stride;
-		const FoldVariant *f = pick_variant(g, take);
-		if (g.fold_win && g.tap_layout == TAPL_OCTET) launches += fold16_go_win<2>(fold_args(g, taps, sp, spec_stride, pp, partial_stride, take, st, first ? start : nullptr, last ? stop : nullptr), g.fold_win);
-		else if (f) launches += f->go(fold_args(g, taps, sp, spec_stride, pp, partial_stride, take, st, first ? start : nullptr, last ? stop : nullptr));
-		else { launch_fold_ref(g, taps, sp, spec_stride, pp, partial_stride, take, st, first ? start : nullptr, last ? stop : nullptr); launches++; }
-		done += take;
-	}
-	return launches;
+	if (nb < 1 || nb > fold_launch_blocks(g, nb, FOLD_MAX_BLOCKS)) return -1;
+	const FoldArgs a = fold_args(g, taps, spectrum, spec_stride, partial, partial_stride, nb, st, start, stop);
+	if (g.fold_win && g.tap_layout == TAPL_OCTET) return fold16_go_win<2>(a, g.fold_win);
+	if (const FoldVariant *f = pick_variant(g, nb)) return f->go(a);
+	launch_fold_ref(g, taps, spectrum, spec_stride, partial, partial_stride, nb, st, start, stop);
+	return 1;
 }
 
 // energy of every (alias row, channel) of the octet-interleaved taps: one workgroup per (quad of rows, octet) walks its M / 4 chunks of

@@ -107,6 +107,96 @@ int HostFftPlan::build(int n)
 	return 0;
 }
 
+// ---------------------------------------------------------------- launch timing
+
+// The timed kernel launches of a front end (hfdl_gpu_frontend_reset_timers), by stage in the order of hfdl_gpu_frontend_stage_times().
+// A timed launch carries a start / stop event pair on its own dispatch (hipExtLaunchKernelGGL): no extra packet in the queue.  The
+// pairs come from a pool filled outside any timed region and are read back and returned to it by the next drain (a sync / poll).
+enum Stage { ST_FFT, ST_FOLD, ST_IFFT, ST_DEMOD, ST_DECODE, ST_N };
+static_assert(ST_N == 5, "hfdl_gpu_frontend_stage_times() reports five stages");
+struct LaunchTimers {
+	struct Timed { hipEvent_t start, stop; int blocks; };
+	struct Totals { double ms = 0; int64_t launches = 0, blocks = 0; std::vector<Timed> pending; };     // read so far; launched, not yet read
+	bool on = false;
+	Totals stage[ST_N];
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;    // free pairs, made by reset() outside any timed region
+	int64_t fold_shapes[FOLD_MAX_BLOCKS + 1] = {};   // fold launches by block count
+	double fold_shape_ms[FOLD_MAX_BLOCKS + 1] = {};  // ... and their kernel time
+	hipEvent_t first_fold = nullptr;    // start of the first timed fold since the reset: anchor of the steady-state step period
+	double span_ms = 0;                 // first timed fold start -> last timed fold start
+	int64_t fold_last_blocks = 0;       // blocks of the last timed fold
+
+	// timing on: a pair from the pool (made here when a long run without a drain has used it up -- a timed launch is never silently
+	// untimed) into `start` / `done`; the stop event stands in as the launch's "done" event.  Timing off: both are left as they are.
+	int arm(Stage s, int blocks, hipEvent_t &start, hipEvent_t &done)
+	{
+		if (!on) return 0;
+		std::pair<hipEvent_t, hipEvent_t> e;
+		if (!pool.empty()) {
+			e = pool.back();
+			pool.pop_back();
+		} else {
+			HIP_TRY(hipEventCreate(&e.first));
+			if (hipEventCreate(&e.second) != hipSuccess) { (void)hipEventDestroy(e.first); return fail(HFDL_GPU_EHIP, "hipEventCreate: %s", hipGetErrorString(hipGetLastError())); }
+		}
+		start = e.first;
+		done = e.second;
+		stage[s].pending.push_back({ e.first, e.second, blocks });
+		return 0;
+	}
+	// every timed launch is complete: add it up, the pairs go back to the pool
+	int drain()
+	{
+		for (int s = 0; s < ST_N; s++) {
+			for (Timed &t : stage[s].pending) {
+				float ms = 0;
+				HIP_TRY(hipEventElapsedTime(&ms, t.start, t.stop));
+				stage[s].ms += ms;
+				stage[s].launches++;
+				stage[s].blocks += t.blocks;
+				if (s == ST_FOLD) {
+					fold_last_blocks = t.blocks;
+					if (t.blocks >= 1 && t.blocks <= FOLD_MAX_BLOCKS) { fold_shapes[t.blocks]++; fold_shape_ms[t.blocks] += ms; }
+					if (!first_fold) {
+						first_fold = t.start;           // kept until the next reset
+						HIP_TRY(hipEventCreate(&t.start));
+					} else {
+						HIP_TRY(hipEventElapsedTime(&ms, first_fold, t.start));
+						span_ms = ms;
+					}
+				}
+				pool.push_back({ t.start, t.stop });
+			}
+			stage[s].pending.clear();
+		}
+		return 0;
+	}
+	// after a drain: every total to zero; timing on fills the pool with enough pairs for the launches between two drains
+	int reset(bool enable)
+	{
+		on = enable;
+		for (Totals &t : stage) { t.ms = 0; t.launches = 0; t.blocks = 0; }
+		for (auto &c : fold_shapes) c = 0;
+		for (auto &c : fold_shape_ms) c = 0;
+		if (first_fold) { (void)hipEventDestroy(first_fold); first_fold = nullptr; }
+		span_ms = 0;
+		fold_last_blocks = 0;
+		while (enable && pool.size() < 1280) {
+			std::pair<hipEvent_t, hipEvent_t> e;
+			HIP_TRY(hipEventCreate(&e.first));
+			HIP_TRY(hipEventCreate(&e.second));
+			pool.push_back(e);
+		}
+		return 0;
+	}
+	void release()
+	{
+		for (auto &e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+		for (Totals &t : stage) for (Timed &e : t.pending) { (void)hipEventDestroy(e.start); (void)hipEventDestroy(e.stop); }
+		if (first_fold) (void)hipEventDestroy(first_fold);
+	}
+};
+
 // ---------------------------------------------------------------- front end
 
 struct hfdl_gpu_frontend {
@@ -119,24 +209,19 @@ struct hfdl_gpu_frontend {
 	static constexpr int MAX_STAGE = HFDL_GPU_PREFETCH_MAX + 1;      // staging buffers for host input at most: uploads run at most 17 blocks ahead
 	hipEvent_t ev_dm[2][MAX_HALF] = {};              // demodulator launch j of the half in buffer 0 / 1 done (the decoder may start)
 	hipEvent_t ev_dm_cur[2] = { nullptr, nullptr };  // LAST demodulator launch of that half done (chan_out free): an ev_dm, or (timing on) the stop event of a timed pair
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_dmt;      // timed demodulator launches not yet read
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_fftt, ev_ifftt, ev_dect;      // ... forward FFTs (first pass start -> last pass stop), inverse FFT / NCO launches, burst decoders
-	double fft_ms = 0, ifft_ms = 0, decode_ms = 0;
-	int64_t fft_timed = 0, ifft_timed = 0, decode_timed = 0;
 	hipEvent_t ev_chan_cur[2] = { nullptr, nullptr };       // "channelizer output of this half ready": ev_chan, or (timing on) the stop event of the timed inverse FFT
 	hipEvent_t ev_fft_cur = nullptr;                        // what the held-back demodulators wait for: ev_fft, or the stop event of a timed forward FFT
-	double demod_ms = 0;
-	int64_t demod_launches = 0, demod_timed_blocks = 0;
-	hipStream_t stream_c = nullptr;     // C: host -> device copies into the staging ring, up to a half ahead of the blocks that compute
+	hipStream_t stream_c = nullptr;     // C: host -> device copies into the staging ring, up to n_stage - 1 blocks ahead of the blocks that compute
 	hipStream_t stream_f = nullptr;     // F: forward FFTs of the half being filled, beside the fold of the half before (== stream when HFDL_GPU_FFT_STREAM=0)
 	bool fft_own_stream = false;
 	hipEvent_t ev_spec[2] = { nullptr, nullptr };    // newest forward FFT of the half in spectrum set 0 / 1 done (rides on its last pass)
 
 	hipEvent_t ev_chan[2] = { nullptr, nullptr }, ev_demod[2] = { nullptr, nullptr };
-	// Host input goes through a RING of n_stage = half_blocks + 2 staging buffers in HBM: host block j is copied (stream C) into buffer
-	// j % n_stage, which the forward FFT's first pass of block j - n_stage has finished reading -- that pass runs BEFORE the fold of its
-	// half, so uploads run a whole half ahead and never sit behind the 3 ms fold (with two buffers, upload k+2 waited for FFT k, which
-	// waited for the fold of the half before: the link idled a third of the time).
+	// Host input goes through a RING of n_stage = min(half_blocks + 2, MAX_STAGE) staging buffers in HBM: host block j is copied (stream
+	// C) into buffer j % n_stage, which the forward FFT's first pass of block j - n_stage has finished reading -- that pass runs BEFORE the
+	// fold of its half, so uploads run up to n_stage - 1 blocks ahead (a whole half of up to 16 blocks, 17 blocks of a 32-block half) and
+	// never sit behind the fold (with two buffers, upload k+2 waited for FFT k, which waited for the fold of the half before: the link
+	// idled a third of the time).
 	int n_stage = 0;
 	hipEvent_t ev_stage_ready[MAX_STAGE] = {};  // copy of the host block in this buffer done: what its forward FFT and input_done_upto() wait for
 	hipEvent_t ev_stage_free[MAX_STAGE] = {};   // pass 1 of the forward FFT that read this buffer done (rides on that dispatch): the copy stream may refill it
@@ -201,17 +286,7 @@ struct hfdl_gpu_frontend {
 	size_t stage_cap[MAX_STAGE] = {};
 	bool fold_bound = false;            // many channels: the fold bounds the block and the demodulator launches of a half are placed under the NEXT half's fold
 	Demod demod;
-	// fold timing
-	bool timing = false;
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;      // timing events made by reset_timers(), outside any timed region
-	std::vector<int> ev_blocks;         // blocks folded between each pair of `ev`
-	double fold_ms = 0;
-	int64_t fold_launches = 0, fold_timed_blocks = 0, fold_last_blocks = 0;
-	int64_t fold_shapes[FOLD_MAX_BLOCKS + 1] = {};   // timed fold launches by block count
-	double fold_shape_ms[FOLD_MAX_BLOCKS + 1] = {};  // ... and their kernel time
-	hipEvent_t ev_first_fold = nullptr;  // start of the first timed fold since reset_timers: anchor of the steady-state step period
-	double span_ms = 0;                 // first timed fold start -> last timed fold start
+	LaunchTimers timers;
 	uint64_t blocks = 0;
 	FftOutLayout tap_layout;
 	int pending_demod_buf = -1;         // half whose demodulator launches are held back until the next half's forward FFTs are queued ...
@@ -221,20 +296,6 @@ struct hfdl_gpu_frontend {
 	int demod_buf = -1;                 // half / snapshot slot of the newest demodulator launch
 	int prev_demod_buf = -1;            // ... and of the one before it
 };
-
-// a start / stop event pair for a timed launch: from the pool reset_timers() filled (no event creation between the timed launches of a
-// bench run), made on demand when a long run without a draining call has used the pool up -- a timed launch is never silently untimed
-static bool take_timer_pair(hfdl_gpu_frontend *fe, std::pair<hipEvent_t, hipEvent_t> &e)
-{
-	if (!fe->ev_pool.empty()) {
-		e = fe->ev_pool.back();
-		fe->ev_pool.pop_back();
-		return true;
-	}
-	if (hipEventCreate(&e.first) != hipSuccess) return false;
-	if (hipEventCreate(&e.second) != hipSuccess) { (void)hipEventDestroy(e.first); return false; }
-	return true;
-}
 
 static void frontend_free(hfdl_gpu_frontend *fe)
 {
@@ -251,12 +312,8 @@ static void frontend_free(hfdl_gpu_frontend *fe)
 	for (hipEvent_t e : fe->ev_stage_ready) if (e) (void)hipEventDestroy(e);
 	for (hipEvent_t e : fe->ev_stage_free) if (e) (void)hipEventDestroy(e);
 	for (auto &h : fe->ev_dm) for (hipEvent_t e : h) if (e) (void)hipEventDestroy(e);
-	for (auto &e : fe->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-	for (auto &e : fe->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-	for (auto &e : fe->ev_dmt) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-	for (auto *v : { &fe->ev_fftt, &fe->ev_ifftt, &fe->ev_dect }) for (auto &e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+	fe->timers.release();
 	if (fe->ev_fft) (void)hipEventDestroy(fe->ev_fft);
-	if (fe->ev_first_fold) (void)hipEventDestroy(fe->ev_first_fold);
 	fe->demod.release();
 	fe->fft.release();
 	void *ptrs[] = { fe->d_hist[0], fe->d_hist[1], fe->d_work, fe->d_spec, fe->d_taps, fe->d_partial, fe->d_chan_all, fe->d_tw_m,
@@ -797,7 +854,7 @@ static int queue_input_copy(hfdl_gpu_frontend *fe, const void *const *iq, size_t
 	return 0;
 }
 
-// Host input is staged in HBM: the copies (stream C) run up to a whole half ahead of the blocks that compute (stream A).
+// Host input is staged in HBM: the copies (stream C) run up to n_stage - 1 blocks ahead of the blocks that compute (stream A).
 // iq[0 .. nrx - 1]: one block of every receiver; in.fresh[] receives where the forward FFT reads them.
 // *stage_idx = staging buffer used (-1 for device input): the forward FFT's first pass signals ev_stage_free when it has read it.
 static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int fmt, int on_device, FftInputs &in, int *stage_idx)
@@ -857,23 +914,15 @@ static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, bool after_fft
 		// the done event rides on the kernel's dispatch; with the decoder on its own stream the channelizer has already waited for the
 		// frame queue (close_half), so on the demodulator-bound geometries ONE barrier packet separates consecutive demodulators
 		hipEvent_t t_start = nullptr, done = fe->ev_dm[buf][l];
-		std::pair<hipEvent_t, hipEvent_t> e;
-		if (fe->timing && take_timer_pair(fe, e)) {
-			// the kernel's own start / stop events (no extra packet): the stop event doubles as this launch's "done" event
-			t_start = e.first; done = e.second;
-			fe->ev_dmt.push_back(e);
-			fe->demod_timed_blocks += take;
-		}
+		int rc = fe->timers.arm(ST_DEMOD, take, t_start, done);
+		if (rc) return rc;
 		fe->ev_dm_cur[buf] = done;           // after the loop: the LAST launch of the half
 		const int slot = buf * fe->half_blocks + j0;
-		int rc = fe->demod.enqueue_demod(fe->chan_slot(slot), fe->cnt_slot(slot), take, fe->stream_b, done, l == 0 && fe->frames_wait_on_a, t_start);
+		rc = fe->demod.enqueue_demod(fe->chan_slot(slot), fe->cnt_slot(slot), take, fe->stream_b, done, l == 0 && fe->frames_wait_on_a, t_start);
 		if (rc) return fail(rc, "demod enqueue failed: %s", hipGetErrorString(hipGetLastError()));
 		if (fe->own_decode_stream) HIP_TRY(hipStreamWaitEvent(fe->stream_d, done, 0));
 		hipEvent_t k5_start = nullptr, k5_stop = nullptr;
-		if (fe->timing && take_timer_pair(fe, e)) {
-			k5_start = e.first; k5_stop = e.second;
-			fe->ev_dect.push_back(e);
-		}
+		if ((rc = fe->timers.arm(ST_DECODE, take, k5_start, k5_stop))) return rc;
 		rc = fe->demod.enqueue_decode(buf, fe->stream_d, k5_start, k5_stop);
 		if (rc) return fail(rc, "burst decoder enqueue failed: %s", hipGetErrorString(hipGetLastError()));
 	}
@@ -909,12 +958,9 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 	job.ph = fe->ph_slot(set, i); job.cont = fe->d_ph_cont;
 	job.nch = g.nch; job.outs = g.outs; job.post_input_size = g.post_input_size; job.post = g.post;
 	hipEvent_t fft_done = fe->fft_own_stream ? fe->ev_spec[set] : (pend ? fe->ev_fft : nullptr), fft_start = nullptr;
-	std::pair<hipEvent_t, hipEvent_t> e;
-	if (fe->timing && !fe->fft_own_stream && take_timer_pair(fe, e)) {
-		// the first pass' start and the last pass' stop ride on their dispatches; the stop event doubles as "this forward FFT is done"
-		fft_start = e.first; fft_done = e.second;
-		fe->ev_fftt.push_back(e);
-	}
+	// timed: the first pass' start and the last pass' stop ride on their dispatches; the stop event doubles as "this forward FFT is done"
+	if (!fe->fft_own_stream)
+		if (int rc = fe->timers.arm(ST_FFT, 1, fft_start, fft_done)) return rc;
 	if (pend) fe->ev_fft_cur = fft_done;
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
@@ -943,23 +989,15 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	const Geometry &g = fe->geo;
 	const int half = fe->cur_half;
 	if (fe->fft_own_stream) HIP_TRY(hipStreamWaitEvent(fe->stream, fe->ev_spec[half], 0));      // the newest forward FFT of this half (stream F)
-	// one launch per `fold_nb` blocks (a half holds a whole number of them only when it is full), each timed and counted AS LAUNCHED: the
-	// shape the bench prices is a launch that happened
+	// launches of up to `fold_nb` blocks (fold_launch_blocks), each timed and counted as the launch it is: the shape the bench prices is a
+	// launch that happened
 	for (int done = 0, take = 0; done < nblk; done += take) {
-		take = std::min(fe->fold_nb, nblk - done);
-		// a ragged rest of 17 .. 20 blocks: sixteen columns, then the four-column form (3.9 + 2.7 ms) -- thirty-two columns cost their 6.8 ms
-		// whatever the block count
-		if (take > 16 && take <= 20) take = 16;
-		float2 *pp = fe->d_partial + (size_t)done * fe->partial_stride();
-		if (fe->timing) {
-			std::pair<hipEvent_t, hipEvent_t> e;
-			if (!take_timer_pair(fe, e)) return fail(HFDL_GPU_EHIP, "hipEventCreate: %s", hipGetErrorString(hipGetLastError()));
-			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), fe->spec_stride(), pp, fe->partial_stride(), take, fe->fold_nb, fe->stream, e.first, e.second);
-			fe->ev.push_back(e);
-			fe->ev_blocks.push_back(take);
-		} else {
-			launch_fold(g, fe->d_taps, fe->spec_slot(half, done), fe->spec_stride(), pp, fe->partial_stride(), take, fe->fold_nb, fe->stream);
-		}
+		take = fold_launch_blocks(g, nblk - done, fe->fold_nb);
+		hipEvent_t start = nullptr, stop = nullptr;
+		if (int rc = fe->timers.arm(ST_FOLD, take, start, stop)) return rc;
+		if (launch_fold(g, fe->d_taps, fe->spec_slot(half, done), fe->spec_stride(), fe->d_partial + (size_t)done * fe->partial_stride(), fe->partial_stride(),
+				take, fe->stream, start, stop) < 0)
+			return fail(HFDL_GPU_EINVAL, "no fold launch of %d blocks on this geometry", take);
 	}
 	// this half is free once the demodulator launches that read it last (two halves ago) are done
 	if (fe->ev_dm_cur[half]) HIP_TRY(hipStreamWaitEvent(fe->stream, fe->ev_dm_cur[half], 0));
@@ -974,11 +1012,7 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	}
 	const int slot0 = half * fe->half_blocks;
 	hipEvent_t ifft_start = nullptr, ifft_done = fe->ev_chan[half];
-	std::pair<hipEvent_t, hipEvent_t> e;
-	if (fe->timing && take_timer_pair(fe, e)) {
-		ifft_start = e.first; ifft_done = e.second;
-		fe->ev_ifftt.push_back(e);
-	}
+	if (int rc = fe->timers.arm(ST_IFFT, nblk, ifft_start, ifft_done)) return rc;
 	fe->ev_chan_cur[half] = ifft_done;
 	launch_ifft_nco(g, fe->d_partial, fe->partial_stride(), fe->d_cc, fe->snap_slot(half, 0), fe->ph_slot(half, 0), fe->ph_stride(), fe->d_tw_m,
 			fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, fe->stream, ifft_done, ifft_start);
@@ -1083,46 +1117,7 @@ extern "C" int hfdl_gpu_frontend_channel_receiver(const hfdl_gpu_frontend *fe, i
 
 static int drain_events(hfdl_gpu_frontend *fe)
 {
-	for (size_t i = 0; i < fe->ev.size(); i++) {
-		auto &e = fe->ev[i];
-		float ms = 0;
-		HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-		fe->fold_ms += ms;
-		fe->fold_launches++;
-		fe->fold_timed_blocks += fe->ev_blocks[i];
-		fe->fold_last_blocks = fe->ev_blocks[i];
-		if (fe->ev_blocks[i] >= 1 && fe->ev_blocks[i] <= FOLD_MAX_BLOCKS) { fe->fold_shapes[fe->ev_blocks[i]]++; fe->fold_shape_ms[fe->ev_blocks[i]] += ms; }
-		if (!fe->ev_first_fold) {
-			fe->ev_first_fold = e.first;            // kept until the next reset
-			HIP_TRY(hipEventCreate(&e.first));
-		} else {
-			HIP_TRY(hipEventElapsedTime(&ms, fe->ev_first_fold, e.first));
-			fe->span_ms = ms;
-		}
-		fe->ev_pool.push_back(e);                   // both events are complete: reused by later launches
-	}
-	fe->ev.clear();
-	fe->ev_blocks.clear();
-	for (auto &e : fe->ev_dmt) {
-		float ms = 0;
-		HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-		fe->demod_ms += ms;
-		fe->demod_launches++;
-		fe->ev_pool.push_back(e);
-	}
-	fe->ev_dmt.clear();
-	struct { std::vector<std::pair<hipEvent_t, hipEvent_t>> *v; double *ms; int64_t *n; } more[] = {
-		{ &fe->ev_fftt, &fe->fft_ms, &fe->fft_timed }, { &fe->ev_ifftt, &fe->ifft_ms, &fe->ifft_timed }, { &fe->ev_dect, &fe->decode_ms, &fe->decode_timed } };
-	for (auto &m : more) {
-		for (auto &e : *m.v) {
-			float ms = 0;
-			HIP_TRY(hipEventElapsedTime(&ms, e.first, e.second));
-			*m.ms += ms;
-			(*m.n)++;
-			fe->ev_pool.push_back(e);
-		}
-		m.v->clear();
-	}
+	if (int rc = fe->timers.drain()) return rc;
 	// everything is complete: the pooled events may be reused (a completed event stands for "done" as well as the half's own)
 	for (int i = 0; i < 2; i++) if (fe->ev_dm_cur[i]) fe->ev_dm_cur[i] = fe->ev_dm[i][0];
 	for (int i = 0; i < 2; i++) fe->ev_chan_cur[i] = nullptr;
@@ -1218,21 +1213,7 @@ extern "C" int hfdl_gpu_frontend_reset_timers(hfdl_gpu_frontend *fe, int enable)
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	fe->fold_ms = 0; fe->fold_launches = 0; fe->fold_timed_blocks = 0; fe->fold_last_blocks = 0; fe->timing = enable != 0;
-	for (auto &c : fe->fold_shapes) c = 0;
-	for (auto &c : fe->fold_shape_ms) c = 0;
-	fe->demod_ms = 0; fe->demod_launches = 0; fe->demod_timed_blocks = 0;
-	fe->fft_ms = fe->ifft_ms = fe->decode_ms = 0; fe->fft_timed = fe->ifft_timed = fe->decode_timed = 0;
-	if (fe->ev_first_fold) { (void)hipEventDestroy(fe->ev_first_fold); fe->ev_first_fold = nullptr; }
-	fe->span_ms = 0;
-	// enough event pairs for the launches between two drains (a sync / poll recycles them): created here, not in the timed loop
-	while (enable && fe->ev_pool.size() < 1280) {
-		std::pair<hipEvent_t, hipEvent_t> e;
-		HIP_TRY(hipEventCreate(&e.first));
-		HIP_TRY(hipEventCreate(&e.second));
-		fe->ev_pool.push_back(e);
-	}
-	return 0;
+	return fe->timers.reset(enable != 0);
 }
 
 extern "C" int hfdl_gpu_frontend_fold_time_ms(hfdl_gpu_frontend *fe, double *total_ms, int64_t *launches)
@@ -1240,8 +1221,8 @@ extern "C" int hfdl_gpu_frontend_fold_time_ms(hfdl_gpu_frontend *fe, double *tot
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	if (total_ms) *total_ms = fe->fold_ms;
-	if (launches) *launches = fe->fold_launches;
+	if (total_ms) *total_ms = fe->timers.stage[ST_FOLD].ms;
+	if (launches) *launches = fe->timers.stage[ST_FOLD].launches;
 	return 0;
 }
 
@@ -1250,8 +1231,8 @@ extern "C" int hfdl_gpu_frontend_fold_launch_shapes(hfdl_gpu_frontend *fe, int64
 	if (!fe || !counts) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	for (int i = 0; i <= FOLD_MAX_BLOCKS; i++) counts[i] = fe->fold_shapes[i];
-	if (ms) for (int i = 0; i <= FOLD_MAX_BLOCKS; i++) ms[i] = fe->fold_shape_ms[i];
+	for (int i = 0; i <= FOLD_MAX_BLOCKS; i++) counts[i] = fe->timers.fold_shapes[i];
+	if (ms) for (int i = 0; i <= FOLD_MAX_BLOCKS; i++) ms[i] = fe->timers.fold_shape_ms[i];
 	return 0;
 }
 
@@ -1260,7 +1241,7 @@ extern "C" int hfdl_gpu_frontend_fold_blocks(hfdl_gpu_frontend *fe, int64_t *blo
 	if (!fe || !blocks) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	*blocks = fe->fold_timed_blocks;
+	*blocks = fe->timers.stage[ST_FOLD].blocks;
 	return 0;
 }
 
@@ -1269,9 +1250,10 @@ extern "C" int hfdl_gpu_frontend_demod_time_ms(hfdl_gpu_frontend *fe, double *to
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	if (total_ms) *total_ms = fe->demod_ms;
-	if (launches) *launches = fe->demod_launches;
-	if (blocks) *blocks = fe->demod_timed_blocks;
+	const LaunchTimers::Totals &t = fe->timers.stage[ST_DEMOD];
+	if (total_ms) *total_ms = t.ms;
+	if (launches) *launches = t.launches;
+	if (blocks) *blocks = t.blocks;
 	return 0;
 }
 
@@ -1280,8 +1262,7 @@ extern "C" int hfdl_gpu_frontend_stage_times(hfdl_gpu_frontend *fe, double ms[5]
 	if (!fe || !ms || !launches) return fail(HFDL_GPU_EINVAL, "null argument");
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
-	ms[0] = fe->fft_ms; ms[1] = fe->fold_ms; ms[2] = fe->ifft_ms; ms[3] = fe->demod_ms; ms[4] = fe->decode_ms;
-	launches[0] = fe->fft_timed; launches[1] = fe->fold_launches; launches[2] = fe->ifft_timed; launches[3] = fe->demod_launches; launches[4] = fe->decode_timed;
+	for (int s = 0; s < ST_N; s++) { ms[s] = fe->timers.stage[s].ms; launches[s] = fe->timers.stage[s].launches; }
 	return 0;
 }
 
@@ -1291,8 +1272,9 @@ extern "C" int hfdl_gpu_frontend_step_period_ms(hfdl_gpu_frontend *fe, double *p
 	int rc = hfdl_gpu_frontend_sync(fe);
 	if (rc) return rc;
 	// first timed fold start -> last timed fold start covers every timed block but the last launch's; per BLOCK
-	const int64_t covered = fe->fold_timed_blocks - fe->fold_last_blocks;
-	*period_ms = (fe->fold_launches > 1 && covered > 0) ? fe->span_ms / (double)covered : 0.0;
+	const LaunchTimers &t = fe->timers;
+	const int64_t covered = t.stage[ST_FOLD].blocks - t.fold_last_blocks;
+	*period_ms = (t.stage[ST_FOLD].launches > 1 && covered > 0) ? t.span_ms / (double)covered : 0.0;
 	return 0;
 }
 

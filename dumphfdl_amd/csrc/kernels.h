@@ -139,12 +139,15 @@ inline void launch_fft_forward(const FftPlan &p, const float2 *hist, const void 
 	in.fresh[0] = fresh;
 	launch_fft_forward(p, hist, in, fmt, split, hist_next, work, out, shifted, st, lay, done, nco, input_read, start);
 }
+// Blocks the next fold launch takes of the `remaining` ones, at most `nb_max`: the one rule for the size of a fold launch.
+int fold_launch_blocks(const Geometry &g, int remaining, int nb_max);
 // optional events ride on the kernel dispatches themselves (hipExtLaunchKernelGGL): no separate barrier packets in the queue
-// `nb` consecutive blocks: spectra `spec_stride` cf32 apart (each block's receivers g.spec_rx_stride apart inside that), partial sums
-// `partial_stride` apart, indexed by CHANNEL (padding slots are skipped); launches of at most `nb_max` blocks
-// sharing one pass over the taps.  Returns the number of kernel launches made.
+// ONE tiling launch -- one pass over the taps -- for `nb` consecutive blocks: spectra `spec_stride` cf32 apart (each block's receivers
+// g.spec_rx_stride apart inside that), partial sums `partial_stride` apart, indexed by CHANNEL (padding slots are skipped).  `nb` must
+// be what fold_launch_blocks(g, nb, FOLD_MAX_BLOCKS) allows.  Returns the number of kernel launches made (the octets left over by the
+// tiling's workgroups take a second one), -1 for a block count this geometry does not launch at once.
 int launch_fold(const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial, size_t partial_stride,
-		int nb, int nb_max, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+		int nb, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // the compiled tilings (the laboratory build carries the sweep set, profiles/fold_variants.py); launch one of them on `nb` spectra.
 // variant -1 = the plain-VALU FMA-chain reference kernel every tiling must equal bit for bit
 int fold_variant_count();

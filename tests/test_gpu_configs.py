@@ -292,6 +292,82 @@ def test_poll_sequence_drain_then_snapshot(gpu):
     fe.close()
 
 
+def _small_octet_frontend(gpu):
+    """2.4 Msps, 16 channels (two octets, fewer than the 128 that make the fold bound the block: every half takes fold_batch blocks)."""
+    fs, cf = 2_400_000, 10_000_000
+    fe = gpu.Frontend(fs, cf, [cf + (i - 8) * 15_000 + 4_000 for i in range(16)])
+    rng = np.random.default_rng(3)
+    x = ((rng.standard_normal(64 * fe.input_size) + 1j * rng.standard_normal(64 * fe.input_size)) * 0.02).astype(np.complex64)
+    return fe, x
+
+
+@pytest.mark.parametrize("fold_batch", [None, 32])
+def test_launch_timers_add_up(gpu, monkeypatch, fold_batch):
+    """The timers of every stage count each timed launch once: whole halves, halves a sync / poll closes part-filled (a 20-block rest
+    runs as 16 + 4), the fold totals of fold_time_ms / fold_launch_shapes / fold_blocks / stage_times agree, every pushed block is
+    folded, demodulated and forward-transformed once -- and reset_timers(False) zeroes everything and times nothing after."""
+    if fold_batch:
+        monkeypatch.setenv("HFDL_GPU_FOLD_BATCH", str(fold_batch))
+    fe, x = _small_octet_frontend(gpu)
+    monkeypatch.delenv("HFDL_GPU_FOLD_BATCH", raising=False)
+    n = fe.input_size
+    fe.reset_timers(True)
+    b = 0
+    for count, cut in ((32, "S"), (20, "S"), (5, "P"), (3, "R")):
+        for _ in range(count):
+            fe.push_block(x[b * n:(b + 1) * n])
+            b += 1
+        if cut == "S":
+            fe.sync()
+        elif cut == "P":
+            fe.poll_pdus()
+        else:
+            fe.poll_pdus(max_in_flight=1)
+    fe.sync()
+    shapes = fe.fold_launch_shapes()
+    fold_ms, fold_n = fe.fold_time_ms()
+    st = fe.stage_times()
+    assert fold_n > 0 and fold_n == sum(shapes.values()) == st["fold"][1]
+    assert sum(k * c for k, c in shapes.items()) == fe.fold_blocks() == b
+    assert st["fold"][0] == fold_ms > 0
+    demod_ms, demod_n, demod_blocks = fe.demod_time_ms()
+    assert (st["demod"][0], st["demod"][1]) == (demod_ms, demod_n) and demod_n > 0 and demod_blocks == b
+    assert st["fft"][1] == b and st["ifft"][1] > 0 and st["decode"][1] == demod_n
+    assert fe.step_period_ms() > 0
+    if fold_batch == 32:
+        assert shapes.get(16, 0) >= 1 and shapes.get(4, 0) >= 1 and max(shapes) <= 32, shapes       # the 20-block rest: 16 + 4
+    else:
+        assert max(shapes) <= fe.geometry.fold_batch, shapes
+    fe.reset_timers(False)
+    for i in range(10):
+        fe.push_block(x[i * n:(i + 1) * n])
+    fe.sync()
+    assert fe.fold_time_ms() == (0.0, 0) and fe.fold_launch_shapes() == {} and fe.fold_blocks() == 0
+    assert fe.demod_time_ms() == (0.0, 0, 0) and fe.step_period_ms() == 0.0
+    assert all(v == (0.0, 0) for v in fe.stage_times().values())
+    fe.close()
+
+
+def test_pruned_fold_launches_are_reported_as_launched(gpu, monkeypatch):
+    """The pruned fold has the sixteen-column form only: a 32-block half runs as two 16-block launches, and fold_launch_shapes()
+    reports those two launches (not one 32-block launch the bench would price as the thirty-two-column form)."""
+    monkeypatch.setenv("HFDL_GPU_FOLD_BATCH", "32")
+    monkeypatch.setenv("HFDL_GPU_FOLD_PRUNE", "3e-7")
+    fe, x = _small_octet_frontend(gpu)
+    monkeypatch.delenv("HFDL_GPU_FOLD_BATCH")
+    monkeypatch.delenv("HFDL_GPU_FOLD_PRUNE")
+    g = fe.geometry
+    assert g.fold_batch == 32 and g.fold_rows < g.pre_decimation, (g.fold_batch, g.fold_rows, g.pre_decimation)
+    n = fe.input_size
+    fe.reset_timers(True)
+    for b in range(32):
+        fe.push_block(x[b * n:(b + 1) * n])
+    fe.sync()
+    assert fe.fold_launch_shapes() == {16: 2}
+    assert fe.fold_blocks() == 32 and fe.fold_time_ms()[1] == 2
+    fe.close()
+
+
 def _run_bench(args, nproc, port, tmp_path, tag, backend="gloo"):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     dump = str(tmp_path / tag)
