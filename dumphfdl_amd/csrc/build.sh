@@ -21,9 +21,11 @@ $HIPCC $COMMON -c fft_kernels.hip -o $BUILD/fft_kernels.o & pids="$pids $!"
 $HIPCC $COMMON -c fold_kernels.hip -o $BUILD/fold_kernels.o & pids="$pids $!"
 # demodulator: no FMA contraction, so the fp32 recurrences round exactly like the plain-C oracle's
 $HIPCC $COMMON -ffp-contract=off -c demod_kernels.hip -o $BUILD/demod_kernels.o & pids="$pids $!"
+# spectrum monitor: no FMA contraction either -- its fp32 sums are what tests/spectrum_f64.py emulates term for term
+$HIPCC $COMMON -ffp-contract=off -c spectrum_kernels.hip -o $BUILD/spectrum_kernels.o & pids="$pids $!"
 $HIPCC $COMMON -x hip -c hfdl_gpu.cpp -o $BUILD/hfdl_gpu.o & pids="$pids $!"
 for p in $pids; do wait $p; done          # set -e: a failed compile stops the build here instead of linking stale objects
 # -Bsymbolic: calls between the library's own entry points stay inside THIS library when the product and the laboratory build
 # are loaded into one process
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT $BUILD/fft_kernels.o $BUILD/fold_kernels.o $BUILD/demod_kernels.o $BUILD/hfdl_gpu.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT $BUILD/fft_kernels.o $BUILD/fold_kernels.o $BUILD/demod_kernels.o $BUILD/spectrum_kernels.o $BUILD/hfdl_gpu.o
 echo "built $(readlink -f $OUT)"

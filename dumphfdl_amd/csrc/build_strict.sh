@@ -10,11 +10,11 @@ cd "$(dirname "$0")"
 OUTDIR=../../build/strict
 mkdir -p $OUTDIR
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-for o in fft_kernels.o fold_kernels.o hfdl_gpu.o; do [ -f ../build/$o ] || bash build.sh > /dev/null; done
+for o in fft_kernels.o fold_kernels.o spectrum_kernels.o hfdl_gpu.o; do [ -f ../build/$o ] || bash build.sh > /dev/null; done
 pids=""
 for F in ${@:-0 1 2 4 8 15}; do
 	( $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off -DHFDL_DM_STRICT_FAST=$F -I. -c ../../tests/hostsim/strict_demod_kernels.hip -o $OUTDIR/demod_kernels_$F.o &&
-	  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUTDIR/libhfdl_gpu_strict_$F.so ../build/fft_kernels.o ../build/fold_kernels.o $OUTDIR/demod_kernels_$F.o ../build/hfdl_gpu.o ) & pids="$pids $!"
+	  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUTDIR/libhfdl_gpu_strict_$F.so ../build/fft_kernels.o ../build/fold_kernels.o $OUTDIR/demod_kernels_$F.o ../build/spectrum_kernels.o ../build/hfdl_gpu.o ) & pids="$pids $!"
 done
 for p in $pids; do wait $p; done
 ls -la $OUTDIR/*.so

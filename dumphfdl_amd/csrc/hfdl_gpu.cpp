@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "planner.h"
 #include "demod.h"
+#include "spectrum.h"
 
 using namespace hfdl;
 
@@ -295,7 +296,28 @@ struct hfdl_gpu_frontend {
 	hipEvent_t ev_fft = nullptr;
 	int demod_buf = -1;                 // half / snapshot slot of the newest demodulator launch
 	int prev_demod_buf = -1;            // ... and of the one before it
+	// Spectrum monitor (hfdl_gpu_frontend_spectrum_enable; spectrum.h): off = no buffer, no launch.  One launch per step behind the forward
+	// FFT's last pass; ev_mon rides on that dispatch, so a read waits for the newest launch without a packet of its own on the stream.
+	int mon_bins = 0;                   // 0: off
+	uint32_t mon_flags = 0;
+	float2 *d_mon_acc = nullptr;        // [nrx][bins] { sum, compensation } of the band powers
+	float *d_mon_peak = nullptr;        // [nrx][bins] with MAXHOLD
+	float *h_mon = nullptr;             // page-locked bounce buffer of a read: [bins] float2 + [bins] float
+	hipEvent_t ev_mon = nullptr;
+	uint64_t mon_fresh = 0;             // receivers whose accumulators the next launch overwrites (after enable / a read with reset)
+	std::vector<uint64_t> mon_blocks, mon_first;       // [nrx] blocks accumulated since the receiver's last reset, index of the first of them
 };
+
+// the monitor's buffers, once nothing queued uses them any more
+static void spectrum_release(hfdl_gpu_frontend *fe)
+{
+	if (fe->ev_mon) { (void)hipEventSynchronize(fe->ev_mon); (void)hipEventDestroy(fe->ev_mon); fe->ev_mon = nullptr; }
+	if (fe->d_mon_acc) (void)hipFree(fe->d_mon_acc);
+	if (fe->d_mon_peak) (void)hipFree(fe->d_mon_peak);
+	if (fe->h_mon) (void)hipHostFree(fe->h_mon);
+	fe->d_mon_acc = nullptr; fe->d_mon_peak = nullptr; fe->h_mon = nullptr;
+	fe->mon_bins = 0; fe->mon_flags = 0;
+}
 
 static void frontend_free(hfdl_gpu_frontend *fe)
 {
@@ -313,6 +335,7 @@ static void frontend_free(hfdl_gpu_frontend *fe)
 	for (hipEvent_t e : fe->ev_stage_free) if (e) (void)hipEventDestroy(e);
 	for (auto &h : fe->ev_dm) for (hipEvent_t e : h) if (e) (void)hipEventDestroy(e);
 	fe->timers.release();
+	spectrum_release(fe);
 	if (fe->ev_fft) (void)hipEventDestroy(fe->ev_fft);
 	fe->demod.release();
 	fe->fft.release();
@@ -968,6 +991,19 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 			FftOutLayout(), fft_done, job,
 			stage_idx >= 0 ? fe->ev_stage_free[stage_idx] : nullptr,        // input consumed once pass 1 is done: the copy stream may refill the buffer
 			fft_start);
+	if (fe->mon_bins) {
+		// the spectrum monitor: one launch behind the last pass; the timed pair and the events other streams wait for stay on that pass
+		SpecmonJob m;
+		m.spec = fe->spec_slot(set, i); m.rx_stride = g.n; m.n = g.n; m.bins = fe->mon_bins; m.nrx = fe->nrx; m.flags = fe->mon_flags;
+		m.scale = (float)(1.0 / ((double)g.n * (double)g.n * ((fe->mon_flags & SPECMON_HANN) ? 0.375 : 1.0)));
+		m.fresh = fe->mon_fresh; m.acc = fe->d_mon_acc; m.peak = fe->d_mon_peak;
+		launch_spectrum_monitor(m, fe->stream_f, fe->ev_mon);
+		for (int r = 0; r < fe->nrx; r++) {
+			if ((fe->mon_fresh >> r) & 1) { fe->mon_blocks[(size_t)r] = 0; fe->mon_first[(size_t)r] = fe->blocks; }
+			fe->mon_blocks[(size_t)r]++;
+		}
+		fe->mon_fresh = 0;
+	}
 	if (pend) {
 		int rc = flush_pending_demod(fe, true);
 		if (rc) return rc;
@@ -1335,6 +1371,63 @@ extern "C" int hfdl_gpu_frontend_all_channel_stats(hfdl_gpu_frontend *fe, hfdl_g
 	if (rc) return fail(rc, "stats read failed: %s", hipGetErrorString(hipGetLastError()));
 	for (int i = 0; i < fe->geo.nch; i++) out[i].freq = fe->freqs[(size_t)i];
 	*n = fe->geo.nch;
+	return 0;
+}
+
+static_assert(HFDL_GPU_SPECTRUM_HANN == SPECMON_HANN && HFDL_GPU_SPECTRUM_MAXHOLD == SPECMON_MAXHOLD, "include/hfdl_gpu.h and spectrum.h name the same flags");
+static_assert(HFDL_GPU_RECEIVERS_MAX <= 64, "SpecmonJob::fresh is one bit per receiver");
+
+extern "C" int hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t bins, uint32_t flags)
+{
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (flags & ~(HFDL_GPU_SPECTRUM_HANN | HFDL_GPU_SPECTRUM_MAXHOLD)) return fail(HFDL_GPU_EINVAL, "unknown spectrum flags 0x%x", flags);
+	if (bins != 0 && (bins < 16 || (bins & (bins - 1)) != 0)) return fail(HFDL_GPU_EINVAL, "spectrum bins %d: a power of two >= 16 (or 0 = off)", bins);
+	if (bins > fe->geo.n / 16) return fail(HFDL_GPU_ERANGE, "spectrum bins %d: at most fft_size / 16 = %d", bins, fe->geo.n / 16);
+	HIP_TRY(hipSetDevice(fe->device));
+	spectrum_release(fe);                  // waits for the monitor launches queued so far, nothing else
+	if (bins == 0) return 0;
+	const size_t nb = (size_t)bins, K = (size_t)fe->nrx;
+	hipError_t e = hipMalloc(&fe->d_mon_acc, sizeof(float2) * nb * K);
+	if (e == hipSuccess && (flags & HFDL_GPU_SPECTRUM_MAXHOLD)) e = hipMalloc(&fe->d_mon_peak, sizeof(float) * nb * K);
+	if (e == hipSuccess) e = hipHostMalloc((void **)&fe->h_mon, sizeof(float) * 3 * nb, hipHostMallocDefault);
+	if (e == hipSuccess) e = hipEventCreateWithFlags(&fe->ev_mon, hipEventDisableTiming);
+	if (e != hipSuccess) {
+		spectrum_release(fe);
+		return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "spectrum monitor buffers: %s", hipGetErrorString(e));
+	}
+	fe->mon_bins = bins;
+	fe->mon_flags = flags;
+	fe->mon_fresh = ~(uint64_t)0;          // every receiver starts over with the next block: nothing to clear on the device
+	fe->mon_blocks.assign(K, 0);
+	fe->mon_first.assign(K, 0);
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_spectrum_read(hfdl_gpu_frontend *fe, int32_t rx, float *mean, float *peak, int32_t cap,
+		uint64_t *blocks, uint64_t *first_block, int reset)
+{
+	if (!fe || !mean || !blocks || !first_block) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (!fe->mon_bins) return fail(HFDL_GPU_EINVAL, "the spectrum monitor is off: hfdl_gpu_frontend_spectrum_enable() first");
+	if (rx < 0 || rx >= fe->nrx) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	if (peak && !(fe->mon_flags & HFDL_GPU_SPECTRUM_MAXHOLD)) return fail(HFDL_GPU_EINVAL, "peak asked for, but the monitor was enabled without HFDL_GPU_SPECTRUM_MAXHOLD");
+	if (cap < fe->mon_bins) return fail(HFDL_GPU_ERANGE, "%d bands, buffer holds %d", fe->mon_bins, cap);
+	const bool pending = (fe->mon_fresh >> rx) & 1;      // reset (or just enabled) and no block since
+	const uint64_t T = pending ? 0 : fe->mon_blocks[(size_t)rx];
+	*blocks = T;
+	*first_block = pending ? fe->blocks : fe->mon_first[(size_t)rx];
+	if (T == 0) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	// the collection stream waits for the newest monitor launch (its event rode on the dispatch) and copies beside the kernels in flight
+	const size_t nb = (size_t)fe->mon_bins;
+	hipStream_t st = fe->demod.st_collect;
+	HIP_TRY(hipStreamWaitEvent(st, fe->ev_mon, 0));
+	HIP_TRY(hipMemcpyAsync(fe->h_mon, fe->d_mon_acc + (size_t)rx * nb, sizeof(float2) * nb, hipMemcpyDeviceToHost, st));
+	if (peak) HIP_TRY(hipMemcpyAsync(fe->h_mon + 2 * nb, fe->d_mon_peak + (size_t)rx * nb, sizeof(float) * nb, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	for (size_t b = 0; b < nb; b++)       // Kahan: the compensation holds what the sum has gained too much
+		mean[b] = (float)(((double)fe->h_mon[2 * b] - (double)fe->h_mon[2 * b + 1]) / (double)T);
+	if (peak) memcpy(peak, fe->h_mon + 2 * nb, sizeof(float) * nb);
+	if (reset) fe->mon_fresh |= (uint64_t)1 << rx;
 	return 0;
 }
 

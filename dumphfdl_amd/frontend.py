@@ -73,11 +73,13 @@ EXPORTS = [
     "hfdl_gpu_fft_forward", "hfdl_gpu_viterbi27", "hfdl_gpu_burst_decode", "hfdl_gpu_nco_decimate", "hfdl_gpu_crc16_ccitt", "hfdl_gpu_pdu_triage", "hfdl_gpu_lpdu_walk", "hfdl_gpu_frontend_prefetch_block_raw", "hfdl_gpu_frontend_prefetch_cancel", "hfdl_gpu_psk_slice",
     "hfdl_gpu_last_error", "hfdl_gpu_device_count",
     "hfdl_gpu_frontend_create_multi", "hfdl_gpu_frontend_push_blocks_raw", "hfdl_gpu_frontend_channel_receiver",
+    "hfdl_gpu_frontend_spectrum_enable", "hfdl_gpu_frontend_spectrum_read",
 ]
 
 
 FOLD_BATCH_MAX = 32        # HFDL_GPU_FOLD_BATCH_MAX of include/hfdl_gpu.h
 RECEIVERS_MAX = 64         # HFDL_GPU_RECEIVERS_MAX
+SPECTRUM_HANN, SPECTRUM_MAXHOLD = 1, 2     # HFDL_GPU_SPECTRUM_*
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
@@ -182,6 +184,8 @@ def _bind(L):
     L.hfdl_gpu_frontend_create_multi.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hfdl_gpu_frontend_push_blocks_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
     L.hfdl_gpu_frontend_channel_receiver.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hfdl_gpu_frontend_spectrum_enable.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+    L.hfdl_gpu_frontend_spectrum_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
     return L
 
 
@@ -228,6 +232,8 @@ class Frontend:
         self.geometry = Geometry()
         _check(L.hfdl_gpu_frontend_geometry(self._h, C.byref(self.geometry)), self._L)
         self.freqs = [int(f) for f in fr]
+        self.centerfreq = int(centerfreq)
+        self._spec_bins, self._spec_peak = 0, False
 
     @property
     def input_size(self):
@@ -419,6 +425,40 @@ class Frontend:
     def stream(self):
         return self._L.hfdl_gpu_frontend_stream(self._h)
 
+    def _rx_center(self, rx):
+        return self.centerfreq
+
+    def spectrum_enable(self, bins, hann=False, maxhold=False):
+        """Spectrum monitor (include/hfdl_gpu.h): `bins` band powers per receiver from every block's forward FFT, from the next block on;
+        bins = 0 turns it off.  Calling it again starts every receiver's average over."""
+        flags = (SPECTRUM_HANN if hann else 0) | (SPECTRUM_MAXHOLD if maxhold else 0)
+        _check(self._L.hfdl_gpu_frontend_spectrum_enable(self._h, bins, flags), self._L)
+        self._spec_bins, self._spec_peak = int(bins), bool(maxhold)
+
+    def spectrum_band_centres(self, rx=0):
+        """Centre frequencies in Hz (float64) of the monitor's bands of receiver rx: band b spans centre +- G fs / 2N with
+        centre = centerfreq + (b G - N/2 - 0.5 + G/2) fs / N, G = N / bins."""
+        g = self.geometry
+        n, b = g.fft_size, self._spec_bins
+        G = n // b
+        return self._rx_center(rx) + (np.arange(b, dtype=np.float64) * G - n / 2 - 0.5 + G / 2) * (g.sample_rate / n)
+
+    def spectrum_read(self, rx=0, reset=False):
+        """dict(mean, peak (None without maxhold), blocks, first_block, freqs): linear band powers (float32; a full-scale tone = 1.0) of
+        receiver rx averaged / max-held over the `blocks` blocks since its last reset, the first of them block `first_block`; freqs =
+        the band centres in Hz.  Nothing accumulated yet: blocks = 0, mean (and peak) None.  Waits for the forward FFTs only."""
+        b = self._spec_bins
+        if not b:
+            raise GpuError("the spectrum monitor is off: spectrum_enable() first")
+        mean = np.zeros(b, np.float32)
+        peak = np.zeros(b, np.float32) if self._spec_peak else None
+        T, first = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.hfdl_gpu_frontend_spectrum_read(self._h, rx, _p(mean), _p(peak) if peak is not None else None, b,
+                                                       C.byref(T), C.byref(first), int(reset)), self._L)
+        if T.value == 0:
+            mean, peak = None, None
+        return dict(mean=mean, peak=peak, blocks=T.value, first_block=first.value, freqs=self.spectrum_band_centres(rx))
+
     def close(self):
         if self._h:
             self._L.hfdl_gpu_frontend_destroy(self._h)
@@ -447,11 +487,15 @@ class MultiFrontend(Frontend):
         self.geometry = Geometry()
         _check(L.hfdl_gpu_frontend_geometry(self._h, C.byref(self.geometry)), L)
         self.freqs = [int(f) for f in fr]
+        self._spec_bins, self._spec_peak = 0, False
         self._rx_of = [r for r, (_, fs) in enumerate(self.receivers) for _ in fs]
 
     @property
     def nrx(self):
         return len(self.receivers)
+
+    def _rx_center(self, rx):
+        return self.receivers[rx][0]
 
     def receiver_of(self, channel):
         """(receiver index, its centre frequency) of a global channel index."""

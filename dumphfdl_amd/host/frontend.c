@@ -20,10 +20,55 @@ struct gpu_fft_block {
 	float transition_bw;
 	int device;
 	hfdl_gpu_geometry geo;
+	char *spec_path;                 /* spectrum monitor as set when fft_create() ran (hfdl_frontend_set_spectrum); NULL = off */
+	int32_t spec_bins, spec_interval_s;
+	int spec_hann;
 };
 
 static int g_device = 0;
 void hfdl_frontend_set_device(int device) { g_device = device; }
+
+/* spectrum monitor of the next front end (hfdl_frontend_set_spectrum): path NULL = off */
+static struct { char *path; int32_t bins, interval_s; int hann; } g_spectrum;
+int hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t interval_s, int hann)
+{
+	if (path != NULL && (bins < 16 || bins > 4096 || (bins & (bins - 1)) != 0 || interval_s < 1)) return -1;
+	free(g_spectrum.path);
+	g_spectrum.path = path ? strdup(path) : NULL;
+	g_spectrum.bins = bins; g_spectrum.interval_s = interval_s; g_spectrum.hann = hann;
+	return 0;
+}
+
+/* ---- spectrum monitor: one rtl_power-compatible CSV line from a row of band powers (plain C, no device call; kept in this file
+ * because the test builds of the host library compile a fixed list of sources):
+ *   date, time, Hz low, Hz high, Hz step, samples, dB, dB, ...
+ * date / time: UTC of `t_unix` (the stream-start convention of the PDU timestamps: wall clock at start + signal time); Hz low / high:
+ * lower edge of the first and upper edge of the last band; Hz step: width of a band; samples: blocks averaged; one value per band,
+ * dB = 10 log10(mean) -- dBFS, a full-scale tone reads 0 -- with a floor of -200 for an empty band. ---- */
+
+int hfdl_spectrum_csv_line(char *buf, size_t cap, double t_unix, double hz_low, double hz_step, uint64_t samples, const float *mean, int32_t bins)
+{
+	if (buf == NULL || mean == NULL || bins < 1 || cap == 0) return -1;
+	time_t sec = (time_t)floor(t_unix);
+	struct tm tm;
+	if (gmtime_r(&sec, &tm) == NULL) return -1;
+	size_t n = strftime(buf, cap, "%Y-%m-%d, %H:%M:%S", &tm);
+	if (n == 0) return -1;
+	int k = snprintf(buf + n, cap - n, ", %.0f, %.0f, %.4f, %llu", hz_low, hz_low + hz_step * (double)bins, hz_step, (unsigned long long)samples);
+	if (k < 0 || (size_t)k >= cap - n) return -1;
+	n += (size_t)k;
+	for (int32_t b = 0; b < bins; b++) {
+		double db = mean[b] > 0.f ? 10.0 * log10((double)mean[b]) : -200.0;
+		if (!(db > -200.0)) db = -200.0;
+		k = snprintf(buf + n, cap - n, ", %.2f", db);
+		if (k < 0 || (size_t)k >= cap - n) return -1;
+		n += (size_t)k;
+	}
+	if (n + 2 > cap) return -1;
+	buf[n++] = '\n';
+	buf[n] = '\0';
+	return (int)n;
+}
 
 /* ---- libcsdr helpers main() needs (src/libcsdr.c:135-144) ---- */
 
@@ -307,6 +352,27 @@ static void *frontend_thread(void *ctx)
 	struct timeval t0;
 	gettimeofday(&t0, NULL);
 	const size_t need = ok ? (size_t)fb->geo.input_size : 1;
+	/* spectrum monitor: one CSV line per interval of SIGNAL (blocks pushed x block length / sample rate), read with reset */
+	FILE *spec_file = NULL;
+	float *spec_mean = NULL;
+	char *spec_line = NULL;
+	int32_t spec_bins = 0;
+	uint64_t spec_lines = 0;
+	if (ok && fb->spec_path != NULL) {
+		spec_bins = fb->spec_bins;
+		while (spec_bins > fb->geo.fft_size / 16) spec_bins /= 2;
+		spec_file = fopen(fb->spec_path, "w");       /* a run writes its own file: nothing of an earlier run stays in front of it */
+		if (spec_file == NULL || hfdl_gpu_frontend_spectrum_enable(fe, spec_bins, fb->spec_hann ? HFDL_GPU_SPECTRUM_HANN : 0u) != 0) {
+			fprintf(stderr, "spectrum monitor: %s\n", spec_file ? hfdl_gpu_last_error() : "cannot open the spectrum file");
+			if (spec_file) fclose(spec_file);
+			spec_file = NULL;
+			do_exit = 1;
+			ok = 0;
+		} else {
+			spec_mean = hfdl_xcalloc((size_t)spec_bins, sizeof(float));
+			spec_line = hfdl_xcalloc(64 + 12 * (size_t)spec_bins, 1);
+		}
+	}
 	const size_t elem = hfdl_ring_elem_size(ring->buf);
 	const int gfmt = gpu_format_of(hfdl_ring_format(ring->buf));
 	/* uploads ahead of the pushes: what the library allows, and what the ring can hold beside the block being pushed and room for
@@ -439,6 +505,26 @@ static void *frontend_thread(void *ctx)
 			uploads++;
 			leased++;
 		}
+		if (spec_file != NULL) {
+			const double fs = (double)slots[0]->sample_rate, step = (double)(fb->geo.fft_size / spec_bins) * fs / (double)fb->geo.fft_size;
+			if ((double)k * (double)need / fs >= (double)(spec_lines + 1) * (double)fb->spec_interval_s) {
+				uint64_t T = 0, first = 0;
+				const int rrc = hfdl_gpu_frontend_spectrum_read(fe, 0, spec_mean, NULL, spec_bins, &T, &first, 1);
+				if (rrc != 0) fprintf(stderr, "spectrum monitor: interval %llu has no line: %s\n", (unsigned long long)spec_lines, hfdl_gpu_last_error());
+				if (rrc == 0 && T > 0) {
+					/* stamped like the PDUs: wall clock at stream start + the signal time of the first block averaged */
+					const double t = (double)t0.tv_sec + 1e-6 * (double)t0.tv_usec + (double)first * (double)need / fs;
+					const double low = (double)slots[0]->centerfreq - (0.5 * (double)fb->geo.fft_size + 0.5) * fs / (double)fb->geo.fft_size;
+					if (hfdl_spectrum_csv_line(spec_line, 64 + 12 * (size_t)spec_bins, t, low, step, T, spec_mean, spec_bins) > 0) {
+						fputs(spec_line, spec_file);
+						fflush(spec_file);
+					} else {
+						fprintf(stderr, "spectrum monitor: interval %llu has no line: it does not fit the line buffer\n", (unsigned long long)spec_lines);
+					}
+				}
+				spec_lines++;
+			}
+		}
 		const double tw2 = now_s();
 		s_push += tw2 - tw1;
 		/* collect what is known to be complete without draining anything and WITHOUT waiting: what this thread may queue ahead is
@@ -486,6 +572,9 @@ shutdown:
 	}
 	block_connection_one2many_shutdown(down);
 	if (fe) hfdl_gpu_frontend_destroy(fe);
+	if (spec_file) fclose(spec_file);
+	free(spec_mean);
+	free(spec_line);
 	free(bounce);
 	free(pdus);
 	free(stats);
@@ -511,6 +600,8 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 	fb->decimation = decimation;
 	fb->transition_bw = transition_bw;
 	fb->device = g_device;
+	fb->spec_path = g_spectrum.path ? strdup(g_spectrum.path) : NULL;
+	fb->spec_bins = g_spectrum.bins; fb->spec_interval_s = g_spectrum.interval_s; fb->spec_hann = g_spectrum.hann;
 	fb->block.producer.type = PRODUCER_MULTI;
 	fb->block.producer.max_tu = (size_t)fb->geo.fft_size;
 	fb->block.consumer.type = CONSUMER_SINGLE;
@@ -521,5 +612,8 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 
 void fft_destroy(struct block *fft_block)
 {
-	if (fft_block) free(container_of(fft_block, struct gpu_fft_block, block));
+	if (fft_block == NULL) return;
+	struct gpu_fft_block *fb = container_of(fft_block, struct gpu_fft_block, block);
+	free(fb->spec_path);
+	free(fb);
 }

@@ -2,13 +2,17 @@
  * I/Q file, with the protocol parsers replaced by the library's printing pdu_decoder_queue_push().
  *
  *   hfdl_replay --iq-file FILE --sample-rate HZ --sample-format CF32|CS16|CU8 --centerfreq KHZ [--device N]
- *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N] FREQ_KHZ...
+ *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
+ *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]] FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
  * --bench       PDUs are counted instead of printed and one JSON line reports Msamples/s of the whole host path
  *               (file in page cache -> input block -> ring -> GPU front end -> pdu_decoder_queue_push), create time excluded.
  * --loop N      replay the file N times back to back (bench runs longer than the file).
+ * --spectrum-file PATH   every S seconds of signal (default 1) write one rtl_power-compatible CSV line of N band powers (default
+ *               1024; a power of two, 16 .. 4096) over the whole span to PATH: date, time, Hz low, Hz high, Hz step, samples, dB...
+ *               (hfdl_frontend_set_spectrum, include/hfdl_host.h); --spectrum-hann: Hann instead of the rectangular window.
  *
  * --statsd-print stands in for dumphfdl's src/statsd.c: the strong statsd_* hooks below print one "STATSD" line per
  * counter total at exit and one per noise-floor gauge as it arrives (metric names as in doc/STATSD_METRICS.md).
@@ -78,6 +82,8 @@ int main(int argc, char **argv)
 	double centerfreq_khz = -1;
 	int32_t freqs[4096];
 	int nfreq = 0, shard_rank = 0, shard_world = 1;
+	const char *spec_path = NULL;
+	int spec_bins = 1024, spec_interval = 1, spec_hann = 0;
 	for (int i = 1; i < argc; i++) {
 		if (!strcmp(argv[i], "--iq-file") && i + 1 < argc) cfg->source = argv[++i];
 		else if (!strcmp(argv[i], "--sample-rate") && i + 1 < argc) cfg->sample_rate = atoi(argv[++i]);
@@ -87,6 +93,10 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--device") && i + 1 < argc) hfdl_frontend_set_device(atoi(argv[++i]));
 		else if (!strcmp(argv[i], "--statsd-print")) statsd_print = 1;
 		else if (!strcmp(argv[i], "--bench")) bench_mode = 1;
+		else if (!strcmp(argv[i], "--spectrum-file") && i + 1 < argc) spec_path = argv[++i];
+		else if (!strcmp(argv[i], "--spectrum-bins") && i + 1 < argc) spec_bins = atoi(argv[++i]);
+		else if (!strcmp(argv[i], "--spectrum-interval") && i + 1 < argc) spec_interval = atoi(argv[++i]);
+		else if (!strcmp(argv[i], "--spectrum-hann")) spec_hann = 1;
 		else if (!strcmp(argv[i], "--loop") && i + 1 < argc) hfdl_file_input_set_loops(atoi(argv[++i]));
 		else if (!strcmp(argv[i], "--shard") && i + 1 < argc) {
 			if (sscanf(argv[++i], "%d/%d", &shard_rank, &shard_world) != 2 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) {
@@ -125,6 +135,10 @@ int main(int argc, char **argv)
 	if (input == NULL || input_init(input) < 0) { fprintf(stderr, "Unable to initialize input\n"); return 1; }
 	int32_t decimation = compute_fft_decimation_rate(cfg->sample_rate, HFDL_SYMBOL_RATE * SPS);
 	float tbw = compute_filter_relative_transition_bw(cfg->sample_rate, HFDL_CHANNEL_TRANSITION_BW_HZ);
+	if (spec_path != NULL && hfdl_frontend_set_spectrum(spec_path, spec_bins, spec_interval, spec_hann) != 0) {
+		fprintf(stderr, "--spectrum-bins wants a power of two from 16 to 4096, --spectrum-interval at least 1\n");
+		return 1;
+	}
 	struct block *fft = fft_create(decimation, tbw);
 	if (fft == NULL) return 1;
 	hfdl_init_globals();

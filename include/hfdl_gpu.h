@@ -273,6 +273,37 @@ int  hfdl_gpu_frontend_channel_stats(hfdl_gpu_frontend *fe, int32_t channel, hfd
  * straddle a block boundary (what a periodic gauge needs: noise_floor_stats_thread, src/hfdl.c:1082-1105) */
 int  hfdl_gpu_frontend_all_channel_stats(hfdl_gpu_frontend *fe, hfdl_gpu_channel_stats *out, int32_t cap, int32_t *n);
 
+/* Spectrum monitor (off by default): band powers of every receiver from the forward FFT's own spectra, accumulated on the device.
+ * For receiver r and block t let X[s], s = 0 .. N - 1 (N = geometry.fft_size) be the fftshifted spectrum of the block's overlap-and-
+ * scrap window [history, new]; shifted index s is the frequency centerfreq_r + (s - N/2) fs/N.  With bins = B and G = N / B:
+ *   window RECT (flags 0): Xw[s] = X[s], wpow = 1;
+ *   window HANN:           Xw[s] = 0.5 X[s] - 0.25 X[(s - 1) mod N] - 0.25 X[(s + 1) mod N], wpow = 0.375 -- the periodic Hann window
+ *                          w[n] = 0.5 - 0.5 cos(2 pi n / N) applied in the frequency domain, exactly FFT(w x);
+ *   band power of a block: p_t[b] = sum_{s = bG}^{(b+1)G - 1} |Xw[s]|^2 / (N^2 wpow): a full-scale tone (|x| = 1) adds 1.0 (0 dBFS) to
+ *                          the band(s) it falls in; with RECT the bands of a block sum to the mean |x|^2 of its window (Parseval);
+ *   read back:             mean[b] = (1/T) sum_t p_t[b] over the T blocks since the last reset and, with MAXHOLD, peak[b] = max_t p_t[b];
+ *                          linear power, fp32.
+ * Band b spans centerfreq_r + (bG - N/2 - 0.5) fs/N .. that + G fs/N.  Consecutive windows overlap by geometry.overlap_length
+ * samples: a Welch estimate with that fixed overlap.  The result for a given input, bins and flags is bit-identical from run to run
+ * and does not depend on how the caller polls or on fold / demodulator batching.  A block = one push (of every receiver) or one
+ * channelize_block; push_baseband is none. */
+#define HFDL_GPU_SPECTRUM_HANN    1u
+#define HFDL_GPU_SPECTRUM_MAXHOLD 2u
+/* bins: a power of two, 16 <= bins <= fft_size / 16; 0 turns the monitor off and frees its buffers.  Takes effect with the next
+ * pushed block; calling it again resets the accumulators of every receiver.  HFDL_GPU_EINVAL (null handle, unknown flag, bins no
+ * power of two or below 16) / HFDL_GPU_ERANGE (bins > fft_size / 16) are checked before any device work. */
+int  hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t bins, uint32_t flags);
+/* mean[bins] (and peak[bins]; may be NULL, HFDL_GPU_EINVAL if asked for without MAXHOLD) of receiver rx over the blocks accumulated
+ * since the last reset; cap = floats each array holds (HFDL_GPU_ERANGE below bins).  *blocks = T (0: nothing yet, the arrays are
+ * left untouched), *first_block = index of the first of them in the numbering of hfdl_gpu_frontend_counters().blocks.  reset != 0
+ * starts a new average for THIS receiver after the read.  The call queues nothing on the kernels' streams: no half is closed, no
+ * fold launched, the PDU stream is what it is without the read.  It BLOCKS until the newest forward FFT (and its monitor launch)
+ * has run.  The forward FFTs share a stream with the folds and inverse FFTs of the halves closed before them, and an inverse FFT
+ * waits for the demodulators that read its buffer last, so the caller in effect waits for the device to catch up to the newest
+ * pushed block (everything but the newest half's fold and demodulators): read every second of signal, not every block. */
+int  hfdl_gpu_frontend_spectrum_read(hfdl_gpu_frontend *fe, int32_t rx, float *mean, float *peak, int32_t cap,
+		uint64_t *blocks, uint64_t *first_block, int reset);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */

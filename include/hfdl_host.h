@@ -199,6 +199,17 @@ void statsd_gauge_per_channel_set(int32_t freq, char *gauge, size_t value);
 /* GPU selection for the front end created by the next fft_create() (default 0); not in the reference */
 void          hfdl_frontend_set_device(int device);
 
+/* Spectrum monitor of the front end created by the next fft_create() (include/hfdl_gpu.h, "Spectrum monitor"); not in the reference.
+ * Every interval_s seconds OF SIGNAL (sample clock: a file replay is reproducible) the front-end thread reads the band powers with
+ * reset and writes one rtl_power-compatible CSV line for the whole span to `path` (created or truncated when the front end starts; an
+ * interval whose read or line fails is reported on stderr and has no line).  bins: a power of two, 16 .. 4096 (cut down to
+ * fft_size / 16 on a small geometry); interval_s >= 1; hann != 0: Hann window.  path NULL: off.  Returns 0, or -1 for bad arguments. */
+int           hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t interval_s, int hann);
+/* The line: "date, time, Hz low, Hz high, Hz step, samples, dB, dB, ...\n" -- date / time = UTC of t_unix, Hz low / high = lower edge of
+ * the first / upper edge of the last band, Hz step = width of a band, samples = blocks averaged, dB = 10 log10(mean[b]) (dBFS; -200
+ * for an empty band).  No device is needed.  Returns the length written (without the terminating 0), -1 if it does not fit. */
+int           hfdl_spectrum_csv_line(char *buf, size_t cap, double t_unix, double hz_low, double hz_step, uint64_t samples, const float *mean, int32_t bins);
+
 /* What the front-end thread did, readable once its block has stopped running (not in the reference; hfdl_replay --bench):
  * seconds runs from the first block handed to the GPU to the last PDU handed to pdu_decoder_queue_push(). */
 struct hfdl_run_stats {
