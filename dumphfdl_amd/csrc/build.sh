@@ -5,6 +5,7 @@
 #                     include/hfdl_gpu_lab.h and the A/B environment switches (profiles/*.py, bench.py's stream-read probe)
 set -e
 cd "$(dirname "$0")"
+. ./objects.sh
 if [ "$1" = "lab" ]; then
 	OUT=${HFDL_OUT:-../libhfdl_gpu_lab.so}
 	BUILD=${HFDL_BUILD_DIR:-../build/lab}
@@ -17,15 +18,18 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${HFDL_EXTRA_FLAGS:-}"
 mkdir -p $BUILD
 pids=""
-$HIPCC $COMMON -c fft_kernels.hip -o $BUILD/fft_kernels.o & pids="$pids $!"
-$HIPCC $COMMON -c fold_kernels.hip -o $BUILD/fold_kernels.o & pids="$pids $!"
-# demodulator: no FMA contraction, so the fp32 recurrences round exactly like the plain-C oracle's
-$HIPCC $COMMON -ffp-contract=off -c demod_kernels.hip -o $BUILD/demod_kernels.o & pids="$pids $!"
-# spectrum monitor: no FMA contraction either -- its fp32 sums are what tests/spectrum_f64.py emulates term for term
-$HIPCC $COMMON -ffp-contract=off -c spectrum_kernels.hip -o $BUILD/spectrum_kernels.o & pids="$pids $!"
-$HIPCC $COMMON -x hip -c hfdl_gpu.cpp -o $BUILD/hfdl_gpu.o & pids="$pids $!"
+objs=""
+for o in $KERNEL_OBJS; do
+	case " $NO_CONTRACT_OBJS " in *" $o "*) contract=-ffp-contract=off ;; *) contract= ;; esac
+	$HIPCC $COMMON $contract -c $o.hip -o $BUILD/$o.o & pids="$pids $!"
+	objs="$objs $BUILD/$o.o"
+done
+for o in $SHIM_OBJS; do
+	$HIPCC $COMMON -x hip -c $o.cpp -o $BUILD/$o.o & pids="$pids $!"
+	objs="$objs $BUILD/$o.o"
+done
 for p in $pids; do wait $p; done          # set -e: a failed compile stops the build here instead of linking stale objects
 # -Bsymbolic: calls between the library's own entry points stay inside THIS library when the product and the laboratory build
 # are loaded into one process
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT $BUILD/fft_kernels.o $BUILD/fold_kernels.o $BUILD/demod_kernels.o $BUILD/spectrum_kernels.o $BUILD/hfdl_gpu.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT $objs
 echo "built $(readlink -f $OUT)"

@@ -4,17 +4,23 @@
 # shipped pipeline's fast forms switched back on per HFDL_DM_STRICT_FAST (1 sums, 2 AGC, 4 trig, 8 slicer).  Loaded through
 # HFDL_GPU_LIB by profiles/strict_study.py and tests/test_gpu_strict.py (which builds the two it needs when they are missing).
 # Output: build/strict/libhfdl_gpu_strict_<F>.so at the repository root -- outside the package.  Only the demodulator kernels are
-# compiled again (tests/hostsim/strict_demod_kernels.hip wraps demod_kernels.hip); the other objects are the product build's (dumphfdl_amd/build, made by build.sh).
+# compiled again (tests/hostsim/strict_demod_kernels.hip wraps demod_kernels.hip); the other objects are the product build's
+# (dumphfdl_amd/build, made by build.sh), the list of them is objects.sh's: a strict build links whatever the product links.
 set -e
 cd "$(dirname "$0")"
+. ./objects.sh
 OUTDIR=../../build/strict
 mkdir -p $OUTDIR
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-for o in fft_kernels.o fold_kernels.o spectrum_kernels.o hfdl_gpu.o; do [ -f ../build/$o ] || bash build.sh > /dev/null; done
+for o in $KERNEL_OBJS $SHIM_OBJS; do [ -f ../build/$o.o ] || bash build.sh > /dev/null; done
 pids=""
 for F in ${@:-0 1 2 4 8 15}; do
+	objs=""
+	for o in $KERNEL_OBJS $SHIM_OBJS; do
+		if [ $o = demod_kernels ]; then objs="$objs $OUTDIR/demod_kernels_$F.o"; else objs="$objs ../build/$o.o"; fi
+	done
 	( $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off -DHFDL_DM_STRICT_FAST=$F -I. -c ../../tests/hostsim/strict_demod_kernels.hip -o $OUTDIR/demod_kernels_$F.o &&
-	  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUTDIR/libhfdl_gpu_strict_$F.so ../build/fft_kernels.o ../build/fold_kernels.o $OUTDIR/demod_kernels_$F.o ../build/spectrum_kernels.o ../build/hfdl_gpu.o ) & pids="$pids $!"
+	  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUTDIR/libhfdl_gpu_strict_$F.so $objs ) & pids="$pids $!"
 done
 for p in $pids; do wait $p; done
 ls -la $OUTDIR/*.so

@@ -1,0 +1,231 @@
+// frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h, its launch ledger, and what the
+// translation units of the shim share (namespace hfdl).  hfdl_gpu.cpp is the pipeline, frontend_create.cpp builds a front end,
+// frontend_query.cpp reads one, stages.cpp holds the one-shot stage entry points, lab.cpp the laboratory build's switches and probes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <deque>
+#include <memory>
+#include <vector>
+#include "../../include/hfdl_gpu.h"
+#include "hip_handles.h"
+#include "kernels.h"
+#include "planner.h"
+#include "demod.h"
+#include "spectrum.h"
+
+namespace hfdl {
+
+int select_device(int device);        // checks the index and the architecture, hipSetDevice
+long env_long(const char *name, long lo, long hi, long otherwise);
+inline int ilog2(int x) { int l = 0; while ((1 << l) < x) l++; return l; }
+inline size_t sample_bytes(int fmt) { return fmt == SFMT_CS16 ? 4 : fmt == SFMT_CU8 ? 2 : 8; }
+bool is_library_pinned(const void *p, size_t bytes);     // inside a range handed out by hfdl_gpu_host_alloc()
+
+// The A/B switches of the measurement scripts, read by ONE function (lab.cpp).  They exist in the laboratory build only (-DHFDL_LAB,
+// libhfdl_gpu_lab.so): the product build returns these defaults and carries neither a getenv nor a knob's name for them.
+struct LabConfig {
+	int fold_tile = -1;            // HFDL_GPU_FOLD_TILE: index of the fold tiling to use instead of the first that fits
+	int fold_slices = 0;           // HFDL_GPU_FOLD_SLICES (BatchOverrides::fold_slices)
+	int cu_split = 0;              // HFDL_GPU_CU_SPLIT = k (2 .. 8): the demodulator's stream on every k-th CU, the channelizer's on the others
+	bool fft_stream = false;       // HFDL_GPU_FFT_STREAM: forward FFTs on a stream of their own
+	bool decode_stream = true;     // HFDL_GPU_DECODE_STREAM: the burst decoders on a stream of their own
+	int fold_bound = -1;           // HFDL_GPU_FOLD_BOUND 0 / 1: instead of "128 channels and more"
+	bool fold_ramp = true;         // HFDL_GPU_FOLD_RAMP=0: every half the full size from the start
+};
+LabConfig read_lab_config();
+
+struct HostFftPlan {
+	FftPlan p{};
+	DevBuf tw[3];
+	int build(int n);
+};
+int upload_twiddles(int r, DevBuf &out);
+
+// ---------------------------------------------------------------- launch timing
+
+// What the next stream waits for.  A launch site owns one fixed event; a TIMED launch carries a pooled start / stop pair on its dispatch
+// (one dispatch carries one start and one stop), so its stop event doubles as its done event.  event() is what the newest launch
+// signalled.  settle(), once everything queued is complete, puts the fixed event back in the pooled one's place before the pool hands
+// that one out again: a completed event stands for "done" as well as any other.
+struct DoneEvent {
+	Event own;
+	hipEvent_t cur = nullptr;
+	hipEvent_t signal() { return cur = own; }                     // an untimed launch: its dispatch signals the fixed event
+	hipEvent_t event() const { return cur ? cur : own.e; }
+	bool pending() const { return cur != nullptr; }               // a launch has signalled it: there is something to wait for (not before the first launch)
+	void settle() { if (cur) cur = own; }
+};
+
+// The timed kernel launches of a front end (hfdl_gpu_frontend_reset_timers), by stage in the order of hfdl_gpu_frontend_stage_times().
+// A timed launch carries a start / stop event pair on its own dispatch (hipExtLaunchKernelGGL): no extra packet in the queue.  The
+// pairs come from a pool filled outside any timed region and are read back and returned to it by the next drain (a sync / poll).
+enum Stage { ST_FFT, ST_FOLD, ST_IFFT, ST_DEMOD, ST_DECODE, ST_N };
+static_assert(ST_N == 5, "hfdl_gpu_frontend_stage_times() reports five stages");
+struct LaunchTimers {
+	struct Timed { Event start, stop; int blocks; };
+	struct Totals { double ms = 0; int64_t launches = 0, blocks = 0; std::vector<Timed> pending; };     // read so far; launched, not yet read
+	bool on = false;
+	Totals stage[ST_N];
+	std::vector<Timed> pool;            // free pairs, made by reset() outside any timed region
+	int64_t fold_shapes[FOLD_MAX_BLOCKS + 1] = {};   // fold launches by block count
+	double fold_shape_ms[FOLD_MAX_BLOCKS + 1] = {};  // ... and their kernel time
+	Event first_fold;                   // start of the first timed fold since the reset: anchor of the steady-state step period
+	double span_ms = 0;                 // first timed fold start -> last timed fold start
+	int64_t fold_last_blocks = 0;       // blocks of the last timed fold
+
+	// timing on: a pair from the pool (made here when a long run without a drain has used it up -- a timed launch is never silently
+	// untimed) into `start` / `stop`.  Timing off: both are left as they are.
+	int arm(Stage s, int blocks, hipEvent_t &start, hipEvent_t &stop);
+	// ... for a launch other streams wait for: the stop event stands in as its done event; timing off, the launch signals `done`'s own
+	int arm(Stage s, int blocks, DoneEvent &done, hipEvent_t &start)
+	{
+		hipEvent_t stop = done.signal();
+		const int rc = arm(s, blocks, start, stop);
+		done.cur = stop;
+		return rc;
+	}
+	int drain();                // every timed launch is complete: add it up, the pairs go back to the pool
+	int reset(bool enable);     // after a drain: every total to zero; timing on fills the pool with enough pairs for the launches between two drains
+};
+
+// ---------------------------------------------------------------- front end
+
+// Spectrum monitor (hfdl_gpu_frontend_spectrum_enable; spectrum.h): off = no monitor, no launch.  One launch per step behind the forward
+// FFT's last pass; `ev` rides on that dispatch, so a read waits for the newest launch without a packet of its own on the stream.
+struct SpectrumMonitor {
+	int bins = 0;
+	uint32_t flags = 0;
+	DevBuf acc;                         // [nrx][bins] float2 { sum, compensation } of the band powers
+	DevBuf peak;                        // [nrx][bins] float with MAXHOLD
+	PinnedBuf<float> host;              // bounce buffer of a read: [bins] float2 + [bins] float
+	Event ev;
+	uint64_t fresh = 0;                 // receivers whose accumulators the next launch overwrites (after enable / a read with reset)
+	std::vector<uint64_t> blocks, first;        // [nrx] blocks accumulated since the receiver's last reset, index of the first of them
+};
+
+}  // namespace hfdl
+
+// Members are destroyed in reverse order of declaration: events first, then memory, then the streams (the destructor has synchronised
+// them).  So: streams, then memory, then events.
+struct hfdl_gpu_frontend {
+	int device = 0;
+	hfdl::Stream stream;                // A: forward FFTs of the half being filled, then ONE fold and ONE inverse FFT / NCO launch per half
+	hfdl::Stream stream_b;              // B: demodulator launches of half k-1, beside the forward FFTs and the fold of half k
+	hfdl::Stream stream_d;              // D: burst decoders + PDU snapshots, off the demodulators' critical path (an alias of B only in a laboratory A/B run)
+	hfdl::Stream stream_c;              // C: host -> device copies into the staging ring, up to n_stage - 1 blocks ahead of the blocks that compute
+	hfdl::Stream stream_f;              // F: forward FFTs of the half being filled, beside the fold of the half before (an alias of A unless HFDL_GPU_FFT_STREAM=1)
+	bool own_decode_stream() const { return stream_d.owned; }
+	bool fft_own_stream() const { return stream_f.owned; }
+	static constexpr int MAX_HALF = hfdl::FOLD_MAX_BLOCKS;      // blocks per half at most: what one fold launch can take (32)
+	static constexpr int MAX_STAGE = HFDL_GPU_PREFETCH_MAX + 1;      // staging buffers for host input at most: uploads run at most 17 blocks ahead
+	static_assert(MAX_HALF == hfdl::PLAN_MAX_HALF && MAX_STAGE == hfdl::PLAN_MAX_STAGE && HFDL_GPU_FOLD_BATCH_MAX == MAX_HALF, "include/hfdl_gpu.h, kernels.h and planner.h name the same limits");
+
+	// ---- memory.  `mem` owns every buffer allocated at create; the typed pointers below are views into it.
+	std::deque<hfdl::DevBuf> mem;
+	template <typename T> hipError_t alloc(T *&view, size_t count)
+	{
+		mem.emplace_back();
+		const hipError_t e = mem.back().alloc(sizeof(T) * count);
+		view = mem.back().as<T>();
+		return e;
+	}
+	hfdl::HostFftPlan fft;
+	hfdl::Demod demod;
+	int4 *d_rx = nullptr, *d_grp = nullptr;      // device copies: receiver table, fold group tables (kernels.h Geometry::grp_tab)
+	float2 *d_hist[2] = { nullptr, nullptr }, *d_work = nullptr, *d_spec = nullptr, *d_taps = nullptr, *d_partial = nullptr;
+	float2 *d_tw_m = nullptr;
+	// Host input goes through a RING of n_stage = min(half_blocks + 2, MAX_STAGE) staging buffers in HBM: host block j is copied (stream
+	// C) into buffer j % n_stage, which the forward FFT's first pass of block j - n_stage has finished reading -- that pass runs BEFORE the
+	// fold of its half, so uploads run up to n_stage - 1 blocks ahead (a whole half of up to 16 blocks, 17 blocks of a 32-block half) and
+	// never sit behind the fold (with two buffers, upload k+2 waited for FFT k, which waited for the fold of the half before: the link
+	// idled a third of the time).
+	int n_stage = 0;
+	std::unique_ptr<hfdl::DevBuf> d_stage[MAX_STAGE];     // allocated (and grown) by the first copy that needs it
+	size_t stage_cap[MAX_STAGE] = {};
+	// Channelizer output, double-buffered between stream A and stream B in two HALVES of `half_blocks` blocks each:
+	// [2][half_blocks][nch][outs].  The forward FFT of a block is queued when it is pushed; the fold and the inverse FFTs run when a
+	// half is closed (full, or a sync / poll found it part-filled): ONE pass over the filter taps serves up to `fold_nb` blocks.
+	// The demodulator then takes the half `batch` blocks per launch while the channelizer fills the other half.
+	float2 *d_chan_all = nullptr;
+	int *d_cnt_all = nullptr;           // [2][half_blocks][nch] outputs per channel of each block
+	hfdl::ChanConst *d_cc = nullptr;
+	int2 *d_win = nullptr;              // pruned fold: window of quads of alias rows per octet (kernels.h Geometry::fold_win)
+	hfdl::NcoState *d_nco = nullptr;    // [nch] carried NCO state, owned by the forward FFT's rider workgroups (kernels.h NcoJob)
+	hfdl::NcoState *d_nco_snap = nullptr;     // [half_blocks][nch] the state each block of the half starts from
+	float2 *d_ph = nullptr, *d_ph_cont = nullptr;      // [half_blocks] NCO phasor tables [outs][nch] and the riders' segment hand-over [nch]
+	std::unique_ptr<hfdl::SpectrumMonitor> mon;        // null: off
+
+	// ---- events
+	// demodulator launch j of the half in buffer 0 / 1 done (the decoder may start), the LAST launch of the half at [0]: chan_out is free
+	hfdl::DoneEvent dm[2][MAX_HALF];
+	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)
+	hfdl::DoneEvent fft_done;           // the last forward FFT of a half on stream A: what the held-back demodulators wait for
+	hfdl::DoneEvent spec[2];            // newest forward FFT of the half in spectrum set 0 / 1 done (rides on its last pass; stream F only, never timed)
+	hfdl::Event ev_demod[2];            // recorded behind the last burst decoder of the half
+	hfdl::Event ev_stage_ready[MAX_STAGE];      // copy of the host block in this buffer done: what its forward FFT and input_done_upto() wait for
+	hfdl::Event ev_stage_free[MAX_STAGE];       // pass 1 of the forward FFT that read this buffer done (rides on that dispatch): the copy stream may refill it
+	hfdl::LaunchTimers timers;
+	int settle_events();                // after a sync: read the timed launches back, every DoneEvent settles
+
+	// ---- plain state
+	uint64_t host_blocks = 0;           // host blocks whose copy has been queued (pushed or prefetched)
+	uint64_t host_pushed = 0;           // ... of which this many have been pushed (or cancelled): the rest wait in the prefetch queue, oldest first
+	const void *pf_ptr[MAX_STAGE] = {}; // prefetch queue entry of host block j at [j % n_stage]: the host pointer ...
+	int pf_fmt[MAX_STAGE] = {};         // ... and its sample format
+	// The copy of host block j signals ev_stage_ready[j % n_stage].  Copies run in order on one stream, so for a block more than
+	// n_stage - 1 behind the newest (its event has been re-recorded since) the oldest event still its own block's implies it.
+	hipEvent_t input_event(uint64_t host_block) const
+	{
+		const uint64_t newest = host_blocks - 1, span = (uint64_t)n_stage - 1;
+		return ev_stage_ready[(newest - host_block <= span ? host_block : newest - span) % (uint64_t)n_stage];
+	}
+	int32_t sample_rate = 0, decimation = 0;
+	float tbw = 0;
+	hfdl::Plan plan{};                  // shift = 0 geometry (src/fft.c:70-86)
+	hfdl::Geometry geo{};
+	std::vector<int32_t> freqs;
+	// Receivers (hfdl_gpu_frontend_create_multi): one stream of input_size samples per receiver and step, channels receiver-major.  Every
+	// per-block buffer of the forward FFT holds one transform per receiver: overlap history [2][nrx][overlap], work [nrx][N], spectra
+	// [set][block][nrx][N], staging buffers [nrx][input_size]; from the fold on, everything is per channel as with one receiver.
+	int nrx = 1;
+	std::vector<int32_t> rx_center;     // [nrx] centre frequencies
+	std::vector<int32_t> rx_of;         // [nch] receiver of each channel
+	std::vector<hfdl::RxSpan> rx_span;  // [nrx] padded tap slots and channels of each receiver (planner.h plan_receiver_slots)
+	std::vector<int4> rx_host;          // the same as the kernels read it (Geometry::rx_tab / rx_host)
+	int slot_of(int c) const { return hfdl::receiver_slot(rx_span[(size_t)rx_of[(size_t)c]], c); }
+	std::vector<hfdl::ChanConst> cc;
+	int batch = 1;                      // blocks per demodulator launch
+	int fold_nb = 1;                    // blocks per fold launch
+	int half_blocks = 1;                // slots per half: a multiple of fold_nb, at least `batch` (planner.h plan_batches)
+	// How many blocks close the half being filled.  A pipeline that starts empty closes its first half at `half_first` blocks (16 where a
+	// half holds 32): the first fold launch is the sixteen-column form and the demodulators start 3 ms earlier; once a half has been
+	// closed BY FILLING -- the caller pushes faster than it collects -- the next ones take all `half_blocks`.  Any sync / poll that closes
+	// a half early (a drain) starts over.  Results do not depend on where the halves are cut (test_fold_batching_changes_nothing).
+	int half_first = 1, half_target = 1;
+	int cur_half = 0, batch_fill = 0;   // the half being filled and the blocks already in it (forward FFT queued, fold not yet)
+	int last_slot = 0;                  // slot (half * half_blocks + index) of the newest channelized block: what HFDL_GPU_TAP_CHAN_OUT reads
+	int last_index = 0;                 // its index inside the half: spectrum / phasor-table slot of the newest block
+	float2 *chan_slot(int slot) const { return d_chan_all + (size_t)slot * (size_t)geo.nch * (size_t)geo.outs; }
+	int *cnt_slot(int slot) const { return d_cnt_all + (size_t)slot * (size_t)geo.nch; }
+	// spectra, NCO phasor tables and carried-state snapshots of a half: two sets (the forward FFTs of half k+1 fill one while the fold
+	// and inverse FFTs of half k read the other); `set` = cur_half of the half they belong to
+	int last_set = 0;                   // set of the newest channelized half: what the taps read
+	float2 *spec_slot(int set, int i) const { return d_spec + ((size_t)set * (size_t)half_blocks + (size_t)i) * spec_stride(); }
+	size_t spec_stride() const { return (size_t)nrx * (size_t)geo.n; }     // between the spectra of consecutive blocks (receiver r at + r N)
+	float2 *ph_slot(int set, int i) const { return d_ph + ((size_t)set * (size_t)half_blocks + (size_t)i) * ph_stride(); }
+	hfdl::NcoState *snap_slot(int set, int i) const { return d_nco_snap + ((size_t)set * (size_t)half_blocks + (size_t)i) * (size_t)geo.nch; }
+	size_t partial_stride() const { return (size_t)geo.nch * (size_t)geo.slices * (size_t)geo.m; }
+	size_t ph_stride() const { return (size_t)geo.nch * (size_t)geo.outs; }
+	double prune_tol = 0.0;             // HFDL_GPU_FOLD_PRUNE: share of a filter's energy (as an amplitude ratio) the skipped alias rows may hold; 0 = fold every row
+	int fold_rows_max = 0;              // the longest row window (0: every row is folded)
+	bool fold_bound = false;            // many channels: the fold bounds the block and the demodulator launches of a half are placed under the NEXT half's fold
+	uint64_t blocks = 0;
+	hfdl::FftOutLayout tap_layout;
+	int pending_demod_buf = -1;         // half whose demodulator launches are held back until the next half's forward FFTs are queued ...
+	int pending_demod_nblk = 0;         // ... and the blocks in it
+	bool frames_wait_on_a = false;      // stream A has waited for the frame queue the next demodulator launch reuses
+	int demod_buf = -1;                 // half / snapshot slot of the newest demodulator launch
+	int prev_demod_buf = -1;            // ... and of the one before it
+
+	~hfdl_gpu_frontend();
+};

@@ -1,0 +1,358 @@
+// frontend_create.cpp -- builds and destroys a front end: argument checks, geometry, streams and events, allocation, the filter taps.
+#include <atomic>
+#include <cmath>
+#include <complex>
+#include <cstring>
+#include <thread>
+#include "frontend.h"
+
+using namespace hfdl;
+
+extern "C" int hfdl_gpu_device_count(void)
+{
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+	return n;
+}
+
+int hfdl::select_device(int device)
+{
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+		return fail(HFDL_GPU_ENODEV, "no HIP device visible: the HFDL front end has no CPU fallback");
+	if (device < 0 || device >= n) return fail(HFDL_GPU_EINVAL, "device %d out of range (%d visible)", device, n);
+	HIP_TRY(hipSetDevice(device));
+	hipDeviceProp_t prop;
+	HIP_TRY(hipGetDeviceProperties(&prop, device));
+	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+		return fail(HFDL_GPU_ENODEV, "device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
+	return 0;
+}
+
+// ---------------------------------------------------------------- FFT plan
+
+int hfdl::upload_twiddles(int r, DevBuf &out)
+{
+	std::vector<float2> h((size_t)r);
+	for (int t = 0; t < r; t++) {
+		double a = -2.0 * M_PI * (double)t / (double)r;
+		h[t] = make_float2((float)std::cos(a), (float)std::sin(a));
+	}
+	HIP_TRY(out.alloc(sizeof(float2) * (size_t)r));
+	HIP_TRY(hipMemcpy(out.p, h.data(), sizeof(float2) * (size_t)r, hipMemcpyHostToDevice));
+	return 0;
+}
+
+int HostFftPlan::build(int n)
+{
+	int logn = ilog2(n);
+	if ((1 << logn) != n || logn < 9 || logn > 24) return fail(HFDL_GPU_ERANGE, "fft size %d unsupported (need 2^9..2^24)", n);
+	// balanced split, largest radix last-but-one; every radix <= 256 so a 16-column tile fits 32 KiB of LDS
+	int l1 = (logn + 2) / 3, l2 = (logn - l1 + 1) / 2, l3 = logn - l1 - l2;
+	p.n = n; p.logn = logn;
+	p.l1 = l1; p.l2 = l2; p.l3 = l3;
+	p.r1 = 1 << l1; p.r2 = 1 << l2; p.r3 = 1 << l3;
+	const int radix[3] = { p.r1, p.r2, p.r3 };
+	for (int i = 0; i < 3; i++) if (int rc = upload_twiddles(radix[i], tw[i])) return rc;
+	p.tw1 = tw[0].as<float2>(); p.tw2 = tw[1].as<float2>(); p.tw3 = tw[2].as<float2>();
+	return 0;
+}
+
+// ---------------------------------------------------------------- create-time configuration
+
+// From the environment (include/hfdl_gpu.h documents every name).  Read at every create and never cached: there is no function-local
+// static to race on when front ends are created from several threads.
+long hfdl::env_long(const char *name, long lo, long hi, long otherwise)
+{
+	const char *e = getenv(name);
+	if (!e || !*e) return otherwise;
+	char *end = nullptr;
+	const long v = strtol(e, &end, 10);
+	return (end != e && v >= lo && v <= hi) ? v : otherwise;
+}
+
+static double env_double(const char *name, double lo, double hi, double otherwise)
+{
+	const char *e = getenv(name);
+	if (!e || !*e) return otherwise;
+	char *end = nullptr;
+	const double v = strtod(e, &end);
+	return (end != e && v >= lo && v <= hi) ? v : otherwise;
+}
+
+// The pruned fold: the energy of the taps per (alias row, slot) from the device, the windows from planner.h fold_row_windows
+static int build_fold_windows(hfdl_gpu_frontend *fe)
+{
+	Geometry &g = fe->geo;
+	DevBuf d_en;
+	std::vector<float> en((size_t)g.pre * (size_t)g.nch_pad);
+	HIP_TRY(d_en.alloc(sizeof(float) * en.size()));
+	HIP_TRY(hipMemsetAsync(d_en.p, 0, sizeof(float) * en.size(), fe->stream));
+	launch_tap_row_energy(fe->d_taps, g, d_en.as<float>(), fe->stream);
+	HIP_TRY(hipMemcpyAsync(en.data(), d_en.p, sizeof(float) * en.size(), hipMemcpyDeviceToHost, fe->stream));
+	HIP_TRY(hipStreamSynchronize(fe->stream));
+	const std::vector<RowWindow> w = fold_row_windows(en, g.pre, g.nch_pad, g.nch, fe->prune_tol, &fe->fold_rows_max);
+	static_assert(sizeof(RowWindow) == sizeof(int2), "a window is what the fold kernels load as an int2 { first quad, count }");
+	HIP_TRY(fe->alloc(fe->d_win, w.size()));
+	HIP_TRY(hipMemcpy(fe->d_win, w.data(), sizeof(int2) * w.size(), hipMemcpyHostToDevice));
+	g.fold_win = fe->d_win;
+	return 0;
+}
+
+static int build_taps(hfdl_gpu_frontend *fe)
+{
+	const Plan &pl = fe->plan;
+	const int nch = (int)fe->freqs.size();
+	const size_t n = (size_t)pl.n;
+	// time-domain taps on the host (exact reference arithmetic), one worker per hardware thread
+	std::vector<std::complex<float>> host((size_t)nch * (size_t)pl.taps_length);
+	fe->cc.resize((size_t)nch);
+	unsigned nthreads = std::max(1u, std::min((unsigned)nch, std::thread::hardware_concurrency()));
+	// several front ends created at once on one host (one process per GPU): share the cores
+	nthreads = std::min(nthreads, (unsigned)env_long("HFDL_GPU_HOST_THREADS", 1, 1 << 16, (long)nthreads));
+	std::atomic<int> next{0};
+	std::atomic<int> bad{0};
+	auto work = [&]() {
+		std::vector<float> lp;
+		float lp_cut = -1.f;
+		for (;;) {
+			int c = next.fetch_add(1);
+			if (c >= nch) break;
+			// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency -- from the centre of ITS receiver
+			float shift = (float)(fe->rx_center[(size_t)fe->rx_of[(size_t)c]] - (fe->freqs[c] + 1440)) / (float)fe->sample_rate;
+			Plan cp;
+			if (!plan_block(cp, fe->tbw, fe->decimation, shift)) { bad++; continue; }
+			ChanConst k{};
+			k.offsetbin = cp.offsetbin;
+			k.nco_sindelta = cp.sindelta; k.nco_cosdelta = cp.cosdelta; k.nco_rate = cp.rate;
+			k.frequency = fe->freqs[c];
+			fe->cc[c] = k;
+			float half_bw = 0.5f / fe->decimation;
+			design_bandpass(host.data() + (size_t)c * pl.taps_length, pl.taps_length, (-shift) - half_bw, (-shift) + half_bw, lp, lp_cut);
+		}
+	};
+	std::vector<std::thread> pool;
+	for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work);
+	work();
+	for (auto &t : pool) t.join();
+	if (bad) return fail(HFDL_GPU_EINVAL, "fastddc planning failed for %d channel(s)", (int)bad);
+
+	// frequency-domain taps on the device: zero-pad to N, forward FFT, fftshift (src/fastddc.c:231-240)
+	DevBuf pad;
+	HIP_TRY(pad.alloc(sizeof(float2) * n));
+	float2 *d_pad = pad.as<float2>();
+	HIP_TRY(hipMemsetAsync(d_pad, 0, sizeof(float2) * n, fe->stream));
+	if (fe->geo.nch_pad > nch)          // the slots that fill each receiver's last group of the interleaved layout up: all-zero taps
+		HIP_TRY(hipMemsetAsync(fe->d_taps, 0, sizeof(float2) * n * (size_t)fe->geo.nch_pad, fe->stream));
+	for (int c = 0; c < nch; c++) {
+		HIP_TRY(hipMemcpyAsync(d_pad, host.data() + (size_t)c * pl.taps_length, sizeof(float2) * (size_t)pl.taps_length,
+				hipMemcpyHostToDevice, fe->stream));
+		// the last pass writes the channel's filter straight into the matrix-operand layout (kernels.h tap_index_f), at its padded slot
+		const int slot = fe->slot_of(c);
+		FftOutLayout lay = fe->tap_layout;
+		lay.chan = slot;
+		float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
+		launch_fft_forward(fe->fft.p, nullptr, d_pad, SFMT_CF32, 0, nullptr, fe->d_work, dst, true, fe->stream, lay);
+	}
+	HIP_TRY(hipStreamSynchronize(fe->stream));
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// Every argument is checked here, before a device is selected (the checks need no GPU)
+static int check_create_args(hfdl_gpu_frontend **out, int32_t sample_rate, int32_t nrx, const int32_t *centerfreqs, const int32_t *freqs,
+		const int32_t *nch_per_rx)
+{
+	if (!out || !centerfreqs || !freqs || !nch_per_rx) return fail(HFDL_GPU_EINVAL, "bad arguments: null pointer");
+	*out = nullptr;
+	if (nrx < 1 || nrx > HFDL_GPU_RECEIVERS_MAX) return fail(HFDL_GPU_EINVAL, "bad arguments: %d receivers (1 .. %d)", nrx, HFDL_GPU_RECEIVERS_MAX);
+	for (int r = 0; r < nrx; r++)
+		if (nch_per_rx[r] <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments: receiver %d has %d channels", r, nch_per_rx[r]);
+	if (sample_rate < 5400) return fail(HFDL_GPU_EINVAL, "sample rate must be >= 5400 (src/main.c:638-641)");
+	for (int r = 0, c = 0; r < nrx; r++)
+		for (int i = 0; i < nch_per_rx[r]; i++, c++)
+			// span check of src/main.c:214-226, against the channel's own receiver
+			if (std::abs((int64_t)centerfreqs[r] - freqs[c]) >= sample_rate / 2)
+				return nrx == 1 ? fail(HFDL_GPU_EINVAL, "channel %d Hz outside +-fs/2 of centre %d", freqs[c], centerfreqs[r])
+				                : fail(HFDL_GPU_EINVAL, "channel %d (%d Hz) outside +-fs/2 of the centre %d of its receiver %d", c, freqs[c], centerfreqs[r], r);
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t centerfreq,
+		const int32_t *freqs, int32_t nch)
+{
+	if (!out || !freqs || nch <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
+	return hfdl_gpu_frontend_create_multi(out, device, sample_rate, 1, &centerfreq, freqs, &nch);
+}
+
+// The streams.  Measured on MI355X: stream priority (hi/lo) and CU-masking of stream A change nothing beyond run-to-run noise
+// (profiles/r01_experiments.md), so plain non-blocking streams are used.
+static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
+{
+	if (lab.cu_split) {
+		// Laboratory A/B: does a demodulator launch still execute twice the cycles while a fold runs, when no fold wave shares its SIMD?
+		// CU i belongs to the demodulator iff ((i >> 3) + i) % k == 0: an equal share of every XCD whether the mask counts XCD-major or
+		// XCD-interleaved.
+		uint32_t mask_a[8] = {}, mask_b[8] = {};
+		for (int i = 0; i < 256; i++)
+			((((i >> 3) + i) % lab.cu_split) == 0 ? mask_b : mask_a)[i >> 5] |= 1u << (i & 31);
+		CREATE_TRY(fe->stream.create_on_cus(mask_a));
+		CREATE_TRY(fe->stream_b.create_on_cus(mask_b));
+	} else {
+		CREATE_TRY(fe->stream.create());
+		CREATE_TRY(fe->stream_b.create());
+	}
+	CREATE_TRY(fe->stream_c.create());
+	// Forward FFTs of the half being filled on a stream of their own, beside the fold of the half before (two sets of spectra / phasor
+	// tables / state snapshots): measured on cfg3 in round 4 (profiles/r04_experiments.md) the passes then take their HBM share out of
+	// the fold and the demodulators and the step gets slower, so the FFTs stay in front of the fold on stream A.  The switch lives in the
+	// laboratory build.  (More than four busy streams also need GPU_MAX_HW_QUEUES > 4: two streams on one hardware queue run in turn.)
+	if (lab.fft_stream) CREATE_TRY(fe->stream_f.create());
+	else fe->stream_f.alias(fe->stream);
+	// The burst decoder of launch k only hands PDUs to the host; the demodulator of launch k+1 does not need it, and a long frame
+	// ending in a block puts 0.3 - 1.2 ms of Viterbi in front of it: the decoder has its own stream (cfg2: +25 % in round 2; at 256
+	// channels the round-4 timeline shows a 1.18 ms decoder launch serially ahead of a half's first demodulator).
+	if (lab.decode_stream) CREATE_TRY(fe->stream_d.create());
+	else fe->stream_d.alias(fe->stream_b);
+	fe->demod.separate_decode = fe->own_decode_stream();
+	return 0;
+}
+
+static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nch_per_rx)
+{
+	const int nch = (int)fe->freqs.size();
+	const LabConfig lab = read_lab_config();
+	if (!plan_block(fe->plan, fe->tbw, fe->decimation, 0.f)) return fail(HFDL_GPU_EINVAL, "fastddc planning failed");
+	const Plan &pl = fe->plan;
+	Geometry &g = fe->geo;
+	g.n = pl.n; g.m = pl.m; g.pre = pl.pre; g.post = pl.post; g.scrap = pl.scrap; g.post_input_size = pl.post_input_size;
+	g.overlap = pl.overlap; g.input_size = pl.input_size; g.outs = (pl.post_input_size + pl.post - 1) / pl.post + 1;
+	g.nch = nch;
+	// Filter taps row-major over channels: alias row r of every channel sits in one nch*M run, so the workgroups of all
+	// channels, which walk the rows together, stream through a few moving windows of HBM instead of nch windows 8N bytes
+	// apart (fold kernel 2.58 -> 2.48 ms on cfg3 and a tighter run-to-run spread, profiles/r01_experiments.md)
+	g.tap_layout = (pl.m % 16) == 0 && (pl.pre % 8) == 0 ? TAPL_OCTET : TAPL_PLAIN;       // the matrix-pipe fold walks the alias rows four at a time, two such quads in flight
+	// each receiver's channels padded to whole groups of the layout on their own (one receiver: nch rounded up, as always)
+	g.nch_pad = plan_receiver_slots(nch_per_rx, nrx, tap_layout_group(g.tap_layout), fe->rx_span);
+	for (const RxSpan &r : fe->rx_span) fe->rx_host.push_back(make_int4(r.slot0, r.slots, r.chan0, r.nch));
+	g.nrx = nrx;
+	g.spec_rx_stride = pl.n;
+	g.rx_host = fe->rx_host.data();
+	g.tap_chan_stride = pl.m; g.tap_row_stride = (int64_t)g.nch_pad * pl.m;
+	g.fold_tile = lab.fold_tile;
+	fe->tap_layout.kind = g.tap_layout;
+	fe->tap_layout.row_log = ilog2(pl.m); fe->tap_layout.row_stride = g.tap_row_stride;
+	// HFDL_GPU_FOLD_PRUNE=tol (0 < tol <= 1e-3; unset: every alias row is folded, the reference's sum term for term): fold only the
+	// rows around each channel's pass band (build_fold_windows) -- one slice, the windows are the parallelism
+	// (the pruned fold's windows are per octet of ONE receiver's taps: off with several receivers)
+	fe->prune_tol = g.tap_layout == TAPL_OCTET && nrx == 1 ? env_double("HFDL_GPU_FOLD_PRUNE", 1e-12, 1e-3, 0.0) : 0.0;
+	// fold_bound: with many channels the fold bounds the block; the demodulator launches of a half are then held back until the next
+	// half's forward FFTs are queued (launch_demod) instead of starting at once.
+	fe->fold_bound = lab.fold_bound < 0 ? nch >= 128 : lab.fold_bound != 0;
+	const float resamp_rate = (float)(1800 * 3) / ((float)fe->sample_rate / (float)fe->decimation);
+	BatchOverrides ov;
+	ov.demod_batch = (int)env_long("HFDL_GPU_DEMOD_BATCH", 1, 8, 0);
+	ov.fold_batch = (int)env_long("HFDL_GPU_FOLD_BATCH", 1, hfdl_gpu_frontend::MAX_HALF, 0);
+	ov.pruned = fe->prune_tol > 0;
+	ov.fold_slices = lab.fold_slices;
+	ov.no_ramp = !lab.fold_ramp;
+	const BatchPlan bp = plan_batches(nch, nrx, pl.n, pl.input_size, fe->sample_rate, pl.pre, fe->fold_bound,
+			[&](int want) { return Demod::fit_batch(g.outs, resamp_rate, want); }, ov);
+	g.slices = bp.slices;
+	g.rows_per_slice = pl.pre / g.slices;
+	if (pl.m > 8192 || pl.m < 16) return fail(HFDL_GPU_ERANGE, "inverse FFT size %d unsupported", pl.m);
+
+	if (int rc = create_streams(fe, lab)) return rc;
+	for (int i = 0; i < 2; i++) {
+		CREATE_TRY(fe->spec[i].own.create(EV_NO_TIMING));
+		CREATE_TRY(fe->chan[i].own.create(EV_NO_TIMING));
+		CREATE_TRY(fe->ev_demod[i].create(EV_NO_TIMING));
+		for (DoneEvent &d : fe->dm[i]) CREATE_TRY(d.own.create(EV_NO_TIMING));
+	}
+	CREATE_TRY(fe->fft_done.own.create(EV_NO_TIMING));
+	if (int rc = fe->fft.build(pl.n)) return rc;
+	const size_t n = (size_t)pl.n;
+	const size_t K = (size_t)nrx;
+	for (int i = 0; i < 2; i++) {      // overlap history, ping-pong: block k reads [k&1] and leaves the next one in [(k+1)&1]; one per receiver
+		CREATE_TRY(fe->alloc(fe->d_hist[i], (size_t)pl.overlap * K));
+		CREATE_TRY(hipMemsetAsync(fe->d_hist[i], 0, sizeof(float2) * (size_t)pl.overlap * K, fe->stream));   // calloc'ed history, src/fft.c:79
+	}
+	CREATE_TRY(fe->alloc(fe->d_work, n * K));
+	CREATE_TRY(fe->alloc(fe->d_rx, K));
+	CREATE_TRY(hipMemcpy(fe->d_rx, fe->rx_host.data(), sizeof(int4) * K, hipMemcpyHostToDevice));
+	g.rx_tab = fe->d_rx;
+	if (g.tap_layout == TAPL_OCTET) {
+		static_assert(sizeof(FoldGroup) == sizeof(int4), "a FoldGroup entry is what the fold kernels load as an int4");
+		const std::vector<FoldGroup> t = fold_group_tables(fe->rx_span, g.nch_pad / 8, FOLD_GROUP_MAX);
+		CREATE_TRY(fe->alloc(fe->d_grp, t.size()));
+		CREATE_TRY(hipMemcpy(fe->d_grp, t.data(), sizeof(int4) * t.size(), hipMemcpyHostToDevice));
+		g.grp_tab = fe->d_grp;
+	}
+	CREATE_TRY(fe->alloc(fe->d_taps, n * (size_t)g.nch_pad));
+	CREATE_TRY(fe->alloc(fe->d_nco, (size_t)nch));
+	CREATE_TRY(hipMemsetAsync(fe->d_nco, 0, sizeof(NcoState) * (size_t)nch, fe->stream));
+	CREATE_TRY(fe->alloc(fe->d_ph_cont, (size_t)nch));
+	CREATE_TRY(fe->alloc(fe->d_cc, (size_t)nch));
+	fe->mem.emplace_back();
+	if (int rc = upload_twiddles(pl.m, fe->mem.back())) return rc;
+	fe->d_tw_m = fe->mem.back().as<float2>();
+	if (prepare_ifft_nco(pl.m) != hipSuccess)
+		return fail(HFDL_GPU_EHIP, "inverse FFT of %d points: LDS attribute refused: %s", pl.m, hipGetErrorString(hipGetLastError()));
+	if (int rc = build_taps(fe)) return rc;
+	if (fe->prune_tol > 0 && g.tap_layout == TAPL_OCTET)
+		if (int rc = build_fold_windows(fe)) return rc;
+	CREATE_TRY(hipMemcpy(fe->d_cc, fe->cc.data(), sizeof(ChanConst) * (size_t)nch, hipMemcpyHostToDevice));
+	fe->fold_nb = bp.fold_nb;
+	if (int rc = fe->demod.init(nch, g.outs, resamp_rate, fe->freqs.data(), fe->stream, bp.batch_want)) return rc;
+	fe->batch = fe->demod.batch;
+	fe->half_blocks = bp.half_blocks;
+	fe->half_first = fe->half_target = bp.half_first;
+	fe->n_stage = bp.n_stage;
+	for (int i = 0; i < fe->n_stage; i++) {
+		CREATE_TRY(fe->ev_stage_ready[i].create(EV_NO_TIMING));
+		CREATE_TRY(fe->ev_stage_free[i].create(EV_NO_TIMING));
+	}
+	const size_t hb = (size_t)fe->half_blocks;
+	CREATE_TRY(fe->alloc(fe->d_spec, fe->spec_stride() * 2 * hb));
+	CREATE_TRY(fe->alloc(fe->d_partial, fe->partial_stride() * hb));
+	CREATE_TRY(fe->alloc(fe->d_ph, fe->ph_stride() * 2 * hb));
+	CREATE_TRY(fe->alloc(fe->d_nco_snap, (size_t)nch * 2 * hb));
+	CREATE_TRY(fe->alloc(fe->d_chan_all, 2 * hb * (size_t)nch * g.outs));
+	CREATE_TRY(fe->alloc(fe->d_cnt_all, 2 * hb * (size_t)nch));
+	CREATE_TRY(hipMemsetAsync(fe->d_cnt_all, 0, sizeof(int) * 2 * hb * (size_t)nch, fe->stream));
+	CREATE_TRY(hipStreamSynchronize(fe->stream));
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx,
+		const int32_t *centerfreqs, const int32_t *freqs, const int32_t *nch_per_rx)
+{
+	int rc = check_create_args(out, sample_rate, nrx, centerfreqs, freqs, nch_per_rx);
+	if (rc || (rc = select_device(device))) return rc;
+	int32_t nch = 0;
+	for (int r = 0; r < nrx; r++) nch += nch_per_rx[r];
+	auto fe = std::make_unique<hfdl_gpu_frontend>();
+	fe->device = device;
+	fe->sample_rate = sample_rate;
+	fe->decimation = fft_decimation_rate(sample_rate, 1800 * 3);
+	fe->tbw = relative_transition_bw(sample_rate, 250);
+	fe->freqs.assign(freqs, freqs + nch);
+	fe->nrx = nrx;
+	fe->rx_center.assign(centerfreqs, centerfreqs + nrx);
+	for (int r = 0; r < nrx; r++) fe->rx_of.insert(fe->rx_of.end(), (size_t)nch_per_rx[r], r);
+	if ((rc = create_frontend(fe.get(), nrx, nch_per_rx))) return rc;       // (the destructor releases what a failed create got as far as)
+	*out = fe.release();
+	return 0;
+}
+
+// The order, explicitly: every owned stream and the monitor's event are synchronised; then the members go in reverse order of
+// declaration -- events, memory, streams (frontend.h)
+hfdl_gpu_frontend::~hfdl_gpu_frontend()
+{
+	(void)hipSetDevice(device);
+	for (const hfdl::Stream *s : { &stream, &stream_b, &stream_d, &stream_c, &stream_f }) (void)s->sync();
+	if (mon) (void)hipEventSynchronize(mon->ev);
+	demod.release();
+}
+
+extern "C" void hfdl_gpu_frontend_destroy(hfdl_gpu_frontend *fe) { delete fe; }

@@ -1,0 +1,7 @@
+# The objects of libhfdl_gpu.so, in ONE place: build.sh compiles and links them, build_strict.sh links the same list with its own
+# demodulator object.  Kernel objects come from <name>.hip, the shim's from <name>.cpp.
+KERNEL_OBJS="fft_kernels fold_kernels demod_kernels spectrum_kernels"
+SHIM_OBJS="hfdl_gpu frontend_create frontend_query stages lab"
+# demodulator and spectrum monitor: no FMA contraction, so the fp32 recurrences round exactly like the plain-C oracle's and the
+# monitor's fp32 sums are what tests/spectrum_f64.py emulates term for term
+NO_CONTRACT_OBJS="demod_kernels spectrum_kernels"

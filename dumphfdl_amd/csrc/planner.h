@@ -7,6 +7,7 @@
 //   firdes_lowpass_f / firdes_bandpass_c / Hamming kernel   src/libcsdr.c:62-68,83-133
 //   compute_fft_decimation_rate, compute_filter_relative_transition_bw   src/libcsdr.c:135-144
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -147,6 +148,161 @@ inline std::vector<FoldGroup> fold_group_tables(const std::vector<RxSpan> &rx, i
 			}
 	}
 	return t;
+}
+
+// ---------------------------------------------------------------- create-time batching and slicing rules
+
+// Slices of alias rows per (channel group, bin group): each slice is a workgroup of its own and leaves a partial sum that the inverse
+// FFT adds up.  A CU holds ONE matrix-pipe fold workgroup at a time (one 384 / 420-register wave per SIMD), so every workgroup
+// generation pays its dispatch, its first loads and its stores with an idle matrix pipe: as few and as long-lived workgroups as fill
+// the chip.  256 channels need no slicing (cfg3: 2048 workgroups of 512 quads at one slice; against round 1's rule of
+// channels x slices >= 1024 -- four slices -- the 32-block fold takes 5.7 instead of 6.8 ms alone, 0.203 instead of 0.22 ms per block
+// in the pipeline, and a quarter of the partial sums are written and read back: profiles/r06_experiments.md); fewer channels are
+// sliced until channels x slices >= 256, a slice keeping at least 8 alias rows.
+inline int pick_slices(int nch, int rows)
+{
+	int s = 1;
+	while (s * 2 <= rows / 8 && nch * s < 256) s *= 2;
+	return s;
+}
+
+// What the environment (the shim reads it; include/hfdl_gpu.h documents the names) and the laboratory build ask for; 0 / false = not asked
+struct BatchOverrides {
+	int demod_batch = 0;        // HFDL_GPU_DEMOD_BATCH 1..8: taken as it is
+	int fold_batch = 0;         // HFDL_GPU_FOLD_BATCH 1..32
+	bool pruned = false;        // HFDL_GPU_FOLD_PRUNE: one slice, the row windows are the parallelism
+	int fold_slices = 0;        // laboratory A/B: slices of alias rows per channel and bin (a power of two; a slice keeps at least 16 rows)
+	bool no_ramp = false;       // laboratory A/B: every half the full size from the start
+};
+
+struct BatchPlan {
+	int slices;                 // Geometry::slices
+	int fold_nb;                // blocks per fold launch
+	int batch_want;             // blocks per demodulator launch to ask Demod::init for (what it keeps is demod_fit(batch_want))
+	int half_blocks;            // slots per half: a multiple of fold_nb, at least the demodulator batch
+	int half_first;             // blocks that close the first half after a drain
+	int n_stage;                // staging buffers for host input
+};
+
+constexpr int PLAN_MAX_HALF = 32;       // blocks per half at most: what one fold launch can take (kernels.h FOLD_MAX_BLOCKS)
+constexpr int PLAN_MAX_STAGE = 18;      // staging buffers at most: uploads run at most 17 blocks ahead (HFDL_GPU_PREFETCH_MAX + 1)
+
+// n / input_size / pre: the block geometry (Plan).  fold_bound: the fold bounds the block (128 channels and more).  demod_fit(want):
+// blocks a demodulator launch can take, `want` or fewer (Demod::fit_batch: LDS, 16-bit output counts, < 1 s of signal).
+template <typename Fit>
+inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sample_rate, int pre, bool fold_bound, Fit demod_fit, const BatchOverrides &ov)
+{
+	BatchPlan b{};
+	b.slices = pick_slices(nch, pre);
+	if (ov.fold_slices > 0 && (ov.fold_slices & (ov.fold_slices - 1)) == 0 && pre % ov.fold_slices == 0 && pre / ov.fold_slices >= 16) b.slices = ov.fold_slices;
+	if (ov.pruned) b.slices = 1;
+
+	// Blocks per fold launch.  The filter taps are 99.9 % of a block's bytes on the fold-bound geometries (cfg3: 16 GiB of taps against
+	// a 64 MiB spectrum) and they are the same for every block: when blocks are pushed faster than they are collected (file replay,
+	// catching up, the bench) the spectra of up to `fold_nb` consecutive blocks are folded in ONE pass over the taps on the matrix pipe
+	// (fold_kernels.hip).  Every block's sums are bit-identical to a launch of its own (fixed FMA chain per bin); a caller that polls
+	// or syncs after every block (live input) still gets one launch per block: a sync / poll closes the half as it is.
+	// 32 where the fold bounds the block (128 channels and more): two column groups of the sixteen-column matrix instruction per loaded tap
+	// operand.  A launch costs about its matrix time plus its memory time (fold_kernels.hip, profiles/r06_experiments.md), so a block's share
+	// shrinks with the blocks per byte of taps: 0.20 ms per block at 32 against 0.245 at 16 in the pipeline.  The
+	// first half after a drain closes at 16 (half_first).  Where the demodulator bounds the block (fewer than 128 channels: the taps are a
+	// few hundred MiB and a fold launch takes 0.2 ms whatever it folds) a long half only adds fill, drain and latency: 8, as in round 4
+	// (cfg2: 0.1545 against 0.1595 ms per block over 256 blocks)
+	b.fold_nb = ov.fold_batch ? ov.fold_batch : (fold_bound ? 32 : 8);      // 1 = a pass over the taps per block
+
+	// Blocks per demodulator launch.  Every launch pays fixed costs: the barrier packet in front of it (~11 us), ~25 KiB of tables and
+	// state staged into LDS and written back, and two chunks of pipeline fill and drain -- ~40 us against ~210 us of recurrence per
+	// cfg2 block.  When blocks arrive faster than they are demodulated (file replay, catching up) consecutive blocks are therefore handed
+	// to ONE launch, which treats them as one longer stretch of samples -- the per-channel state is carried sample by sample, so the
+	// result is that of block-by-block processing.  A caller that waits for its PDUs after every block (live input: poll / sync) still
+	// gets a launch per block: a partial batch is launched by any call that needs the results.  Bounds: the LDS (Demod::init keeps what
+	// fits: 30 B per sample, three cfg3 blocks), and one second of signal -- less than half the shortest frame (2.34 s), so that a channel
+	// finishes at most one frame per launch (frame queue: one entry per channel; two data slots).
+	int want = (int)std::floor(1.0 / ((double)input_size / (double)sample_rate));
+	want = std::max(1, std::min(8, want));
+	// Where the fold bounds the block the demodulator workgroups (one per channel, ~one per CU) must stay CO-RESIDENT with the fold's
+	// (34 KiB of LDS per workgroup in the thirty-two-column form) and a forward-FFT tile: three cfg3 blocks per launch take 117 KiB of a
+	// CU's 160 KiB since the timing-recovery outputs go through a ring (round 6; round 5: two blocks, 118 KiB).  One block more and the
+	// kernels take turns (measured in round 5 at 159 KiB: a demodulator launch beside a 4.8 ms fold took 5.5 ms, profiles/r05_experiments.md).
+	if (fold_bound) want = std::min(want, 3);
+	if (ov.demod_batch) want = ov.demod_batch;                              // 1 = a launch per block
+	want = demod_fit(want);
+	if (nrx > 1) {
+		// The per-block buffers of the forward FFT scale with the receivers (spectra: two sets x half x K x N cf32; staging ring, overlap
+		// history, work): a half holds at most 32 x 2^23 / (K N) blocks -- the single-receiver cfg3 footprint (32 blocks of 2^23 bins),
+		// known to fit.  Where that binds, the fold batch (and with it the half and the staging ring) shrinks, never below one block, and
+		// the demodulator batch is clamped to the half.
+		const int64_t cap = std::max<int64_t>(1, ((int64_t)32 << 23) / ((int64_t)nrx * (int64_t)n));
+		if (cap < std::max(b.fold_nb, want)) {
+			b.fold_nb = (int)std::min<int64_t>(b.fold_nb, cap);
+			want = std::min(want, b.fold_nb);
+		}
+	}
+	if (!ov.demod_batch && want < b.fold_nb) {
+		// even launches: a half of 8 blocks at up to 7 per launch is two launches of 4, not 7 + 1 (cfg2: 5.5 against 5.8 Gsamples/s); an
+		// explicit HFDL_GPU_DEMOD_BATCH is taken as it is
+		const int launches = (b.fold_nb + want - 1) / want;
+		want = (b.fold_nb + launches - 1) / launches;
+	}
+	b.batch_want = want;
+	const int batch = demod_fit(want);
+	b.half_blocks = std::min(PLAN_MAX_HALF, ((std::max(b.fold_nb, batch) + b.fold_nb - 1) / b.fold_nb) * b.fold_nb);
+	// A pipeline that starts empty closes its first half at 16 blocks where a half holds 32: the first fold launch is the sixteen-column
+	// form and the demodulators start 3 ms earlier (the front end's half_target)
+	b.half_first = (fold_bound && b.half_blocks > 16 && !ov.no_ramp) ? 16 : b.half_blocks;
+	b.n_stage = std::min(b.half_blocks + 2, PLAN_MAX_STAGE);      // a 32-block half is not uploaded a whole half ahead: 17 blocks of link time cover a 6 ms fold five times over
+	return b;
+}
+
+// ---------------------------------------------------------------- the pruned fold's row windows (HFDL_GPU_FOLD_PRUNE = tolerance)
+
+// A channel's filter is a band-pass M / 2 bins wide with a Hamming-window stop band: of the p = N / M alias rows the fold adds up, all
+// but the few around the pass band hold taps below fp32 resolution of the sum (cfg3: rows 32 or more from the pass band hold 3.7e-8 of
+// the filter's energy as an amplitude ratio -- less than half an ulp).  From the taps' energy per (row, slot),
+// en[r * npad + c]: per channel the smallest window of rows around the pass band outside which less than tol^2 of the filter's energy
+// lies; the workgroup of an octet folds the circular hull of its eight channels' windows in quads of rows (what one matrix instruction
+// takes), rounded up to whole look-ahead groups of two quads.  Returns per octet { first quad, count } (slots nch .. npad - 1 only fill
+// an octet up) and, in *rows_max, the longest window in rows.
+struct RowWindow { int32_t first, count; };
+inline std::vector<RowWindow> fold_row_windows(const std::vector<float> &en, int p, int npad, int nch, double tol, int *rows_max)
+{
+	// per channel: the window grows from the row that holds the most energy, towards the richer neighbour, until the rows outside
+	// hold less than tol^2 of the total (rows picked by energy alone would scatter: the fp32 transform that made the taps left its
+	// rounding noise in every row, and the largest noise rows lie anywhere)
+	std::vector<std::vector<char>> keep((size_t)npad, std::vector<char>((size_t)p, 0));
+	for (int c = 0; c < nch; c++) {
+		double tot = 0;
+		int peak = 0;
+		for (int r = 0; r < p; r++) { tot += en[(size_t)r * npad + c]; if (en[(size_t)r * npad + c] > en[(size_t)peak * npad + c]) peak = r; }
+		auto e_at = [&](int r) { return (double)en[(size_t)((r % p + p) % p) * npad + c]; };
+		int lo = peak, hi = peak;                         // window [lo, hi], indices unwrapped
+		double left = tot - e_at(peak);
+		while (hi - lo + 1 < p && left > tol * tol * tot) {
+			if (e_at(lo - 1) > e_at(hi + 1)) left -= e_at(--lo); else left -= e_at(++hi);
+		}
+		for (int r = lo; r <= hi; r++) keep[(size_t)c][(size_t)((r % p + p) % p)] = 1;
+	}
+	auto hull = [&](int c0, int c1) {                   // circular hull of the rows kept by channels [c0, c1), in QUADS of rows (first quad, count)
+		const int nq = p / 4;
+		std::vector<char> any((size_t)nq, 0);
+		int kept = 0;
+		for (int c = c0; c < c1; c++) for (int r = 0; r < p; r++) if (keep[(size_t)c][(size_t)r] && !any[(size_t)(r >> 2)]) { any[(size_t)(r >> 2)] = 1; kept++; }
+		if (kept == 0) return RowWindow{ 0, 2 };         // channels that only fill the octet up: zero taps, any two quads
+		int best_len = 0, best_end = 0;                  // the longest circular run of quads nobody keeps
+		for (int q = 0; q < nq; q++) {
+			if (any[(size_t)q] || !any[(size_t)((q + nq - 1) % nq)]) continue;      // q = first quad of a gap
+			int len = 0;
+			while (len < nq && !any[(size_t)((q + len) % nq)]) len++;
+			if (len > best_len) { best_len = len; best_end = (q + len) % nq; }
+		}
+		int count = nq - best_len;
+		count = std::min(nq, (count + 1) & ~1);          // whole look-ahead groups of two quads
+		return RowWindow{ best_len ? best_end : 0, count };
+	};
+	std::vector<RowWindow> w((size_t)(npad / 8));
+	*rows_max = 0;
+	for (size_t i = 0; i < w.size(); i++) { w[i] = hull(8 * (int)i, 8 * (int)i + 8); *rows_max = std::max(*rows_max, 4 * w[i].count); }
+	return w;
 }
 
 }  // namespace hfdl

@@ -1080,7 +1080,7 @@ def test_fold_batching_changes_nothing(gpu, monkeypatch, fs, nch):
             for j in range(k):
                 fe.push_block(x[(b + j) * n:(b + j + 1) * n])
             got += fe.poll_pdus()                 # closes the half as it is: one fold launch for its k blocks
-            half = min(32, -(-max(g.fold_batch, g.demod_batch) // g.fold_batch) * g.fold_batch)      # blocks a half holds (hfdl_gpu.cpp half_blocks)
+            half = min(32, -(-max(g.fold_batch, g.demod_batch) // g.fold_batch) * g.fold_batch)      # blocks a half holds (planner.h plan_batches, half_blocks)
             # blocks of the newest half: what read_tap(back=...) still reaches.  After a drain the first half closes at 16 blocks where the
             # fold bounds the block (128 channels and more) and a half holds more; the following ones take all `half` slots
             held, target = k, (16 if (nch >= 128 and half > 16) else half)

@@ -82,3 +82,15 @@ def test_padded_receiver_layout_is_a_bijection(tmp_path):
                            os.path.join(ROOT, "tests", "hostsim", "rx_layout_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
+
+
+def test_batch_plan_and_row_windows_follow_the_documented_rules(tmp_path):
+    """planner.h plan_batches / fold_row_windows on the host (tests/hostsim/batch_plan_check.cpp): the slices, fold and demodulator
+    batches, halves and staging buffers DESIGN.md documents for cfg1 .. cfg3, the multi-receiver memory cap, explicit HFDL_GPU_DEMOD_BATCH /
+    HFDL_GPU_FOLD_BATCH; and the pruned fold's row windows: a single peak, a peak wrapping row p - 1 -> 0, an all-padding octet = (0, 2),
+    counts even and at most p / 4, a smaller tolerance never folds fewer rows."""
+    exe = str(tmp_path / "batch_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "dumphfdl_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "hostsim", "batch_plan_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
