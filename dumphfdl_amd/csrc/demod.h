@@ -13,7 +13,7 @@ struct FrameRec;
 
 struct Demod {
 	int nch = 0, outs = 0, cap = 0;         // cap = max 5400-sps samples per demodulator launch (`batch` blocks)
-	int batch = 1;                          // blocks a launch can take: what was asked for, cut down to what fits the LDS
+	int batch = 1;                          // blocks a launch can take: what was asked for, cut down by fit_batch
 	float *d_tables = nullptr;              // packed DemodTables image
 	ChanState *d_states = nullptr;
 	float2 *d_data = nullptr;               // [nch][2][5040] equalised data symbols
@@ -43,7 +43,8 @@ struct Demod {
 	size_t lds_bytes = 0;
 	void *priv = nullptr;                   // DemodPriv (host image of the tables + resolved device pointers)
 
-	static int fit_batch(int outs, float resamp_rate, int want);     // blocks a launch can take at most, `want` or fewer (LDS, 16-bit output counts, < 1 s of signal)
+	static int fit_batch(int outs, float resamp_rate, int want);     // blocks a launch can take at most, `want` or fewer (16-bit output counts, < 1 s of signal)
+	static size_t workgroup_lds();          // LDS bytes of a demodulator workgroup: the same for every launch length
 	int init(int nch, int outs, float resamp_rate, const int32_t *freqs, hipStream_t st, int batch_want = 1);
 	// K4 of a block.  `done` (optional) is signalled by the kernel's own dispatch packet.  frames_free: the caller has already
 	// ordered this launch after the decoder of launch i-2 (frames_free_event()), so no wait is queued in front of the kernel.

@@ -10,9 +10,15 @@
 // sample in dependent-instruction latency.  They only feed FORWARD -- AGC -> timing recovery -> carrier/equaliser/framer --
 // with one rare exception, so they run concurrently on three SIMDs of the CU:
 //
+//   wave 3   arbitrary resampler (msresamp_crcf_execute; no recurrence: a lane per output) of chunk s+1, and the channelizer samples
+//            of chunk s+3 fetched from HBM into an LDS ring
 //   wave 0   AGC recurrence (agc_crcf_execute) + matched filter (lanes over outputs) of chunk s
 //   wave 1   symsync_crcf of chunk s-1: every output gathers its 18-tap windows from LDS, four dot products per DPP row reduction
 //   wave 2   Costas loop, equaliser, slicer, framer FSM of chunk s-2 (demod_logic.h on_symbol)
+//
+// Every per-sample array the waves hand on is a power-of-two ring indexed by the sample's index in the launch (demod_lds.h): the LDS a
+// workgroup takes does not depend on the launch's length.  A wave is held back when it would overwrite what a later stage -- or a
+// restart of the timing recovery -- can still read; all distances are measured from wave 2's progress.
 //
 // The exception: the framer resets the timing loop (symsync_crcf_reset at the end of a frame, on a failed preamble search,
 // on carrier run-away: src/hfdl.c:714,751,969).  Wave 1 therefore runs AHEAD speculatively; when wave 2 hits a reset at
@@ -23,18 +29,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "demod_logic.h"
+#include "demod_lds.h"
 
 namespace hfdl {
 
-#ifndef HFDL_DM_CHUNK
-#define HFDL_DM_CHUNK 32
-#endif
-constexpr int DM_WAVES = 3, DM_THREADS = 64 * DM_WAVES, DM_CHUNK = HFDL_DM_CHUNK;      // chunk: measured, profiles/r02_experiments.md
-// The timing-recovery outputs travel from wave 1 to wave 2 through a RING of this many entries (round 6; until then a buffer of twice the
-// launch's samples: 16 of the 46 bytes of LDS a sample cost).  Wave 1 never runs more than two chunks ahead of what wave 2 has finished
-// (demod_block), a sample yields at most four outputs and wave 2 looks at 64 entries at a time: at most 2 x 32 x 4 + 64 entries are live.
-constexpr int OUTQ_RING = 512;
-static_assert((OUTQ_RING & (OUTQ_RING - 1)) == 0 && OUTQ_RING >= 2 * DM_CHUNK * 4 + 64 + 64, "ring: a power of two that holds what can be live");
+constexpr int DM_WAVES = 4, DM_THREADS = 64 * DM_WAVES;      // (chunk and ring sizes: demod_lds.h)
 
 // ---- DPP helpers (GFX9 encodings): all row-local, a row = 16 lanes ----
 __device__ __forceinline__ float dpp_row_shr1(float old, float src)      // lane i <- src[i-1]; lane 0 of every row <- old
@@ -93,20 +92,21 @@ __device__ __forceinline__ float lane_value(float v, int lane)           // wave
 struct DemodShared {
 	cf *outq;                      // symsync outputs of the launch, in order: output j at outq[j & (OUTQ_RING - 1)]
 	int outq_cap;                  // outputs a launch may produce at most (the 16-bit counts of cum[]); beyond it they are dropped
-	uint16_t *cum;                 // cum[k] = outputs produced up to and including input sample k
+	uint16_t *cum;                 // cum[k & DM_MASK] = outputs produced up to and including input sample k
 	const float2 *sstab;           // [16 banks][64 lanes] {tap t, tap t+16} of the lane's row: rows 0,1 matched filter, rows 2,3 derivative
 	ChanScalars *S;                // the channel's scalars; every wave owns a disjoint set of fields
-	int *mbox;                     // [2][4] progress mailbox: {mf_ready, ss_to, s3_done, s3_reset}
+	int *mbox;                     // [2][8] progress mailbox: {mf_ready, ss_to, s3_done, s3_reset, rs_ready}
 	float *sink;                   // [64] write-only scratch, one word per lane
 	cf *stage;                     // [64] the carrier wave's data symbols of one chunk (a chunk has at most 64 outputs)
 };
 
 // progress of the three stages as every wave sees it after a step's barrier
 struct PipeProgress {
-	int mf_ready = 0, ss_ready = 0, s3_done = 0;
+	int rs_ready = 0, mf_ready = 0, ss_ready = 0, s3_done = 0;
 	bool restart = false;
 	__device__ __forceinline__ void read(const int *mb)
 	{
+		rs_ready = mb[4];
 		mf_ready = mb[0];
 		s3_done = mb[2];
 		restart = mb[3] != 0;
@@ -116,11 +116,12 @@ struct PipeProgress {
 
 // ---------------- wave 0: AGC + matched filter of samples [a0, a1) ----------------
 
-__device__ __forceinline__ void agc_mf_chunk(float &g, float &y2, const ChanArrays &a, const DemodConst &T, const BlockIo &io, int a0, int a1, int lane)
+template <bool TAPS>
+__device__ __forceinline__ void agc_mf_chunk(float &g, float &y2, const DemodConst &T, const BlockIo &io, int a0, int a1, int lane)
 {
 	// agc_crcf_execute (src/hfdl.c:686): a per-sample gain recurrence, wave-uniform
 	const float alpha = AGC_BANDWIDTH;
-	const cf xin = (a0 + lane < a1 && lane < DM_CHUNK) ? io.rs[a0 + lane] : cf{0.f, 0.f};      // the chunk, one sample per lane
+	const cf xin = (a0 + lane < a1 && lane < DM_CHUNK) ? io.rs[(a0 + lane) & DM_MASK] : cf{0.f, 0.f};      // the chunk, one sample per lane
 	for (int k = a0; k < a1; k++) {
 		cf x; x.x = lane_value(xin.x, k - a0); x.y = lane_value(xin.y, k - a0);
 		cf y; y.x = x.x * g; y.y = x.y * g;
@@ -129,34 +130,82 @@ __device__ __forceinline__ void agc_mf_chunk(float &g, float &y2, const ChanArra
 		// exp(a ln y2) == 2^(a log2 y2): one v_log_f32 + one v_exp_f32 on the gain recurrence's critical path
 		if (y2 > 1e-6f) g *= __builtin_amdgcn_exp2f(-0.5f * alpha * __builtin_amdgcn_logf(y2));
 		if (g > 1e6f) g = 1e6f;
-		io.agc[k] = y;
-		io.lvl[k] = __builtin_amdgcn_rcpf(g);
+		io.agc[k & DM_AGC_MASK] = y;
+		io.lvl[k & DM_MASK] = __builtin_amdgcn_rcpf(g);
 	}
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 	__builtin_amdgcn_wave_barrier();
-	// 19-tap matched filter, lanes over the chunk's outputs (firfilt_crcf, src/hfdl.c:694-695)
+	// 19-tap matched filter, lanes over the chunk's outputs (firfilt_crcf, src/hfdl.c:694-695).  The AGC ring's entries in front of
+	// sample 0 hold the previous launch's last outputs (demod_block put mf_hist there).
 	const int k = a0 + lane;
 	if (k < a1) {
 		float ar = 0, ai = 0;
 		for (int t = 0; t < D_MF; t++) {
-			const int idx = k - t;
-			const cf x = idx >= 0 ? io.agc[idx] : a.mf_hist[-idx - 1];
+			const cf x = io.agc[(k - t) & DM_AGC_MASK];
 			ar += T.mf[t] * x.x;
 			ai += T.mf[t] * x.y;
 		}
-		io.mf[k].x = ar; io.mf[k].y = ai;
+		cf v; v.x = ar; v.y = ai;
+		const int p = k & DM_MASK;
+		io.mf[p] = v;
+		if (p >= DM_RING - SS_HIST) io.mf[p - DM_RING] = v;      // the mirror in front of entry 0 (demod_lds.h)
+		if (TAPS) { io.tap_mf[k] = v; io.tap_level[k] = io.lvl[p]; }
+	}
+}
+
+// ---------------- wave 3: arbitrary resampler, 24-bit fixed-point phase (msresamp_crcf_execute, src/hfdl.c:676) ----------------
+
+// The launch's channelizer output: `nblk` blocks end to end, one stretch of samples g = 0 .. n_in - 1.  Sample g waits in
+// ring[g & DM_IN_MASK] from when it is fetched until the resampler has gone past it; the entries in front of sample 0 hold the
+// previous launch's last D_RS_TAPS - 1 samples (ChanArrays::rs_hist).
+struct DemodInput {
+	const cf *chan;                // this channel's samples of the launch's first block
+	size_t blk_stride;             // from a block's samples to the next block's
+	const int *ends;               // LDS [DM_MAX_BLOCKS]: samples up to and including each block (blocks past the launch's last add nothing)
+	cf *ring;                      // LDS [DM_IN_RING]
+	int n_in;
+};
+
+__device__ __forceinline__ cf input_sample(const DemodInput &in, int g)
+{
+	int b = 0, start = 0;
+#pragma unroll
+	for (int u = 0; u < DM_MAX_BLOCKS - 1; u++) {
+		const int e = in.ends[u];
+		if (g >= e) { b = u + 1; start = e; }
+	}
+	return in.chan[(size_t)b * in.blk_stride + (size_t)(g - start)];
+}
+
+// outputs [k0, k1), k1 - k0 <= 64: a lane per output
+template <bool TAPS>
+__device__ __forceinline__ void resample_outputs(uint32_t rs_phase, const DemodConst &T, const BlockIo &io, const cf *ring, int k0, int k1, int lane)
+{
+	const int k = k0 + lane;
+	if (k < k1) {
+		const uint64_t t = (uint64_t)rs_phase + (uint64_t)k * T.rs_step;
+		const int i = (int)(t >> 24);
+		const float *h = T.rs_h + ((t & 0xFFFFFFu) >> 16) * D_RS_TAPS;
+		float ar = 0, ai = 0;
+		for (int j = 0; j < D_RS_TAPS; j++) {
+			const cf x = ring[(i - j) & DM_IN_MASK];
+			ar += h[j] * x.x;
+			ai += h[j] * x.y;
+		}
+		cf v; v.x = ar; v.y = ai;
+		io.rs[k & DM_MASK] = v;
+		if (TAPS) io.tap_resampled[k] = v;
 	}
 }
 
 // ---------------- wave 1: symbol timing recovery (symsync_crcf_execute, src/hfdl.c:696) ----------------
 
 // The filter windows are not kept anywhere: window sample `age` of input sample k is matched-filter output k - age, and the
-// block's matched-filter outputs sit in LDS behind a prefix holding the previous block's last 18 (SS_HIST entries before
-// mf[0], padded so that the unused "tap t + 16" reads of lanes t >= 2 stay in bounds).  Every output GATHERS its taps with
+// launch's matched-filter outputs sit in a mirrored LDS ring (demod_lds.h) whose SS_HIST entries before mf[0] hold, at the start of
+// a launch, the previous launch's last 18 (padded with zeros: the "tap t + 16" products of lanes t >= 2 read them against a zero tap).  Every output GATHERS its taps with
 // one LDS read per lane, issued one input sample ahead; nothing is shifted per input sample.  liquid's symsync_crcf_reset
 // clears the matched-filter window only: `valid_from` is the first input sample whose matched-filter window entries count
 // (older ones read as zero in rows 0, 1); ChanScalars.ss_head carries it from block to block (<= 0 at block start).
-constexpr int SS_HIST = 34;
 struct SymsyncRegs {
 	float rate, del, tau, bf, q, qhat, v1;
 	int b, decim, j;               // filter-bank index, decimation counter, running output index of the block
@@ -181,13 +230,13 @@ __device__ __forceinline__ void symsync_restart(SymsyncRegs &r, const DemodShare
 {
 	r.rate = 1.5f; r.del = 1.5f; r.tau = 0.f; r.bf = 0.f; r.q = 0.f; r.qhat = 0.f; r.v1 = 0.f;
 	r.b = 0; r.decim = 0;
-	r.j = k0 > 0 ? (int)sh.cum[k0 - 1] : 0;
+	r.j = k0 > 0 ? (int)sh.cum[(k0 - 1) & DM_MASK] : 0;
 	r.valid_from = k0;
 }
 
 __device__ __forceinline__ void symsync_store(const SymsyncRegs &r, ChanScalars &s, ChanArrays &a, const BlockIo &io, int n_out, int lane)
 {
-	if (lane < D_SS_TAPS) a.ss_dmf[lane == 0 ? 0 : D_SS_TAPS - lane] = io.mf[n_out - 1 - lane];      // reaches into the prefix when n_out < 18
+	if (lane < D_SS_TAPS) a.ss_dmf[lane == 0 ? 0 : D_SS_TAPS - lane] = io.mf[((n_out - 1) & DM_MASK) - lane];      // reaches into the mirror (the prefix when n_out < 18)
 	if (lane == 0) {
 		s.ss_rate = r.rate; s.ss_del = r.del; s.ss_tau = r.tau; s.ss_bf = r.bf; s.ss_q = r.q; s.ss_qhat = r.qhat; s.ss_v1 = r.v1;
 		s.ss_b = r.b; s.ss_decim = (uint32_t)r.decim;
@@ -196,14 +245,15 @@ __device__ __forceinline__ void symsync_store(const SymsyncRegs &r, ChanScalars 
 	}
 }
 
+// Samples [k0, k1) of ONE turn of the ring (the caller cuts a chunk at the wrap).
 // MASKED: some window entries of the chunk's first samples date from before the last timing-loop reset (only in the 18 samples after
 // one); the common chunk runs the variant without the per-sample test and selects (14 instructions of this wave's ~75 per sample).
 template <bool MASKED>
 __device__ __forceinline__ void symsync_chunk(SymsyncRegs &r, const DemodConst &T, const BlockIo &io, const DemodShared &sh, int k0, int k1, int lane)
 {
 	const int row = lane >> 4, t = lane & 15;
-	// &mf[k - t].component of this lane's row for k = 0; tap t + 16 is 16 samples further back
-	const float *base = (const float *)(io.mf - t) + (row & 1);
+	// &mf[k - t].component of this lane's row for k = the first sample of this turn of the ring; tap t + 16 is 16 samples further back
+	const float *base = (const float *)(io.mf - (k0 & ~DM_MASK) - t) + (row & 1);
 	int bi = r.b < 0 ? 0 : (r.b >= D_SS_NPFB ? D_SS_NPFB - 1 : r.b);
 	float2 h = sh.sstab[bi * 64 + lane];
 	float w_lo = base[2 * k0], w_hi = base[2 * (k0 - 16)];
@@ -259,7 +309,7 @@ __device__ __forceinline__ void symsync_chunk(SymsyncRegs &r, const DemodConst &
 		cum_v = (lane == k - k0) ? (r.j < 65535 ? r.j : 65535) : cum_v;
 		w_lo = n_lo; w_hi = n_hi;
 	}
-	if (lane < k1 - k0) sh.cum[k0 + lane] = (uint16_t)cum_v;
+	if (lane < k1 - k0) sh.cum[(k0 + lane) & DM_MASK] = (uint16_t)cum_v;
 }
 
 // ---------------- wave 2: carrier loop, equaliser, slicer, framer (src/hfdl.c:709-891) ----------------
@@ -349,9 +399,9 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 	int n = k1 - k0;                             // <= DM_CHUNK <= 64
 	// the chunk's levels, output counts and (up to 64) timing-recovery outputs, one per lane: the loop below takes them with
 	// v_readlane instead of a dependent LDS round trip per sample
-	const float lv_l = (lane < n) ? io.lvl[k0 + lane] : 0.f;
-	const int cum_l = (lane < n) ? (int)sh.cum[k0 + lane] : 0x7fffffff;
-	const int jbase = k0 > 0 ? (int)sh.cum[k0 - 1] : 0;
+	const float lv_l = (lane < n) ? io.lvl[(k0 + lane) & DM_MASK] : 0.f;
+	const int cum_l = (lane < n) ? (int)sh.cum[(k0 + lane) & DM_MASK] : 0x7fffffff;
+	const int jbase = k0 > 0 ? (int)sh.cum[(k0 - 1) & DM_MASK] : 0;
 	const cf oq_l = (jbase + lane < sh.outq_cap) ? sh.outq[(jbase + lane) & (OUTQ_RING - 1)] : cf{0.f, 0.f};
 	{   // the chunk's outputs are taken from the 64 lanes of oq_l: a chunk that produced more (a timing loop far off its rate: up to four
 		// outputs per input sample) is cut where they end, and k1 tells the caller
@@ -612,76 +662,112 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 	return -1;
 }
 
-// ---------------- one block ----------------
+// ---------------- one launch ----------------
 
 // All DM_THREADS threads of the channel's workgroup call this.  On return the channel's arrays (LDS, `a`) and scalars (*sh.S)
-// hold the state after the block.  Returns the number of 5400-sps samples produced.
+// hold the state after the launch's samples.  Returns the number of 5400-sps samples produced.
 // TAPS: the per-stage debug taps (DATADUMPS analogue) and the phase cycle counters are compiled in; the production launch uses the
-// variant without them (fewer live pointers in the carrier wave, which is short of SGPRs as it is).
+// variant without them (fewer live pointers in the carrier wave, which is short of SGPRs as it is).  A tap is written by the lane
+// that computes the sample, when it computes it.
 template <bool TAPS>
-__device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const BlockIo &io, const DemodShared &sh, const cf *in, int n_in)
+__device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const BlockIo &io, const DemodShared &sh, const DemodInput &in)
 {
 	const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
 	ChanScalars &S = *sh.S;
 	unsigned long long tR0 = __builtin_amdgcn_s_memtime();
 
-	// ---- R: arbitrary resampler, 24-bit fixed-point phase, all threads over the outputs (msresamp_crcf_execute, src/hfdl.c:676)
 	const uint32_t rs_phase = S.rs_phase;
+	const int n_in = in.n_in;
 	const uint64_t total = (uint64_t)n_in << 24;
 	int n_out = 0;
 	if ((uint64_t)rs_phase < total) n_out = (int)((total - rs_phase + T.rs_step - 1) / T.rs_step);
 	if (n_out > io.cap - 4) n_out = io.cap - 4;      // cannot happen: cap is sized from the geometry (+8); the last 4 level slots carry phase cycles
-	for (int k = tid; k < n_out; k += DM_THREADS) {
-		const uint64_t t = (uint64_t)rs_phase + (uint64_t)k * T.rs_step;
-		const int i = (int)(t >> 24);
-		const float *h = T.rs_h + ((t & 0xFFFFFFu) >> 16) * D_RS_TAPS;
-		float ar = 0, ai = 0;
-		for (int j = 0; j < D_RS_TAPS; j++) {
-			const int idx = i - j;
-			const cf x = idx >= 0 ? in[idx] : a.rs_hist[-idx - 1];
-			ar += h[j] * x.x;
-			ai += h[j] * x.y;
-		}
-		io.rs[k].x = ar; io.rs[k].y = ai;
-	}
-	__syncthreads();
-	{
+	// channelizer samples the outputs [0, k_end) need; the whole input once the last output is covered (the hand-over below reads its end)
+	auto need = [&](int k_end) {
+		return k_end >= n_out ? n_in : (int)(((uint64_t)rs_phase + (uint64_t)(k_end - 1) * T.rs_step) >> 24) + 1;
+	};
+	// what the resampler leaves for the next launch, by wave 3 when it is done with the ring
+	auto resampler_store = [&]() {
 		cf nh;
-		if (tid < D_RS_TAPS - 1) nh = (n_in - 1 - tid >= 0) ? in[n_in - 1 - tid] : a.rs_hist[tid - n_in];
-		__syncthreads();
-		if (tid < D_RS_TAPS - 1) a.rs_hist[tid] = nh;
-		if (tid == 0) {
+		if (lane < D_RS_TAPS - 1) nh = in.ring[(n_in - 1 - lane) & DM_IN_MASK];       // reaches into the entries in front of sample 0 when n_in < 13
+		__builtin_amdgcn_wave_barrier();
+		if (lane < D_RS_TAPS - 1) a.rs_hist[lane] = nh;
+		if (lane == 0) {
 			S.rs_phase = (uint32_t)((uint64_t)rs_phase + (uint64_t)n_out * T.rs_step - total);
-			if (TAPS) { io.tap_counts[0] = n_out; io.tap_counts[1] = 0; }
+			if (TAPS) io.tap_counts[0] = n_out;
 		}
+	};
+
+	// ---- ahead of the pipeline: the histories in front of sample 0 of the input and AGC rings, the channelizer samples of the first
+	// three chunks, and the resampler's first chunk -- wave 0 starts on it at once
+	if (tid < D_RS_TAPS - 1) in.ring[(-1 - tid) & DM_IN_MASK] = a.rs_hist[tid];
+	if (wave == 1 && lane < D_MF - 1) io.agc[(-1 - lane) & DM_AGC_MASK] = a.mf_hist[lane];
+	const int rs0 = n_out < DM_CHUNK ? n_out : DM_CHUNK;
+	int in_loaded = need(rs0 + 2 * DM_CHUNK);
+	for (int g = tid; g < in_loaded; g += DM_THREADS) in.ring[g & DM_IN_MASK] = input_sample(in, g);
+	if (TAPS && tid == 0) io.tap_counts[1] = 0;
+	__syncthreads();
+	if (wave == 3) resample_outputs<TAPS>(rs_phase, T, io, in.ring, 0, rs0, lane);
+	__syncthreads();
+	if (n_out < 1) {
+		if (wave == 3) resampler_store();
+		return 0;
 	}
-	__syncthreads();             // `in` (staged in the space of agc + mf) is dead from here on
-	if (n_out < 1) return 0;
 
 	unsigned long long tP0 = __builtin_amdgcn_s_memtime();
-	// ---- the three-wave pipeline over chunks of DM_CHUNK samples.  Every wave runs its OWN copy of the step loop (same number
+	// ---- the four-wave pipeline over chunks of DM_CHUNK samples.  Every wave runs its OWN copy of the step loop (same number
 	// of barriers, same mailbox reads), so that only its own stage's state is live in its registers.
 	unsigned long long busy = 0;
 	int nsym = 0;
 #ifdef HFDL_DM_PROBE
 	unsigned long long cr_probe[3] = { 0, 0, 0 };
 #endif
-	if (wave == 0) {
-		float agc_g = S.agc_g, agc_y2 = S.agc_y2;
-		PipeProgress pp;
+	PipeProgress pp;
+	pp.rs_ready = rs0;
+	if (wave == 3) {
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 4 * (step & 1);
-			int to = pp.mf_ready;
-			if (pp.mf_ready < n_out) {
-				to = pp.mf_ready + DM_CHUNK < n_out ? pp.mf_ready + DM_CHUNK : n_out;
-				agc_mf_chunk(agc_g, agc_y2, a, T, io, pp.mf_ready, to, lane);
+			int *mb = sh.mbox + 8 * (step & 1);
+			int to = pp.rs_ready;
+			if (to < n_out) {
+				to = to + DM_CHUNK < n_out ? to + DM_CHUNK : n_out;
+				if (to > pp.s3_done + DM_RS_AHEAD) to = pp.s3_done + DM_RS_AHEAD;      // the ring holds that much (never binds while the waves run in step)
+				// the samples two chunks further on are asked for first and put into the ring last: a round trip to HBM beside the fold
+				// takes as long as a chunk
+				const int hi = need(to + 2 * DM_CHUNK < n_out ? to + 2 * DM_CHUNK : n_out);
+				cf nx[2];
+#pragma unroll
+				for (int u = 0; u < 2; u++) {
+					const int g = in_loaded + 64 * u + lane;
+					nx[u] = g < hi ? input_sample(in, g) : cf{0.f, 0.f};
+				}
+				resample_outputs<TAPS>(rs_phase, T, io, in.ring, pp.rs_ready, to, lane);
+#pragma unroll
+				for (int u = 0; u < 2; u++) {
+					const int g = in_loaded + 64 * u + lane;
+					if (g < hi) in.ring[g & DM_IN_MASK] = nx[u];
+				}
+				for (int g = in_loaded + 128 + lane; g < hi; g += 64) in.ring[g & DM_IN_MASK] = input_sample(in, g);      // (a chunk spans fewer than 65 samples)
+				if (hi > in_loaded) in_loaded = hi;
 			}
+			if (lane == 0) mb[4] = to;
+			__syncthreads();
+			pp.read(mb);
+		}
+		resampler_store();
+	} else if (wave == 0) {
+		float agc_g = S.agc_g, agc_y2 = S.agc_y2;
+		for (int step = 0; pp.s3_done < n_out; step++) {
+			int *mb = sh.mbox + 8 * (step & 1);
+			int to = pp.mf_ready + DM_CHUNK < pp.rs_ready ? pp.mf_ready + DM_CHUNK : pp.rs_ready;
+			// the matched-filter ring keeps what a restart of wave 1 can read (in step, wave 2 is two chunks behind and this never binds)
+			if (to > pp.s3_done + DM_MF_AHEAD) to = pp.s3_done + DM_MF_AHEAD;
+			if (to > pp.mf_ready) agc_mf_chunk<TAPS>(agc_g, agc_y2, T, io, pp.mf_ready, to, lane); else to = pp.mf_ready;
 			if (lane == 0) mb[0] = to;
 			__syncthreads();
 			pp.read(mb);
 		}
 		cf nh;
-		if (lane < D_MF - 1) nh = (n_out - 1 - lane >= 0) ? io.agc[n_out - 1 - lane] : a.mf_hist[lane - n_out];
+		if (lane < D_MF - 1) nh = io.agc[(n_out - 1 - lane) & DM_AGC_MASK];       // reaches into the entries in front of sample 0 when n_out < 18
 		__builtin_amdgcn_wave_barrier();
 		if (lane < D_MF - 1) a.mf_hist[lane] = nh;
 		if (lane == 0) { S.agc_g = agc_g; S.agc_y2 = agc_y2; }
@@ -690,34 +776,35 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 		symsync_load(ss, S, a, io, lane);
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 		__builtin_amdgcn_wave_barrier();
-		PipeProgress pp;
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 4 * (step & 1);
+			int *mb = sh.mbox + 8 * (step & 1);
 			const unsigned long long tb = TAPS ? __builtin_amdgcn_s_memtime() : 0ull;
 			if (pp.restart) symsync_restart(ss, sh, pp.ss_ready);
 			int to = pp.ss_ready + DM_CHUNK < pp.mf_ready ? pp.ss_ready + DM_CHUNK : pp.mf_ready;
 			// never more than two chunks ahead of what wave 2 has finished: the output ring holds that much (in step, wave 2 is exactly one
 			// chunk behind and this never binds; it does when a timing loop far off its rate makes wave 2 cut its chunks short)
 			if (to > pp.s3_done + 2 * DM_CHUNK) to = pp.s3_done + 2 * DM_CHUNK;
-			if (to > pp.ss_ready) {
-				if (__builtin_expect(pp.ss_ready - (D_SS_TAPS - 1) < ss.valid_from, 0)) symsync_chunk<true>(ss, T, io, sh, pp.ss_ready, to, lane);
-				else symsync_chunk<false>(ss, T, io, sh, pp.ss_ready, to, lane);
-			} else to = pp.ss_ready;
+			if (to < pp.ss_ready) to = pp.ss_ready;
+			for (int k0 = pp.ss_ready; k0 < to;) {
+				const int k1 = (k0 | DM_MASK) + 1 < to ? (k0 | DM_MASK) + 1 : to;      // a chunk that crosses the ring's wrap: two pieces
+				if (__builtin_expect(k0 - (D_SS_TAPS - 1) < ss.valid_from, 0)) symsync_chunk<true>(ss, T, io, sh, k0, k1, lane);
+				else symsync_chunk<false>(ss, T, io, sh, k0, k1, lane);
+				k0 = k1;
+			}
 			if (lane == 0) mb[1] = to;
 			if (TAPS) busy += __builtin_amdgcn_s_memtime() - tb;
 			__syncthreads();
 			pp.read(mb);
 		}
-		if (pp.restart) symsync_restart(ss, sh, n_out);      // a reset during the block's last sample
+		if (pp.restart) symsync_restart(ss, sh, n_out);      // a reset during the launch's last sample
 		symsync_store(ss, S, a, io, n_out, lane);
 	} else {
 		CarrierRegs cr;
 		ChanScalars s3 = S;               // wave 2's working copy: it owns every field but the resampler / AGC / timing-loop ones
 		s3.ev_flags = 0;
 		carrier_load(cr, s3, a, T, lane);
-		PipeProgress pp;
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 4 * (step & 1);
+			int *mb = sh.mbox + 8 * (step & 1);
 			const unsigned long long tb = TAPS ? __builtin_amdgcn_s_memtime() : 0ull;
 			int to = pp.s3_done + DM_CHUNK < pp.ss_ready ? pp.s3_done + DM_CHUNK : pp.ss_ready;
 			int reset_at = -1;
@@ -750,13 +837,7 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	}
 	unsigned long long tP1 = __builtin_amdgcn_s_memtime();
 	if (TAPS) {
-		__syncthreads();
-		for (int k = tid; k < n_out; k += DM_THREADS) {
-			io.tap_resampled[k] = io.rs[k];
-			io.tap_mf[k] = io.mf[k];
-			io.tap_level[k] = io.lvl[k];
-		}
-		// phase cycles: resampler, the whole pipelined phase (wall), wave 1 busy, wave 2 busy
+		// phase cycles: what runs ahead of the pipeline, the whole pipelined phase (wall), wave 1 busy, wave 2 busy
 		if (tid == 0) { io.tap_level[io.cap - 4] = (float)(tP0 - tR0); io.tap_level[io.cap - 3] = (float)(tP1 - tP0); }
 		if (wave == 1 && lane == 0) io.tap_level[io.cap - 2] = (float)busy;
 		if (wave == 2 && lane == 0) io.tap_level[io.cap - 1] = (float)busy;

@@ -1,6 +1,6 @@
 // demod_kernels.hip -- K4 (per-channel streaming demodulator) and K5 (batched burst decoder) for gfx950.
 //
-// K4  demod_kernel        one workgroup of three wavefronts per channel, a software pipeline over chunks of samples;
+// K4  demod_kernel        one workgroup of four wavefronts per channel, a software pipeline over chunks of samples;
 //                         body in demod_core.h / demod_logic.h (reference src/hfdl.c:676-892)
 // K5  burst_decode_kernel one wavefront per finished frame: descramble + soft de-map + 40-row de-interleave
 //                         + rate-1/4 combine + K=7 Viterbi + octet bit reversal + PDU metadata
@@ -60,34 +60,6 @@ __device__ __forceinline__ void stage_copy(T *__restrict__ dst, const T *__restr
 	for (; i < n; i += NT) dst[i] = src[i];
 }
 
-// LDS carve-up of a channel's workgroup, shared by the kernel and the host-side size computation
-struct DemodLds {
-	size_t arrays, scalars, sstab, mf, eq, m1, corr, mbox, sink, stage, rs, agc, mfo, lvl, outq, cum, rs_h, total;
-	__host__ __device__ explicit DemodLds(int cap)
-	{
-		size_t o = 0;
-		auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
-		arrays = take(sizeof(ChanArrays));
-		scalars = take(sizeof(ChanScalars));
-		sstab = take(sizeof(float2) * D_SS_NPFB * 64);
-		mf = take(sizeof(float) * 32);
-		eq = take(sizeof(float) * 16);
-		m1 = take(sizeof(uint64_t) * 16);
-		corr = take(sizeof(float) * 128);
-		mbox = take(sizeof(int) * 8);
-		sink = take(sizeof(float) * 64);               // where the lanes of an all-lane LDS write that have nothing to say put it
-		stage = take(sizeof(cf) * 64);                 // data symbols of the carrier wave's current chunk, on their way to HBM
-		rs = take(sizeof(cf) * (size_t)cap);
-		agc = take(sizeof(cf) * (size_t)cap);          // agc and mfo are adjacent: together they stage the block's input
-		mfo = take(sizeof(cf) * ((size_t)cap + SS_HIST)) + sizeof(cf) * SS_HIST;     // SS_HIST history entries sit right before mf[0]
-		lvl = take(sizeof(float) * (size_t)cap);
-		outq = take(sizeof(cf) * (size_t)OUTQ_RING);
-		cum = take(sizeof(uint16_t) * (size_t)cap);
-		rs_h = take(sizeof(float) * D_RS_NPFB * D_RS_TAPS);
-		total = o;
-	}
-};
-
 #ifdef HFDL_LAB
 // Laboratory build: the shader clock a launch ran at, measured from inside it.  Workgroup 0 notes s_memtime (shader cycles) and
 // s_memrealtime (the constant 100 MHz reference) when it starts and when it ends: cycles / reference ticks x 100 MHz = the average clock
@@ -104,8 +76,8 @@ __device__ unsigned hfdl_clk_probe_n;
 #define HFDL_CLK_PROBE_END(tag)
 #endif
 
-// __launch_bounds__(192, 5): at most 96 VGPRs per wave (the code object says 73 used, 80 allocated).  The demodulator workgroups (three
-// waves each, on three SIMDs of a CU) are co-resident with the fold kernel's workgroups (stream A), and the two are budgeted against each
+// __launch_bounds__(256, 5): at most 96 VGPRs per wave.  The demodulator workgroups (four
+// waves each, one per SIMD of a CU; 37 KiB of LDS whatever the launch's length: demod_lds.h) are co-resident with the fold kernel's workgroups (stream A), and the two are budgeted against each
 // other: the fold's tiling leaves a SIMD at least these registers of its 512 (one 372 / 420-register wave per SIMD since round 5; four waves
 // of 104 in round 1) -- a fold tiling that does not (two waves of 256) makes the two kernels take turns and costs the pipeline 10 %
 // (fold_kernels.hip, profiles/r05/k4_tilings_in_pipeline.txt).  Staying inside the budget also keeps the loops free of scratch spills:
@@ -127,22 +99,25 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	float *l_mf = (float *)(lds + L.mf), *l_eq = (float *)(lds + L.eq), *l_corr = (float *)(lds + L.corr);
 	uint64_t *l_m1 = (uint64_t *)(lds + L.m1);
 	float *l_rs_h = (float *)(lds + L.rs_h);
-	// The channelizer output of this block is staged in LDS (in the space of agc + mf, which are written only after the
-	// resampler has consumed it: 16 cap >= 8 n_in because the resampling rate is > 0.5), and so is the resampler's filter
-	// bank: all loads of a lane are in flight together, instead of one dependent memory round trip per filter tap.
-	cf *l_in = (cf *)(lds + L.agc);
-
 	ChanState *gs = B.states + c;
 	// prologue copies with 8 loads of a lane in flight at a time: beside the fold kernel a dependent load costs microseconds
 	stage_copy<DM_THREADS>((uint32_t *)A, (const uint32_t *)&gs->a, (int)(sizeof(ChanArrays) / 4), tid);
 	stage_copy<DM_THREADS>((uint32_t *)S, (const uint32_t *)&gs->s, (int)(sizeof(ChanScalars) / 4), tid);
 	// the launch's blocks ([nblk][nch][outs]; one block unless the host batches) end to end: one stretch of channelizer output
+	int *l_blk = (int *)(lds + L.blk);
+	if (tid < DM_MAX_BLOCKS) l_blk[tid] = tid < nblk ? n_in[tid * nch + c] : 0;
+#ifdef HFDL_DM_STRICT
+	// the serial loop reads the launch's channelizer output from LDS (in the space of agc + mf, which are written only after the
+	// resampler has consumed it: 16 cap >= 8 n_in because the resampling rate is > 0.5)
+	cf *l_in = (cf *)(lds + L.agc);
 	int n_block = 0;
 	for (int b = 0; b < nblk; b++) {
 		const int nb = n_in[b * nch + c];
 		stage_copy<DM_THREADS>(l_in + n_block, chan_out + ((size_t)b * nch + c) * outs_stride, nb, tid);
 		n_block += nb;
 	}
+#endif
+	// the resampler's filter bank in LDS: all loads of a lane are in flight together, instead of one dependent memory round trip per tap
 	stage_copy<DM_THREADS>((float4 *)l_rs_h, (const float4 *)T.c.rs_h, D_RS_NPFB * D_RS_TAPS / 4, tid);
 	// symsync taps in the lane order of the timing-recovery wave: entry [bank][lane] = {tap t, tap t + 16} of the lane's row
 	for (int e = tid; e < D_SS_NPFB * 64; e += DM_THREADS) {
@@ -154,7 +129,13 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	if (tid < D_EQ) l_eq[tid] = T.c.eq_h0[tid];
 	if (tid < 8) { l_m1[tid] = T.c.m1_hi[tid]; l_m1[8 + tid] = T.c.m1_lo[tid]; }
 	if (tid < 128) l_corr[tid] = T.c.corr_tab[tid];
-	if (tid < 8) ((int *)(lds + L.mbox))[tid] = 0;
+	if (tid < 16) ((int *)(lds + L.mbox))[tid] = 0;
+	__syncthreads();
+	if (tid < DM_MAX_BLOCKS) {           // samples up to and including block tid
+		int sum = 0;
+		for (int u = 0; u <= tid; u++) sum += l_blk[u];
+		l_blk[DM_MAX_BLOCKS + tid] = sum;
+	}
 	__syncthreads();
 
 	DemodConst K = T.c;
@@ -164,6 +145,9 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	io.data = B.data + (size_t)c * 2 * MAX_DATA_SYMBOLS;
 	io.frames = B.frames; io.frame_count = B.frame_count; io.frame_cap = B.frame_cap;
 	io.channel = c;
+	DemodInput in;
+	in.chan = chan_out + (size_t)c * outs_stride; in.blk_stride = (size_t)nch * outs_stride;
+	in.ends = l_blk + DM_MAX_BLOCKS; in.ring = (cf *)(lds + L.in); in.n_in = l_blk[2 * DM_MAX_BLOCKS - 1];
 	if (TAPS) {
 		io.tap_resampled = B.tap_rs + (size_t)c * B.cap; io.tap_mf = B.tap_mf + (size_t)c * B.cap;
 		io.tap_symbols = B.tap_sym + (size_t)c * B.cap; io.tap_level = B.tap_lvl + (size_t)c * B.cap;
@@ -184,9 +168,10 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 		DemodConst Ks = K;
 		Ks.ss_mf = T.c.ss_mf; Ks.ss_dmf = T.c.ss_dmf;      // the serial loop reads the filter banks where they lie
 		demod_block_serial(*S, *A, Ks, io, l_in, n_block);
+		(void)in;
 	}
 #else
-	demod_block<TAPS>(*A, K, io, sh, l_in, n_block);
+	demod_block<TAPS>(*A, K, io, sh, in);
 #endif
 	__syncthreads();
 	{
@@ -609,16 +594,22 @@ static int set_big_lds(const void *fn, size_t bytes)
 	return 0;
 }
 
-// blocks a launch can take at most, `want` or fewer: what fits the LDS ...
+size_t Demod::workgroup_lds() { return demod_lds_bytes(0); }
+
+// blocks a launch can take at most, `want` or fewer: what the kernel's block table holds, output counts that fit 16 bits ...
+// (The LDS is no bound: the per-sample arrays are rings, demod_lds.h.  The test-only strict build keeps whole-launch arrays.)
 int Demod::fit_batch(int outs, float resamp_rate, int want)
 {
-	int batch = want < 1 ? 1 : want;
+	int batch = want < 1 ? 1 : (want > DM_MAX_BLOCKS ? DM_MAX_BLOCKS : want);
 	for (;; batch--) {
 		const int cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
+#ifdef HFDL_DM_STRICT
+		if (batch > 1 && demod_lds_bytes(cap) > 160 * 1024) continue;
+#endif
 		// ... and less than one second of signal per launch WHATEVER asked for the batch (cap samples at 5400 sps): a channel then finishes
 		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (hfdl_gpu.cpp
-		// pick_demod_batch states the same bound; an override or a larger LDS must not get past it)
-		if (batch == 1 || (demod_lds_bytes(cap) <= 160 * 1024 && 2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
+		// pick_demod_batch states the same bound; an override must not get past it)
+		if (batch == 1 || (2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
 	}
 	return batch;
 }
@@ -627,7 +618,7 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 {
 	nch = nch_; outs = outs_;
 	if (resamp_rate <= 0.5f || resamp_rate > 1.0f) return HFDL_GPU_ERANGE;   // one arbitrary stage, no half-band stages
-	// blocks per launch: the per-launch sample buffers live in LDS (30 bytes per 5400-sps sample next to ~29 KiB of tables, state and the output ring)
+	// blocks per launch
 	batch = fit_batch(outs, resamp_rate, batch_want);
 	cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
 	auto *pv = new DemodPriv();
@@ -685,7 +676,7 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, bool frames_free, hipEvent_t start)
 {
 	DemodPriv *pv = priv_of(this);
-	if (!pv || nblk < 1 || nblk > batch) return HFDL_GPU_EINVAL;
+	if (!pv || nblk < 1 || nblk > batch || nblk > DM_MAX_BLOCKS) return HFDL_GPU_EINVAL;      // (the kernel's block table holds DM_MAX_BLOCKS)
 	DemodBuffers B;
 	const uint64_t i = launches++;          // per demodulator launch (not per block: channelize-only blocks launch none)
 	// the decoder of launch i-2 has read this frame queue.  Every wait or record is a barrier packet of its own in the queue

@@ -1,0 +1,94 @@
+// demod_lds.h -- the sizes of the demodulator's LDS rings and the carve-up of a channel's workgroup (demod_kernels.hip, demod_core.h).
+// Plain C++ over demod_logic.h's state structs: the kernel, the host-side size computation and tests/hostsim read the same constructor.
+//
+// Every per-sample array is a power-of-two RING indexed by the sample's index in the launch: a workgroup's LDS does not depend on how
+// many blocks the launch takes (37 KiB: four workgroups per CU), and the batch is bounded by the 16-bit output counts and the frame
+// queue alone (Demod::fit_batch).  What keeps a ring entry alive until its last reader is done is the distance the stages may run apart,
+// all of them measured from the carrier wave's progress s3_done (demod_core.h demod_block):
+//   carrier wave (2)       reads levels, output counts and outputs of [s3_done - 1, s3_done + DM_CHUNK)
+//   timing recovery (1)    at most 2 DM_CHUNK ahead of s3_done; a restart takes it back to s3_done, where it reads SS_HIST matched-filter
+//                          samples further back
+//   AGC + matched filter   at most DM_MF_AHEAD ahead of s3_done
+//   resampler (3)          at most DM_RS_AHEAD ahead of s3_done; channelizer samples fetched two chunks ahead of that
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "demod_logic.h"
+
+namespace hfdl {
+
+#ifndef HFDL_DM_CHUNK
+#define HFDL_DM_CHUNK 32
+#endif
+constexpr int DM_CHUNK = HFDL_DM_CHUNK;      // chunk: measured, profiles/r02_experiments.md
+// The timing-recovery outputs travel from wave 1 to wave 2 through a RING of this many entries (round 6; until then a buffer of twice the
+// launch's samples: 16 of the 46 bytes of LDS a sample cost).  Wave 1 never runs more than two chunks ahead of what wave 2 has finished
+// (demod_block), a sample yields at most four outputs and wave 2 looks at 64 entries at a time: at most 2 x 32 x 4 + 64 entries are live.
+constexpr int OUTQ_RING = 512;
+static_assert((OUTQ_RING & (OUTQ_RING - 1)) == 0 && OUTQ_RING >= 2 * DM_CHUNK * 4 + 64 + 64, "ring: a power of two that holds what can be live");
+
+constexpr int SS_HIST = 34;                  // matched-filter samples the timing recovery reads behind its current one (demod_core.h)
+// Samples of the launch live at index & (DM_RING - 1): resampler output, matched-filter output, AGC level, cumulative output count.
+constexpr int DM_RING = 256, DM_MASK = DM_RING - 1;
+// The matched-filter ring is MIRRORED: its last SS_HIST entries are also kept right in front of entry 0, so that the SS_HIST samples
+// behind any sample are consecutive in memory and the timing recovery's gathers need no wrap (a chunk that crosses the wrap is
+// processed in two pieces).  An entry is overwritten DM_RING samples later, its mirror likewise: the writer must stay less than
+// DM_RING - SS_HIST ahead of the oldest sample a restart can need.
+constexpr int DM_MF_AHEAD = DM_RING - 2 * DM_CHUNK, DM_RS_AHEAD = DM_RING - DM_CHUNK;
+static_assert(DM_MF_AHEAD + SS_HIST <= DM_RING && DM_MF_AHEAD >= 3 * DM_CHUNK, "matched-filter ring: history survives, and the pipeline in step (three chunks ahead) is never held back");
+static_assert(DM_RS_AHEAD <= DM_RING && DM_RS_AHEAD >= DM_MF_AHEAD + DM_CHUNK, "resampler ring");
+// AGC outputs are read by the matched filter of the same wave only: a chunk and D_MF - 1 samples of history
+constexpr int DM_AGC_RING = 64, DM_AGC_MASK = DM_AGC_RING - 1;
+static_assert(DM_AGC_RING >= DM_CHUNK + D_MF - 1 && DM_CHUNK <= 64, "AGC ring");
+// Channelizer samples of the launch (its blocks end to end), fetched from HBM up to three chunks of resampler outputs ahead: at a
+// resampling rate > 0.5 a chunk of outputs spans fewer than 2 DM_CHUNK + 1 inputs, plus D_RS_TAPS - 1 of history
+constexpr int DM_IN_RING = 256, DM_IN_MASK = DM_IN_RING - 1;
+static_assert(DM_IN_RING >= 3 * (2 * DM_CHUNK + 1) + D_RS_TAPS, "input ring");
+// Blocks per launch at most (the block table in LDS).  Seven is what the whole-launch arrays of the earlier layout let the small
+// geometries take, and what every measurement of them was made with: cfg2's half of 8 blocks is two launches of 4, the first launch's
+// burst decoder beside the second.  Eight (one launch per half there) has not been measured.
+constexpr int DM_MAX_BLOCKS = 7;
+constexpr size_t DM_LDS_BUDGET = 40 * 1024;  // per workgroup: four to a CU's 160 KiB
+
+// LDS carve-up of a channel's workgroup, shared by the kernel and the host-side size computation
+struct DemodLds {
+	size_t arrays, scalars, sstab, mf, eq, m1, corr, mbox, blk, sink, stage, in, rs, agc, mfo, lvl, outq, cum, rs_h, total;
+	__host__ __device__ explicit DemodLds(int cap)
+	{
+		size_t o = 0;
+		auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+		arrays = take(sizeof(ChanArrays));
+		scalars = take(sizeof(ChanScalars));
+		sstab = take(sizeof(float) * 2 * D_SS_NPFB * 64);
+		mf = take(sizeof(float) * 32);
+		eq = take(sizeof(float) * 16);
+		m1 = take(sizeof(uint64_t) * 16);
+		corr = take(sizeof(float) * 128);
+		mbox = take(sizeof(int) * 16);                 // [2][8] progress mailbox
+		blk = take(sizeof(int) * 2 * DM_MAX_BLOCKS);   // channelizer samples per block of the launch, then their running sums
+		sink = take(sizeof(float) * 64);               // where the lanes of an all-lane LDS write that have nothing to say put it
+		stage = take(sizeof(cf) * 64);                 // data symbols of the carrier wave's current chunk, on their way to HBM
+#ifdef HFDL_DM_STRICT
+		// the test-only serial loop indexes the launch's samples absolutely: whole-launch arrays, the input staged in agc + mfo
+		in = 0;
+		rs = take(sizeof(cf) * (size_t)cap);
+		agc = take(sizeof(cf) * (size_t)cap);
+		mfo = take(sizeof(cf) * ((size_t)cap + SS_HIST)) + sizeof(cf) * SS_HIST;
+		lvl = take(sizeof(float) * (size_t)cap);
+		cum = take(sizeof(uint16_t) * (size_t)cap);
+#else
+		(void)cap;
+		in = take(sizeof(cf) * DM_IN_RING);
+		rs = take(sizeof(cf) * DM_RING);
+		agc = take(sizeof(cf) * DM_AGC_RING);
+		mfo = take(sizeof(cf) * (SS_HIST + DM_RING + 1)) + sizeof(cf) * SS_HIST;      // mirror, ring, one entry the look-ahead read may touch
+		lvl = take(sizeof(float) * DM_RING);
+		cum = take(sizeof(uint16_t) * DM_RING);
+#endif
+		outq = take(sizeof(cf) * (size_t)OUTQ_RING);
+		rs_h = take(sizeof(float) * D_RS_NPFB * D_RS_TAPS);
+		total = o;
+	}
+};
+
+}  // namespace hfdl

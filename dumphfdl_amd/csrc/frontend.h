@@ -27,7 +27,8 @@ struct LabConfig {
 	int fold_tile = -1;            // HFDL_GPU_FOLD_TILE: index of the fold tiling to use instead of the first that fits
 	int fold_slices = 0;           // HFDL_GPU_FOLD_SLICES (BatchOverrides::fold_slices)
 	int cu_split = 0;              // HFDL_GPU_CU_SPLIT = k (2 .. 8): the demodulator's stream on every k-th CU, the channelizer's on the others
-	bool fft_stream = false;       // HFDL_GPU_FFT_STREAM: forward FFTs on a stream of their own
+	bool cu_partition = false;     // HFDL_GPU_CU_PARTITION=1: the planner's CU partition of the fold-bound geometries (planner.h plan_cu_partition)
+	int fft_stream = -1;           // HFDL_GPU_FFT_STREAM 0 / 1: forward FFTs on a stream of their own, instead of "where the CU partition applies"
 	bool decode_stream = true;     // HFDL_GPU_DECODE_STREAM: the burst decoders on a stream of their own
 	int fold_bound = -1;           // HFDL_GPU_FOLD_BOUND 0 / 1: instead of "128 channels and more"
 	bool fold_ramp = true;         // HFDL_GPU_FOLD_RAMP=0: every half the full size from the start
@@ -113,7 +114,8 @@ struct hfdl_gpu_frontend {
 	hfdl::Stream stream_b;              // B: demodulator launches of half k-1, beside the forward FFTs and the fold of half k
 	hfdl::Stream stream_d;              // D: burst decoders + PDU snapshots, off the demodulators' critical path (an alias of B only in a laboratory A/B run)
 	hfdl::Stream stream_c;              // C: host -> device copies into the staging ring, up to n_stage - 1 blocks ahead of the blocks that compute
-	hfdl::Stream stream_f;              // F: forward FFTs of the half being filled, beside the fold of the half before (an alias of A unless HFDL_GPU_FFT_STREAM=1)
+	hfdl::Stream stream_f;              // F: forward FFTs of the half being filled, beside the fold of the half before (its own stream under the CU partition or with HFDL_GPU_FFT_STREAM=1, else an alias of A)
+	bool cu_partitioned = false;        // streams A, F and B are bound to disjoint sets of CUs (planner.h plan_cu_partition)
 	bool own_decode_stream() const { return stream_d.owned; }
 	bool fft_own_stream() const { return stream_f.owned; }
 	static constexpr int MAX_HALF = hfdl::FOLD_MAX_BLOCKS;      // blocks per half at most: what one fold launch can take (32)

@@ -185,11 +185,30 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 	return hfdl_gpu_frontend_create_multi(out, device, sample_rate, 1, &centerfreq, freqs, &nch);
 }
 
-// The streams.  Measured on MI355X: stream priority (hi/lo) and CU-masking of stream A change nothing beyond run-to-run noise
-// (profiles/r01_experiments.md), so plain non-blocking streams are used.
+// The streams: plain non-blocking ones (stream priority and CU-masking of stream A alone change nothing beyond run-to-run noise,
+// profiles/r01_experiments.md).  The laboratory build can bind the demodulator's stream and the channelizer's to disjoint sets of CUs
+// where the fold bounds the block (planner.h plan_cu_partition); the forward FFTs then get a stream of their own.  Measured slower than
+// the plain streams on cfg3 (profiles/r09_experiments.md section 2): not the product's path.
+// Order of creation: the runtime hands its hardware queues (four by default) to streams in turn, and two streams on one queue run in
+// turn -- the four that carry kernels (A, B, D, F) come first, the copy stream after them.
 static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
 {
-	if (lab.cu_split) {
+	CuPartition part = plan_cu_partition((int)fe->freqs.size(), Demod::workgroup_lds(), fe->fold_bound);
+	if (!lab.cu_partition || lab.cu_split) part.on = false;
+	if (part.on) {
+		const hipError_t ea = fe->stream.create_on_cus(part.mask_fold), eb = fe->stream_b.create_on_cus(part.mask_demod);
+		if (ea != hipSuccess || eb != hipSuccess) {
+			// the runtime refuses CU masks: plain streams, and the text says so (not an error)
+			fe->stream.reset(); fe->stream_b.reset();
+			(void)hipGetLastError();
+			(void)fail(0, "CU-masked streams refused (%s): the demodulators share the fold's CUs", hipGetErrorString(ea != hipSuccess ? ea : eb));
+			part.on = false;
+		}
+	}
+	fe->cu_partitioned = part.on;
+	if (part.on) {
+		// A and B are made
+	} else if (lab.cu_split) {
 		// Laboratory A/B: does a demodulator launch still execute twice the cycles while a fold runs, when no fold wave shares its SIMD?
 		// CU i belongs to the demodulator iff ((i >> 3) + i) % k == 0: an equal share of every XCD whether the mask counts XCD-major or
 		// XCD-interleaved.
@@ -202,19 +221,22 @@ static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
 		CREATE_TRY(fe->stream.create());
 		CREATE_TRY(fe->stream_b.create());
 	}
-	CREATE_TRY(fe->stream_c.create());
-	// Forward FFTs of the half being filled on a stream of their own, beside the fold of the half before (two sets of spectra / phasor
-	// tables / state snapshots): measured on cfg3 in round 4 (profiles/r04_experiments.md) the passes then take their HBM share out of
-	// the fold and the demodulators and the step gets slower, so the FFTs stay in front of the fold on stream A.  The switch lives in the
-	// laboratory build.  (More than four busy streams also need GPU_MAX_HW_QUEUES > 4: two streams on one hardware queue run in turn.)
-	if (lab.fft_stream) CREATE_TRY(fe->stream_f.create());
-	else fe->stream_f.alias(fe->stream);
 	// The burst decoder of launch k only hands PDUs to the host; the demodulator of launch k+1 does not need it, and a long frame
 	// ending in a block puts 0.3 - 1.2 ms of Viterbi in front of it: the decoder has its own stream (cfg2: +25 % in round 2; at 256
 	// channels the round-4 timeline shows a 1.18 ms decoder launch serially ahead of a half's first demodulator).
 	if (lab.decode_stream) CREATE_TRY(fe->stream_d.create());
 	else fe->stream_d.alias(fe->stream_b);
 	fe->demod.separate_decode = fe->own_decode_stream();
+	// Forward FFTs of the half being filled on a stream of their own, beside the fold of the half before (two sets of spectra / phasor
+	// tables / state snapshots): a laboratory switch, and what goes with the CU partition, where stream A alone would be serial.  Round 4
+	// measured it slower on cfg3 (beside demodulator workgroups of 117 KiB of LDS); with the 37 KiB demodulator it gains 2 - 4 % on cfg3
+	// and 8 % on cfg4 from device-resident input and loses 16 % with host input (profiles/r09_experiments.md section 2), so the product
+	// keeps the FFTs in front of the fold on stream A.
+	if (lab.fft_stream < 0 ? part.on : lab.fft_stream != 0) {
+		if (part.on) CREATE_TRY(fe->stream_f.create_on_cus(part.mask_fold));
+		else CREATE_TRY(fe->stream_f.create());
+	} else fe->stream_f.alias(fe->stream);
+	CREATE_TRY(fe->stream_c.create());
 	return 0;
 }
 

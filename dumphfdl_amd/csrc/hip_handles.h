@@ -39,6 +39,7 @@ struct Stream {
 	hipError_t create() { owned = true; return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 	hipError_t create_on_cus(const uint32_t mask[8]) { owned = true; return hipExtStreamCreateWithCUMask(&s, 8, mask); }
 	void alias(const Stream &o) { s = o.s; owned = false; }
+	void reset() { if (owned && s) (void)hipStreamDestroy(s); s = nullptr; owned = false; }
 	hipError_t sync() const { return owned && s ? hipStreamSynchronize(s) : hipSuccess; }
 	operator hipStream_t() const { return s; }
 };

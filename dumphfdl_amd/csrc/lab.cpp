@@ -17,7 +17,8 @@ LabConfig hfdl::read_lab_config()
 	c.fold_tile = (int)env_long("HFDL_GPU_FOLD_TILE", 0, 63, -1);
 	c.fold_slices = (int)env_long("HFDL_GPU_FOLD_SLICES", 1, 64, 0);
 	c.cu_split = (int)env_long("HFDL_GPU_CU_SPLIT", 2, 8, 0);
-	c.fft_stream = env_long("HFDL_GPU_FFT_STREAM", 0, 1, 0) != 0;
+	c.cu_partition = env_long("HFDL_GPU_CU_PARTITION", 0, 1, 0) != 0;
+	c.fft_stream = (int)env_long("HFDL_GPU_FFT_STREAM", 0, 1, -1);
 	c.decode_stream = env_long("HFDL_GPU_DECODE_STREAM", 0, 1, 1) != 0;
 	c.fold_bound = (int)env_long("HFDL_GPU_FOLD_BOUND", 0, 1, -1);
 	c.fold_ramp = env_long("HFDL_GPU_FOLD_RAMP", 0, 1, 1) != 0;

@@ -188,7 +188,7 @@ constexpr int PLAN_MAX_HALF = 32;       // blocks per half at most: what one fol
 constexpr int PLAN_MAX_STAGE = 18;      // staging buffers at most: uploads run at most 17 blocks ahead (HFDL_GPU_PREFETCH_MAX + 1)
 
 // n / input_size / pre: the block geometry (Plan).  fold_bound: the fold bounds the block (128 channels and more).  demod_fit(want):
-// blocks a demodulator launch can take, `want` or fewer (Demod::fit_batch: LDS, 16-bit output counts, < 1 s of signal).
+// blocks a demodulator launch can take, `want` or fewer (Demod::fit_batch: 16-bit output counts, < 1 s of signal).
 template <typename Fit>
 inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sample_rate, int pre, bool fold_bound, Fit demod_fit, const BatchOverrides &ov)
 {
@@ -252,6 +252,40 @@ inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sampl
 	b.half_first = (fold_bound && b.half_blocks > 16 && !ov.no_ramp) ? 16 : b.half_blocks;
 	b.n_stage = std::min(b.half_blocks + 2, PLAN_MAX_STAGE);      // a 32-block half is not uploaded a whole half ahead: 17 blocks of link time cover a 6 ms fold five times over
 	return b;
+}
+
+// ---------------------------------------------------------------- the CU partition of the fold-bound geometries
+
+// Where the fold bounds the block, the demodulator's latency-bound waves and the fold's matrix waves are kept off each other's SIMDs:
+// an fp32 matrix instruction holds a SIMD's vector issue while it runs, and beside a stream of them a demodulator wave takes 3.4 - 4.3 x
+// its cycles.  The demodulator's stream (B) gets ceil(channels / workgroups per CU) CUs, rounded up to an equal
+// share of every XCD; the channelizer's streams (A, F) get the rest.  A device of PLAN_CUS CUs in PLAN_XCDS XCDs; a CU mask counts
+// them either XCD-major (CU i in XCD i / 32) or XCD-interleaved (XCD i % 8): seen as 32 rows of 8, an XCD is a band of four rows in one
+// numbering and a column in the other.  Cell q of band m is row 4 m + q % 4, column (m + q % 4 + 2 (q / 4)) % 8: the cells of a band are
+// distinct, and over the eight bands every (q % 4, q / 4) lands in every column once -- `per_xcd` CUs in every band and in every column.
+constexpr int PLAN_CUS = 256, PLAN_XCDS = 8, PLAN_CU_LDS = 160 * 1024;
+constexpr int PLAN_DEMOD_WG_PER_CU = 4;     // at most: a demodulator workgroup puts one wave on every SIMD, its register budget is a fifth of a SIMD's
+struct CuPartition {
+	bool on = false;
+	int wg_per_cu = 0, demod_cus = 0;
+	uint32_t mask_fold[PLAN_CUS / 32] = {}, mask_demod[PLAN_CUS / 32] = {};
+};
+inline CuPartition plan_cu_partition(int nch, size_t demod_lds, bool fold_bound)
+{
+	CuPartition p;
+	if (!fold_bound || nch < 1 || demod_lds == 0 || demod_lds > (size_t)PLAN_CU_LDS) return p;
+	p.wg_per_cu = std::min<int>(PLAN_DEMOD_WG_PER_CU, (int)((size_t)PLAN_CU_LDS / demod_lds));
+	const int cus = (nch + p.wg_per_cu - 1) / p.wg_per_cu, per_xcd = (cus + PLAN_XCDS - 1) / PLAN_XCDS;
+	if (per_xcd > PLAN_CUS / PLAN_XCDS / 2) return p;        // more than half the device: the channels run beside the fold as they are
+	for (int m = 0; m < PLAN_XCDS; m++)
+		for (int q = 0; q < per_xcd; q++) {
+			const int i = (4 * m + (q & 3)) * 8 + ((m + (q & 3) + 2 * (q >> 2)) & 7);
+			p.mask_demod[i >> 5] |= 1u << (i & 31);
+		}
+	for (int w = 0; w < PLAN_CUS / 32; w++) p.mask_fold[w] = ~p.mask_demod[w];
+	p.demod_cus = per_xcd * PLAN_XCDS;
+	p.on = true;
+	return p;
 }
 
 // ---------------------------------------------------------------- the pruned fold's row windows (HFDL_GPU_FOLD_PRUNE = tolerance)

@@ -5,7 +5,10 @@
  * include/hfdl_gpu.h, plus the fold tiling sweep, the probes below and the A/B environment switches the scripts under profiles/
  * use.  Nothing here is part of the drop-in boundary; the product library exports none of it (tests/test_host_lib_cpu.py checks).
  *
- *   HFDL_GPU_FFT_STREAM=1     forward FFTs of the half being filled on a stream of their own (measured slower in round 4)
+ *   HFDL_GPU_FFT_STREAM=0|1   forward FFTs of the half being filled on the fold's stream / on a stream of their own (default: their own
+ *                             stream where the CU partition applies)
+ *   HFDL_GPU_CU_PARTITION=1   the CU partition of the fold-bound geometries (planner.h plan_cu_partition): demodulators and channelizer
+ *                             on disjoint CUs; nothing below 128 channels
  *   HFDL_GPU_DECODE_STREAM=0  burst decoders back on the demodulators' stream
  *   HFDL_GPU_FOLD_TILE=i      the i-th entry of fold_kernels.hip fold_variants[] instead of the first that fits (25: the thirty-two-column
  *                             tiling with two waves of 208 registers per SIMD)
