@@ -1,0 +1,256 @@
+// demod_host.cpp -- Demod: the host-side owner of the per-channel demodulator / burst decoder state (K4 + K5) of a front end -- its
+// device memory, the PDU ring's host logic, the statistics read-back.  The kernels and their launchers are demod_kernels.hip's
+// (demod_launch.h).
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "demod.h"
+#include "demod_launch.h"
+#include "demod_lds.h"
+#include "demod_tables.h"
+
+namespace hfdl {
+
+struct DemodImage { DemodTables h; DevTables t; };
+
+Demod::Demod() = default;
+Demod::~Demod() = default;
+
+static DevTables resolve_tables(const void *d_img, const DemodTables &h)
+{
+	const unsigned char *base = (const unsigned char *)d_img;
+	auto at = [&](const void *field) { return base + ((const unsigned char *)field - (const unsigned char *)&h); };
+	DevTables t;
+	t.c.rs_h = (const float *)at(h.rs_h);
+	t.c.rs_step = h.rs_step;
+	t.c.mf = (const float *)at(h.mf);
+	t.c.ss_mf = (const float *)at(h.ss_mf);
+	t.c.ss_dmf = (const float *)at(h.ss_dmf);
+	t.c.lf_b0 = h.lf_b0; t.c.lf_a1 = h.lf_a1; t.c.ss_rate_adj = h.ss_rate_adj;
+	t.c.eq_h0 = (const float *)at(h.eq_h0);
+	t.c.a_hi = h.a_hi; t.c.a_lo = h.a_lo;
+	t.c.m1_hi = (const uint64_t *)at(h.m1_hi);
+	t.c.m1_lo = (const uint64_t *)at(h.m1_lo);
+	t.scrambler = (const uint8_t *)at(h.scrambler);
+	t.c.corr_tab = (const float *)at(h.corr_tab);
+	t.c.psk_pts = (const float *)at(h.psk_pts);
+	t.c.a1_lo = h.a1_lo; t.c.a1_hi = h.a1_hi; t.c.a2_lo = h.a2_lo; t.c.a2_hi = h.a2_hi; t.c.pos_min = h.pos_min;
+	return t;
+}
+
+size_t Demod::workgroup_lds() { return demod_workgroup_lds(0); }
+
+// blocks a launch can take at most, `want` or fewer: what the kernel's block table holds, a workgroup's LDS (no bound for the product,
+// whose per-sample arrays are rings, demod_lds.h; the test-only strict build keeps whole-launch arrays), output counts that fit 16 bits ...
+int Demod::fit_batch(int outs, float resamp_rate, int want)
+{
+	int batch = want < 1 ? 1 : (want > DM_MAX_BLOCKS ? DM_MAX_BLOCKS : want);
+	for (;; batch--) {
+		const int cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
+		if (batch > 1 && demod_workgroup_lds(cap) > 160 * 1024) continue;
+		// ... and less than one second of signal per launch WHATEVER asked for the batch (cap samples at 5400 sps): a channel then finishes
+		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (hfdl_gpu.cpp
+		// pick_demod_batch states the same bound; an override must not get past it)
+		if (batch == 1 || (2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
+	}
+	return batch;
+}
+
+int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hipStream_t st, int batch_want)
+{
+	nch = nch_; outs = outs_;
+	if (resamp_rate <= 0.5f || resamp_rate > 1.0f) return fail(HFDL_GPU_ERANGE, "resampling rate %g outside (0.5, 1]", (double)resamp_rate);   // one arbitrary stage, no half-band stages
+	// blocks per launch
+	batch = fit_batch(outs, resamp_rate, batch_want);
+	cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
+	img = std::make_unique<DemodImage>();
+	build_demod_tables(img->h, resamp_rate);
+	CREATE_TRY(d_tables.alloc(sizeof(DemodTables)));
+	CREATE_TRY(hipMemcpyAsync(d_tables.p, &img->h, sizeof(DemodTables), hipMemcpyHostToDevice, st));
+	img->t = resolve_tables(d_tables.p, img->h);
+
+	std::vector<ChanState> init((size_t)nch);
+	for (auto &s : init) chan_state_init(s, img->h.eq_h0);
+	CREATE_TRY(d_states.alloc((size_t)nch));
+	CREATE_TRY(hipMemcpy(d_states, init.data(), sizeof(ChanState) * (size_t)nch, hipMemcpyHostToDevice));
+	CREATE_TRY(d_data.alloc((size_t)nch * 2 * MAX_DATA_SYMBOLS));
+	CREATE_TRY(hipMemsetAsync(d_data, 0, sizeof(float2) * (size_t)nch * 2 * MAX_DATA_SYMBOLS, st));
+	CREATE_TRY(d_frames.alloc(2 * (size_t)nch));
+	CREATE_TRY(d_counts.alloc(8));
+	CREATE_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * 8, st));
+	CREATE_TRY(h_snap.alloc(8));
+	std::memset(h_snap.p, 0, sizeof(int) * 8);
+	taken = 0; dropped = 0;
+	pdu_cap = std::max(4096, 64 * nch);       // ~1 KiB each; polled by the host at least once per few seconds of signal
+	if (const char *e = getenv("HFDL_GPU_PDU_RING")) {       // test / tuning knob (include/hfdl_gpu.h)
+		const long v = strtol(e, nullptr, 10);
+		if (v >= 1 && v <= (1 << 20)) pdu_cap = (int)v;
+	}
+	CREATE_TRY(d_pdus.alloc((size_t)pdu_cap));
+	CREATE_TRY(st_collect.create());
+	bounce_cap = pdu_cap < 512 ? pdu_cap : 512;
+	CREATE_TRY(h_pdu_bounce.alloc((size_t)bounce_cap));
+	CREATE_TRY(h_stats_bounce.alloc((size_t)nch));
+	CREATE_TRY(d_freqs.alloc((size_t)nch));
+	CREATE_TRY(hipMemcpyAsync(d_freqs, freqs, sizeof(int32_t) * (size_t)nch, hipMemcpyHostToDevice, st));
+	if (taps_on) {
+		CREATE_TRY(d_tap_rs.alloc((size_t)nch * cap));
+		CREATE_TRY(d_tap_mf.alloc((size_t)nch * cap));
+		CREATE_TRY(d_tap_sym.alloc((size_t)nch * cap));
+		CREATE_TRY(d_tap_lvl.alloc((size_t)nch * cap));
+		CREATE_TRY(d_tap_counts.alloc(2 * (size_t)nch));
+		CREATE_TRY(hipMemsetAsync(d_tap_counts, 0, sizeof(int) * 2 * (size_t)nch, st));
+	}
+	lds_bytes = demod_workgroup_lds(cap);
+	if (lds_bytes > 160 * 1024) return fail(HFDL_GPU_ERANGE, "a demodulator launch of %d samples needs %zu bytes of LDS", cap, lds_bytes);
+	return prepare_demod_kernels(lds_bytes);
+}
+
+// Frames finished by the demodulator of launch i are queued in d_frames[i & 1] and counted in d_counts[4 + (i & 3)].  The
+// burst decoder of launch i may run on another stream than the demodulator of launch i+1; it zeroes the counter of launch i+2,
+// whose previous users (launch i-2) are done and whose next user (the demodulator of launch i+2) is made to wait for this
+// decoder by the caller -- no memset launch per block, no counter shared by two kernels that can overlap.
+int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, bool frames_free, hipEvent_t start)
+{
+	if (!img || nblk < 1 || nblk > batch || nblk > DM_MAX_BLOCKS)       // (the kernel's block table holds DM_MAX_BLOCKS)
+		return fail(HFDL_GPU_EINVAL, "demodulator launch of %d blocks: 1 .. %d", nblk, batch);
+	DemodBuffers B;
+	const uint64_t i = launches++;          // per demodulator launch (not per block: channelize-only blocks launch none)
+	// the decoder of launch i-2 has read this frame queue.  Every wait or record is a barrier packet of its own in the queue
+	// (~5 us of idle stream each): on the demodulator-bound geometries the caller moves this one to the channelizer's stream
+	if (separate_decode && !frames_free && ev_dec[i & 1]) HIP_TRY(hipStreamWaitEvent(st, ev_dec[i & 1], 0));
+	B.states = d_states; B.data = (cf *)d_data.p; B.frames = d_frames + (size_t)(i & 1) * nch; B.counts = d_counts;
+	B.frame_count = d_counts + 4 + (int)(i & 3); B.frame_cap = nch;
+	const bool tw = taps_on && taps_enabled;
+	B.tap_rs = tw ? (cf *)d_tap_rs.p : nullptr; B.tap_mf = (cf *)d_tap_mf.p; B.tap_sym = (cf *)d_tap_sym.p; B.tap_lvl = d_tap_lvl; B.tap_counts = d_tap_counts;
+	B.cap = cap;
+	launch_demod(tw, img->t, B, (const cf *)chan_out, out_count, outs, nblk, nch, lds_bytes, st, start, done);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int Demod::enqueue_decode(int buf, hipStream_t st, hipEvent_t start, hipEvent_t stop)
+{
+	if (!img) return fail(HFDL_GPU_EINVAL, "burst decoder launch before init");
+	const uint64_t i = decodes++;
+	if (i + 1 != launches) return fail(HFDL_GPU_EINVAL, "burst decoder launch %llu without its demodulator launch", (unsigned long long)i);      // one per demodulator launch, in order
+	launch_burst_decode(d_frames + (size_t)(i & 1) * nch, d_counts, d_counts + 4 + (int)(i & 3), d_counts + 4 + (int)((i + 2) & 3), nch,
+			(const cf *)d_data.p, img->t.scrambler, d_freqs, d_pdus, pdu_cap, st, start, stop);
+	// what the ring holds once this block is done, for a host that collects without draining the pipeline
+	HIP_TRY(hipMemcpyAsync(h_snap.p + 4 * (buf & 1), d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+	if (separate_decode) {
+		if (!ev_dec[i & 1]) HIP_TRY(ev_dec[i & 1].create(EV_NO_TIMING));
+		HIP_TRY(hipEventRecord(ev_dec[i & 1], st));
+	}
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// copy ring entries [taken, produced) to the host, at most `max`; every entry below `produced` is complete.
+// `produced` may be an OLDER snapshot than `taken` (a draining poll followed by a snapshot poll with no push in between):
+// the difference is taken as signed, so a stale snapshot yields nothing instead of wrapping.
+int Demod::take(unsigned produced, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
+{
+	*n = 0;
+	const int32_t avail = (int32_t)(produced - taken);
+	if (avail <= 0 || max <= 0) return 0;
+	if (!out) return fail(HFDL_GPU_EINVAL, "null PDU buffer");              // a NULL buffer never discards PDUs
+	unsigned have = (unsigned)avail;
+	if (have > (unsigned)pdu_cap) have = (unsigned)pdu_cap;
+	const unsigned cnt = have < (unsigned)max ? have : (unsigned)max;
+	// ring entries [taken, taken + cnt) in pieces that neither wrap nor exceed the bounce buffer; each piece is copied on the
+	// collection stream (beside whatever kernels are running) and waited for on that stream alone
+	for (unsigned done = 0; done < cnt;) {
+		const unsigned first = (taken + done) % (unsigned)pdu_cap;
+		unsigned n1 = cnt - done;
+		if (n1 > (unsigned)pdu_cap - first) n1 = (unsigned)pdu_cap - first;
+		if (n1 > (unsigned)bounce_cap) n1 = (unsigned)bounce_cap;
+		HIP_TRY(hipMemcpyAsync(h_pdu_bounce.p, d_pdus + first, sizeof(hfdl_gpu_pdu) * n1, hipMemcpyDeviceToHost, st_collect));
+		HIP_TRY(hipStreamSynchronize(st_collect));
+		std::memcpy(out + done, h_pdu_bounce.p, sizeof(hfdl_gpu_pdu) * n1);
+		done += n1;
+	}
+	taken += cnt;
+	HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(d_counts + 3), (int)taken, 1, st));    // ordered after the blocks already queued
+	*n = (int32_t)cnt;
+	return 0;
+}
+
+int Demod::collect(hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
+{
+	int counts[4];
+	HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	dropped = (uint32_t)counts[2];
+	return take((unsigned)counts[1], out, max, n, st);
+}
+
+int Demod::collect_snapshot(int buf, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
+{
+	const volatile int *snap = h_snap.p + 4 * (buf & 1);
+	const uint32_t d = (uint32_t)snap[2];
+	if ((int32_t)(d - dropped) > 0) dropped = d;       // monotone: an older snapshot never takes the count back
+	return take((unsigned)snap[1], out, max, n, st);
+}
+
+int Demod::tap(int what, int channel, const void **src, size_t *nfloats)
+{
+	if (!taps_on || !taps_enabled) return fail(HFDL_GPU_EINVAL, "the stage taps are off");
+	int counts[2];
+	HIP_TRY(hipMemcpy(counts, d_tap_counts + 2 * channel, sizeof(counts), hipMemcpyDeviceToHost));
+	switch (what) {
+	case HFDL_GPU_TAP_RESAMPLED: *src = d_tap_rs + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[0]; return 0;
+	case HFDL_GPU_TAP_MF_OUT: *src = d_tap_mf + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[0]; return 0;
+	case HFDL_GPU_TAP_SYMBOLS: *src = d_tap_sym + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[1]; return 0;
+	case HFDL_GPU_TAP_AGC_LEVEL: *src = d_tap_lvl + (size_t)channel * cap; *nfloats = (size_t)counts[0]; return 0;
+	default: return fail(HFDL_GPU_EINVAL, "unknown tap %d", what);
+	}
+}
+
+static void fill_stats(const ChanScalars &sc, hfdl_gpu_channel_stats *out)
+{
+	out->a2_found = sc.cnt_a2_found; out->m1_found = sc.cnt_m1_found; out->m1_not_found = sc.cnt_m1_not_found; out->frames = sc.cnt_frames;
+	out->noise_floor_db = 20.0f * log10f(sc.noise_floor);
+	out->agc_level = 1.0f / sc.agc_g;
+	out->costas_dphi = sc.dphi;
+	out->framer_state = sc.fr_state;
+	out->sample_cnt = sc.sample_cnt; out->symbol_cnt = sc.symbol_cnt;
+	out->a1_found = sc.cnt_a1_found;
+	out->a1_corr_avg = sc.cnt_a1_found ? (float)sc.sum_a1_dev / 127.0f / (float)sc.cnt_a1_found : 0.f;
+	out->a2_corr_avg = sc.cnt_a2_found ? (float)sc.sum_a2_dev / 127.0f / (float)sc.cnt_a2_found : 0.f;
+	out->m1_corr_avg = sc.cnt_m1_found ? (float)sc.sum_m1_dev / 127.0f / (float)sc.cnt_m1_found : 0.f;
+	out->train_bits_bad = sc.cum_train_bad; out->train_bits_total = sc.cum_train_total;
+}
+
+int Demod::stats(int channel, hfdl_gpu_channel_stats *out)
+{
+	ChanScalars sc;
+	HIP_TRY(hipMemcpy(&sc, &d_states[channel].s, sizeof(sc), hipMemcpyDeviceToHost));
+	fill_stats(sc, out);
+	return 0;
+}
+
+// all channels in one strided copy; does not wait for blocks in flight (each field is read whole, the set may straddle a block)
+int Demod::stats_all(hfdl_gpu_channel_stats *out, int n)
+{
+	if (n > nch) return fail(HFDL_GPU_EINVAL, "statistics of %d channels asked for, %d exist", n, nch);
+	ChanScalars *sc = h_stats_bounce.p;
+	HIP_TRY(hipMemcpy2DAsync(sc, sizeof(ChanScalars), &d_states[0].s, sizeof(ChanState), sizeof(ChanScalars), (size_t)n, hipMemcpyDeviceToHost, st_collect));
+	HIP_TRY(hipStreamSynchronize(st_collect));
+	for (int i = 0; i < n; i++) fill_stats(sc[i], out + i);
+	return 0;
+}
+
+// the DemodTables image resident on the device and the device's own evaluation of hfdl_constants()
+int Demod::read_constants(void *tables, size_t tables_bytes, void *constants, size_t constants_bytes)
+{
+	if (tables_bytes != sizeof(DemodTables) || constants_bytes != sizeof(HfdlConstants) || !d_tables.p)
+		return fail(HFDL_GPU_EINVAL, "constants read-back: sizes %zu / %zu, this build's are %zu / %zu", tables_bytes, constants_bytes, sizeof(DemodTables), sizeof(HfdlConstants));
+	if (int rc = read_device_constants(constants)) return rc;
+	HIP_TRY(hipMemcpy(tables, d_tables.p, sizeof(DemodTables), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+}  // namespace hfdl

@@ -8,8 +8,10 @@
 //                          libfec update_viterbi27_blk / chainback_viterbi27, src/libfec/viterbi27_port.c:105-221).
 //     Viterbi mapping: lane = trellis state (64 = one wavefront); the two predecessor metrics arrive by
 //     cross-lane shuffle, the 64 decisions of a trellis step are one __ballot word kept in LDS.
+//
+// Below the kernels: their launchers (demod_launch.h; the owner of a front end's demodulator state is demod_host.cpp), the one-shot stage
+// entry points and the laboratory clock-probe read.
 #include <hip/hip_ext.h>
-#include <cstdlib>
 #include <utility>
 #include <vector>
 #include <cstring>
@@ -22,28 +24,11 @@
 #endif
 #include "demod_tables.h"
 #include "demod.h"
+#include "demod_launch.h"
 
 namespace hfdl {
 
 static_assert(sizeof(cf) == sizeof(float2), "cf must alias float2");
-
-struct DevTables {            // device image, pointers resolved on the host
-	DemodConst c;
-	const uint8_t *scrambler;
-};
-
-struct DemodBuffers {
-	ChanState *states;
-	cf *data;
-	FrameRec *frames;
-	int *counts;
-	int *frame_count;           // this launch's frames-queued counter (four, rotating: see Demod::enqueue_demod)
-	int frame_cap;
-	cf *tap_rs, *tap_mf, *tap_sym;
-	float *tap_lvl;
-	int *tap_counts;
-	int cap;
-};
 
 // global -> LDS copy by NT threads, 8 independent loads per thread issued before the first is used
 template <int NT, typename T>
@@ -547,281 +532,38 @@ __global__ void constants_kernel(HfdlConstants *out)
 	}
 }
 
-// ---------------------------------------------------------------- host side
+// ---------------------------------------------------------------- launchers (demod_launch.h)
 
-#define D_TRY(expr) do { if ((expr) != hipSuccess) return HFDL_GPU_EHIP; } while (0)
+size_t demod_workgroup_lds(int cap) { return DemodLds(cap).total; }
 
-// HIP events on the null stream around a stage entry point's launch (kernel time without the copies)
-struct KernelTimer {
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	explicit KernelTimer(bool on) { if (on && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, nullptr); }
-	double stop() { float ms = 0; if (e0 && e1) { (void)hipEventRecord(e1, nullptr); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1); } return ms; }
-	~KernelTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-static size_t demod_lds_bytes(int cap) { return DemodLds(cap).total; }
-
-static size_t k5_lds_bytes() { return 2 * (size_t)K5_TABLE_BYTES + viterbi_lds_bytes(7560) + DEC_CONST_BYTES; }
-
-static DevTables resolve_tables(const float *d_img, const DemodTables &h)
-{
-	const unsigned char *base = (const unsigned char *)d_img;
-	auto at = [&](const void *field) { return base + ((const unsigned char *)field - (const unsigned char *)&h); };
-	DevTables t;
-	t.c.rs_h = (const float *)at(h.rs_h);
-	t.c.rs_step = h.rs_step;
-	t.c.mf = (const float *)at(h.mf);
-	t.c.ss_mf = (const float *)at(h.ss_mf);
-	t.c.ss_dmf = (const float *)at(h.ss_dmf);
-	t.c.lf_b0 = h.lf_b0; t.c.lf_a1 = h.lf_a1; t.c.ss_rate_adj = h.ss_rate_adj;
-	t.c.eq_h0 = (const float *)at(h.eq_h0);
-	t.c.a_hi = h.a_hi; t.c.a_lo = h.a_lo;
-	t.c.m1_hi = (const uint64_t *)at(h.m1_hi);
-	t.c.m1_lo = (const uint64_t *)at(h.m1_lo);
-	t.scrambler = (const uint8_t *)at(h.scrambler);
-	t.c.corr_tab = (const float *)at(h.corr_tab);
-	t.c.psk_pts = (const float *)at(h.psk_pts);
-	t.c.a1_lo = h.a1_lo; t.c.a1_hi = h.a1_hi; t.c.a2_lo = h.a2_lo; t.c.a2_hi = h.a2_hi; t.c.pos_min = h.pos_min;
-	return t;
-}
-
-struct DemodPriv { DemodTables h; DevTables t; };
-static DemodPriv *priv_of(const Demod *d) { return (DemodPriv *)d->priv; }
+size_t burst_decode_lds() { return 2 * (size_t)K5_TABLE_BYTES + viterbi_lds_bytes(7560) + DEC_CONST_BYTES; }
 
 static int set_big_lds(const void *fn, size_t bytes)
 {
-	if (bytes > 64 * 1024) D_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+	if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 	return 0;
 }
 
-size_t Demod::workgroup_lds() { return demod_lds_bytes(0); }
-
-// blocks a launch can take at most, `want` or fewer: what the kernel's block table holds, output counts that fit 16 bits ...
-// (The LDS is no bound: the per-sample arrays are rings, demod_lds.h.  The test-only strict build keeps whole-launch arrays.)
-int Demod::fit_batch(int outs, float resamp_rate, int want)
+int prepare_demod_kernels(size_t demod_lds)
 {
-	int batch = want < 1 ? 1 : (want > DM_MAX_BLOCKS ? DM_MAX_BLOCKS : want);
-	for (;; batch--) {
-		const int cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
-#ifdef HFDL_DM_STRICT
-		if (batch > 1 && demod_lds_bytes(cap) > 160 * 1024) continue;
-#endif
-		// ... and less than one second of signal per launch WHATEVER asked for the batch (cap samples at 5400 sps): a channel then finishes
-		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (hfdl_gpu.cpp
-		// pick_demod_batch states the same bound; an override must not get past it)
-		if (batch == 1 || (2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
-	}
-	return batch;
-}
-
-int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hipStream_t st, int batch_want)
-{
-	nch = nch_; outs = outs_;
-	if (resamp_rate <= 0.5f || resamp_rate > 1.0f) return HFDL_GPU_ERANGE;   // one arbitrary stage, no half-band stages
-	// blocks per launch
-	batch = fit_batch(outs, resamp_rate, batch_want);
-	cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
-	auto *pv = new DemodPriv();
-	build_demod_tables(pv->h, resamp_rate);
-	priv = pv;
-	D_TRY(hipMalloc(&d_tables, sizeof(DemodTables)));
-	D_TRY(hipMemcpyAsync(d_tables, &pv->h, sizeof(DemodTables), hipMemcpyHostToDevice, st));
-	pv->t = resolve_tables(d_tables, pv->h);
-
-	std::vector<ChanState> init((size_t)nch);
-	for (auto &s : init) chan_state_init(s, pv->h.eq_h0);
-	D_TRY(hipMalloc(&d_states, sizeof(ChanState) * (size_t)nch));
-	D_TRY(hipMemcpy(d_states, init.data(), sizeof(ChanState) * (size_t)nch, hipMemcpyHostToDevice));
-	D_TRY(hipMalloc(&d_data, sizeof(float2) * (size_t)nch * 2 * MAX_DATA_SYMBOLS));
-	D_TRY(hipMemsetAsync(d_data, 0, sizeof(float2) * (size_t)nch * 2 * MAX_DATA_SYMBOLS, st));
-	D_TRY(hipMalloc(&d_frames, sizeof(FrameRec) * 2 * (size_t)nch));
-	D_TRY(hipMalloc(&d_counts, sizeof(int) * 8));
-	D_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * 8, st));
-	D_TRY(hipHostMalloc((void **)&h_snap, sizeof(int) * 8, hipHostMallocDefault));
-	std::memset(h_snap, 0, sizeof(int) * 8);
-	taken = 0; dropped = 0;
-	pdu_cap = std::max(4096, 64 * nch);       // ~1 KiB each; polled by the host at least once per few seconds of signal
-	if (const char *e = getenv("HFDL_GPU_PDU_RING")) {       // test / tuning knob (include/hfdl_gpu.h)
-		const long v = strtol(e, nullptr, 10);
-		if (v >= 1 && v <= (1 << 20)) pdu_cap = (int)v;
-	}
-	D_TRY(hipMalloc(&d_pdus, sizeof(hfdl_gpu_pdu) * (size_t)pdu_cap));
-	D_TRY(hipStreamCreateWithFlags(&st_collect, hipStreamNonBlocking));
-	bounce_cap = pdu_cap < 512 ? pdu_cap : 512;
-	D_TRY(hipHostMalloc((void **)&h_pdu_bounce, sizeof(hfdl_gpu_pdu) * (size_t)bounce_cap, hipHostMallocDefault));
-	D_TRY(hipHostMalloc(&h_stats_bounce, sizeof(ChanScalars) * (size_t)nch, hipHostMallocDefault));
-	D_TRY(hipMalloc(&d_freqs, sizeof(int32_t) * (size_t)nch));
-	D_TRY(hipMemcpyAsync(d_freqs, freqs, sizeof(int32_t) * (size_t)nch, hipMemcpyHostToDevice, st));
-	if (taps_on) {
-		D_TRY(hipMalloc(&d_tap_rs, sizeof(float2) * (size_t)nch * cap));
-		D_TRY(hipMalloc(&d_tap_mf, sizeof(float2) * (size_t)nch * cap));
-		D_TRY(hipMalloc(&d_tap_sym, sizeof(float2) * (size_t)nch * cap));
-		D_TRY(hipMalloc(&d_tap_lvl, sizeof(float) * (size_t)nch * cap));
-		D_TRY(hipMalloc(&d_tap_counts, sizeof(int) * 2 * (size_t)nch));
-		D_TRY(hipMemsetAsync(d_tap_counts, 0, sizeof(int) * 2 * (size_t)nch, st));
-	}
-	lds_bytes = demod_lds_bytes(cap);
-	if (lds_bytes > 160 * 1024) return HFDL_GPU_ERANGE;
 	int rc;
-	if ((rc = set_big_lds((const void *)demod_kernel<true>, lds_bytes))) return rc;
-	if ((rc = set_big_lds((const void *)demod_kernel<false>, lds_bytes))) return rc;
-	if ((rc = set_big_lds((const void *)burst_decode_kernel, k5_lds_bytes()))) return rc;
-	return 0;
+	if ((rc = set_big_lds((const void *)demod_kernel<true>, demod_lds))) return rc;
+	if ((rc = set_big_lds((const void *)demod_kernel<false>, demod_lds))) return rc;
+	return set_big_lds((const void *)burst_decode_kernel, burst_decode_lds());
 }
 
-// Frames finished by the demodulator of launch i are queued in d_frames[i & 1] and counted in d_counts[4 + (i & 3)].  The
-// burst decoder of launch i may run on another stream than the demodulator of launch i+1; it zeroes the counter of launch i+2,
-// whose previous users (launch i-2) are done and whose next user (the demodulator of launch i+2) is made to wait for this
-// decoder by the caller -- no memset launch per block, no counter shared by two kernels that can overlap.
-int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, bool frames_free, hipEvent_t start)
+void launch_demod(bool taps, const DevTables &T, const DemodBuffers &B, const cf *chan_out, const int *n_in, int outs_stride, int nblk, int nch,
+		size_t lds, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
-	DemodPriv *pv = priv_of(this);
-	if (!pv || nblk < 1 || nblk > batch || nblk > DM_MAX_BLOCKS) return HFDL_GPU_EINVAL;      // (the kernel's block table holds DM_MAX_BLOCKS)
-	DemodBuffers B;
-	const uint64_t i = launches++;          // per demodulator launch (not per block: channelize-only blocks launch none)
-	// the decoder of launch i-2 has read this frame queue.  Every wait or record is a barrier packet of its own in the queue
-	// (~5 us of idle stream each): on the demodulator-bound geometries the caller moves this one to the channelizer's stream
-	if (separate_decode && !frames_free && ev_dec[i & 1]) D_TRY(hipStreamWaitEvent(st, ev_dec[i & 1], 0));
-	B.states = d_states; B.data = (cf *)d_data; B.frames = d_frames + (size_t)(i & 1) * nch; B.counts = d_counts;
-	B.frame_count = d_counts + 4 + (int)(i & 3); B.frame_cap = nch;
-	const bool tw = taps_on && taps_enabled;
-	B.tap_rs = tw ? (cf *)d_tap_rs : nullptr; B.tap_mf = (cf *)d_tap_mf; B.tap_sym = (cf *)d_tap_sym; B.tap_lvl = d_tap_lvl; B.tap_counts = d_tap_counts;
-	B.cap = cap;
-	if (tw) hipExtLaunchKernelGGL(demod_kernel<true>, dim3((unsigned)nch), dim3(DM_THREADS), (unsigned)lds_bytes, st, start, done, 0, pv->t, B, (const cf *)chan_out, out_count, outs, nblk, nch);
-	else hipExtLaunchKernelGGL(demod_kernel<false>, dim3((unsigned)nch), dim3(DM_THREADS), (unsigned)lds_bytes, st, start, done, 0, pv->t, B, (const cf *)chan_out, out_count, outs, nblk, nch);
-	D_TRY(hipGetLastError());
-	return 0;
+	if (taps) hipExtLaunchKernelGGL(demod_kernel<true>, dim3((unsigned)nch), dim3(DM_THREADS), (unsigned)lds, st, start, stop, 0, T, B, chan_out, n_in, outs_stride, nblk, nch);
+	else hipExtLaunchKernelGGL(demod_kernel<false>, dim3((unsigned)nch), dim3(DM_THREADS), (unsigned)lds, st, start, stop, 0, T, B, chan_out, n_in, outs_stride, nblk, nch);
 }
 
-int Demod::enqueue_decode(int buf, hipStream_t st, hipEvent_t start, hipEvent_t stop)
+void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data,
+		const uint8_t *scrambler, const int32_t *freqs, hfdl_gpu_pdu *pdus, int pdu_cap, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
-	DemodPriv *pv = priv_of(this);
-	if (!pv) return HFDL_GPU_EINVAL;
-	const uint64_t i = decodes++;
-	if (i + 1 != launches) return HFDL_GPU_EINVAL;      // one decoder launch per demodulator launch, in order
-	hipExtLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)nch), dim3(64), (unsigned)k5_lds_bytes(), st, start, stop, 0, (const FrameRec *)(d_frames + (size_t)(i & 1) * nch), d_counts,
-			d_counts + 4 + (int)(i & 3), d_counts + 4 + (int)((i + 2) & 3), nch,
-			(const cf *)d_data, pv->t.scrambler, (const int32_t *)d_freqs, d_pdus, pdu_cap);
-	// what the ring holds once this block is done, for a host that collects without draining the pipeline
-	D_TRY(hipMemcpyAsync(h_snap + 4 * (buf & 1), d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-	if (separate_decode) {
-		if (!ev_dec[i & 1]) D_TRY(hipEventCreateWithFlags(&ev_dec[i & 1], hipEventDisableTiming));
-		D_TRY(hipEventRecord(ev_dec[i & 1], st));
-	}
-	D_TRY(hipGetLastError());
-	return 0;
-}
-
-// copy ring entries [taken, produced) to the host, at most `max`; every entry below `produced` is complete.
-// `produced` may be an OLDER snapshot than `taken` (a draining poll followed by a snapshot poll with no push in between):
-// the difference is taken as signed, so a stale snapshot yields nothing instead of wrapping.
-int Demod::take(unsigned produced, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
-{
-	*n = 0;
-	const int32_t avail = (int32_t)(produced - taken);
-	if (avail <= 0 || max <= 0) return 0;
-	if (!out) return HFDL_GPU_EINVAL;              // a NULL buffer never discards PDUs
-	unsigned have = (unsigned)avail;
-	if (have > (unsigned)pdu_cap) have = (unsigned)pdu_cap;
-	const unsigned cnt = have < (unsigned)max ? have : (unsigned)max;
-	// ring entries [taken, taken + cnt) in pieces that neither wrap nor exceed the bounce buffer; each piece is copied on the
-	// collection stream (beside whatever kernels are running) and waited for on that stream alone
-	for (unsigned done = 0; done < cnt;) {
-		const unsigned first = (taken + done) % (unsigned)pdu_cap;
-		unsigned n1 = cnt - done;
-		if (n1 > (unsigned)pdu_cap - first) n1 = (unsigned)pdu_cap - first;
-		if (n1 > (unsigned)bounce_cap) n1 = (unsigned)bounce_cap;
-		D_TRY(hipMemcpyAsync(h_pdu_bounce, d_pdus + first, sizeof(hfdl_gpu_pdu) * n1, hipMemcpyDeviceToHost, st_collect));
-		D_TRY(hipStreamSynchronize(st_collect));
-		std::memcpy(out + done, h_pdu_bounce, sizeof(hfdl_gpu_pdu) * n1);
-		done += n1;
-	}
-	taken += cnt;
-	D_TRY(hipMemsetD32Async((hipDeviceptr_t)(d_counts + 3), (int)taken, 1, st));    // ordered after the blocks already queued
-	*n = (int32_t)cnt;
-	return 0;
-}
-
-int Demod::collect(hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
-{
-	int counts[4];
-	D_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, st));
-	D_TRY(hipStreamSynchronize(st));
-	dropped = (uint32_t)counts[2];
-	return take((unsigned)counts[1], out, max, n, st);
-}
-
-int Demod::collect_snapshot(int buf, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
-{
-	const volatile int *snap = h_snap + 4 * (buf & 1);
-	const uint32_t d = (uint32_t)snap[2];
-	if ((int32_t)(d - dropped) > 0) dropped = d;       // monotone: an older snapshot never takes the count back
-	return take((unsigned)snap[1], out, max, n, st);
-}
-
-int Demod::tap(int what, int channel, const void **src, size_t *nfloats)
-{
-	if (!taps_on || !taps_enabled) return HFDL_GPU_EINVAL;
-	int counts[2];
-	D_TRY(hipMemcpy(counts, d_tap_counts + 2 * channel, sizeof(counts), hipMemcpyDeviceToHost));
-	switch (what) {
-	case HFDL_GPU_TAP_RESAMPLED: *src = d_tap_rs + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[0]; return 0;
-	case HFDL_GPU_TAP_MF_OUT: *src = d_tap_mf + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[0]; return 0;
-	case HFDL_GPU_TAP_SYMBOLS: *src = d_tap_sym + (size_t)channel * cap; *nfloats = 2 * (size_t)counts[1]; return 0;
-	case HFDL_GPU_TAP_AGC_LEVEL: *src = d_tap_lvl + (size_t)channel * cap; *nfloats = (size_t)counts[0]; return 0;
-	default: return HFDL_GPU_EINVAL;
-	}
-}
-
-static void fill_stats(const ChanScalars &sc, hfdl_gpu_channel_stats *out)
-{
-	out->a2_found = sc.cnt_a2_found; out->m1_found = sc.cnt_m1_found; out->m1_not_found = sc.cnt_m1_not_found; out->frames = sc.cnt_frames;
-	out->noise_floor_db = 20.0f * log10f(sc.noise_floor);
-	out->agc_level = 1.0f / sc.agc_g;
-	out->costas_dphi = sc.dphi;
-	out->framer_state = sc.fr_state;
-	out->sample_cnt = sc.sample_cnt; out->symbol_cnt = sc.symbol_cnt;
-	out->a1_found = sc.cnt_a1_found;
-	out->a1_corr_avg = sc.cnt_a1_found ? (float)sc.sum_a1_dev / 127.0f / (float)sc.cnt_a1_found : 0.f;
-	out->a2_corr_avg = sc.cnt_a2_found ? (float)sc.sum_a2_dev / 127.0f / (float)sc.cnt_a2_found : 0.f;
-	out->m1_corr_avg = sc.cnt_m1_found ? (float)sc.sum_m1_dev / 127.0f / (float)sc.cnt_m1_found : 0.f;
-	out->train_bits_bad = sc.cum_train_bad; out->train_bits_total = sc.cum_train_total;
-}
-
-int Demod::stats(int channel, hfdl_gpu_channel_stats *out)
-{
-	ChanScalars sc;
-	D_TRY(hipMemcpy(&sc, &d_states[channel].s, sizeof(sc), hipMemcpyDeviceToHost));
-	fill_stats(sc, out);
-	return 0;
-}
-
-// all channels in one strided copy; does not wait for blocks in flight (each field is read whole, the set may straddle a block)
-int Demod::stats_all(hfdl_gpu_channel_stats *out, int n)
-{
-	if (n > nch) return HFDL_GPU_EINVAL;
-	ChanScalars *sc = (ChanScalars *)h_stats_bounce;
-	D_TRY(hipMemcpy2DAsync(sc, sizeof(ChanScalars), &d_states[0].s, sizeof(ChanState), sizeof(ChanScalars), (size_t)n, hipMemcpyDeviceToHost, st_collect));
-	D_TRY(hipStreamSynchronize(st_collect));
-	for (int i = 0; i < n; i++) fill_stats(sc[i], out + i);
-	return 0;
-}
-
-void Demod::release()
-{
-	void *ptrs[] = { d_tables, d_states, d_data, d_frames, d_counts, d_pdus, d_freqs, d_tap_rs, d_tap_mf, d_tap_sym, d_tap_lvl, d_tap_counts };
-	for (void *p : ptrs) if (p) (void)hipFree(p);
-	if (h_snap) (void)hipHostFree(h_snap);
-	h_snap = nullptr;
-	if (st_collect) { (void)hipStreamSynchronize(st_collect); (void)hipStreamDestroy(st_collect); st_collect = nullptr; }
-	if (h_pdu_bounce) (void)hipHostFree(h_pdu_bounce);
-	if (h_stats_bounce) (void)hipHostFree(h_stats_bounce);
-	h_pdu_bounce = nullptr; h_stats_bounce = nullptr;
-	for (auto &e : ev_dec) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-	d_tables = nullptr; d_states = nullptr; d_data = nullptr; d_frames = nullptr; d_counts = nullptr; d_pdus = nullptr; d_freqs = nullptr;
-	d_tap_rs = d_tap_mf = d_tap_sym = nullptr; d_tap_lvl = nullptr; d_tap_counts = nullptr;
-	delete (DemodPriv *)priv;
-	priv = nullptr;
+	hipExtLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)frame_cap), dim3(64), (unsigned)burst_decode_lds(), st, start, stop, 0, frames, counts,
+			nframes, stale_count, frame_cap, data, scrambler, freqs, pdus, pdu_cap);
 }
 
 #ifdef HFDL_LAB
@@ -829,10 +571,10 @@ void Demod::release()
 int demod_clock_probe_read(unsigned long long *out, int max, int *n)
 {
 	unsigned cnt = 0;
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(hfdl_clk_probe_n), sizeof(cnt)));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(hfdl_clk_probe_n), sizeof(cnt)));
 	std::vector<unsigned long long> all(4096 * 4);
-	D_TRY(hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(hfdl_clk_probe), sizeof(unsigned long long) * all.size()));
+	HIP_TRY(hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(hfdl_clk_probe), sizeof(unsigned long long) * all.size()));
 	const unsigned have = cnt < 4096u ? cnt : 4096u;
 	int k = 0;
 	for (unsigned i = 0; i < have && k < max; i++) {
@@ -842,58 +584,57 @@ int demod_clock_probe_read(unsigned long long *out, int max, int *n)
 	}
 	*n = k;
 	cnt = 0;
-	D_TRY(hipMemcpyToSymbol(HIP_SYMBOL(hfdl_clk_probe_n), &cnt, sizeof(cnt)));
+	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(hfdl_clk_probe_n), &cnt, sizeof(cnt)));
 	return 0;
 }
 #endif
 
-// the DemodTables image resident on the device and the device's own evaluation of hfdl_constants()
-int Demod::read_constants(void *tables, size_t tables_bytes, void *constants, size_t constants_bytes)
+int read_device_constants(void *constants)
 {
-	if (tables_bytes != sizeof(DemodTables) || constants_bytes != sizeof(HfdlConstants) || !d_tables) return HFDL_GPU_EINVAL;
 	DevBuf d_k;
-	D_TRY(d_k.alloc(sizeof(HfdlConstants)));
-	D_TRY(hipMemset(d_k.p, 0xff, sizeof(HfdlConstants)));
+	HIP_TRY(d_k.alloc(sizeof(HfdlConstants)));
+	HIP_TRY(hipMemset(d_k.p, 0xff, sizeof(HfdlConstants)));
 	hipLaunchKernelGGL(constants_kernel, dim3(1), dim3(64), 0, nullptr, d_k.as<HfdlConstants>());
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
-	D_TRY(hipMemcpy(constants, d_k.p, sizeof(HfdlConstants), hipMemcpyDeviceToHost));
-	D_TRY(hipMemcpy(tables, d_tables, sizeof(DemodTables), hipMemcpyDeviceToHost));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(constants, d_k.p, sizeof(HfdlConstants), hipMemcpyDeviceToHost));
 	return 0;
 }
+
+// ---------------------------------------------------------------- one-shot stage entry points (demod.h; stages.cpp calls them)
 
 int demod_viterbi_batch(const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out, double *kernel_ms)
 {
 	const size_t in_bytes = (size_t)nframes * 2 * nbits, out_bytes = (size_t)nframes * ((nbits + 7) / 8);
 	const size_t lds = viterbi_lds_bytes(nbits);
-	if (lds > 160 * 1024) return HFDL_GPU_ERANGE;
+	if (lds > 160 * 1024) return fail(HFDL_GPU_ERANGE, "a Viterbi run over %d bits needs %zu bytes of LDS", nbits, lds);
 	DevBuf d_in, d_out;
-	D_TRY(d_in.alloc(in_bytes));
-	D_TRY(d_out.alloc(out_bytes));
-	D_TRY(hipMemcpy(d_in.p, soft, in_bytes, hipMemcpyHostToDevice));
-	D_TRY(hipMemset(d_out.p, 0, out_bytes));
+	HIP_TRY(d_in.alloc(in_bytes));
+	HIP_TRY(d_out.alloc(out_bytes));
+	HIP_TRY(hipMemcpy(d_in.p, soft, in_bytes, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemset(d_out.p, 0, out_bytes));
 	int rc = set_big_lds((const void *)viterbi_batch_kernel, lds);
 	if (rc) return rc;
-	KernelTimer tm(kernel_ms != nullptr);
+	StageTimer tm;
 	hipLaunchKernelGGL(viterbi_batch_kernel, dim3((unsigned)nframes), dim3(64), lds, nullptr, d_in.as<const uint8_t>(), nbits, d_out.as<uint8_t>());
-	if (kernel_ms) *kernel_ms = tm.stop();
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
-	D_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+	*kernel_ms = tm.stop();
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
 	return 0;
 }
 
 int demod_crc16(const uint8_t *data, uint32_t len, uint16_t crc_init, uint16_t *crc)
 {
 	DevBuf d_in, d_out;
-	D_TRY(d_in.alloc(len));
-	D_TRY(d_out.alloc(sizeof(uint32_t)));
-	if (len) D_TRY(hipMemcpy(d_in.p, data, len, hipMemcpyHostToDevice));
+	HIP_TRY(d_in.alloc(len));
+	HIP_TRY(d_out.alloc(sizeof(uint32_t)));
+	if (len) HIP_TRY(hipMemcpy(d_in.p, data, len, hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(crc16_kernel, dim3(1), dim3(64), 0, nullptr, d_in.as<const uint8_t>(), len, (uint32_t)crc_init, d_out.as<uint32_t>());
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
 	uint32_t v = 0;
-	D_TRY(hipMemcpy(&v, d_out.p, sizeof(v), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(&v, d_out.p, sizeof(v), hipMemcpyDeviceToHost));
 	*crc = (uint16_t)v;
 	return 0;
 }
@@ -902,18 +643,18 @@ int demod_pdu_triage_batch(const uint8_t *octets, const int32_t *lens, int32_t n
 {
 	DevBuf d_oct, d_lens, d_fcs, d_kind, d_hl;
 	const size_t n = (size_t)npdus;
-	D_TRY(d_oct.alloc(n * (size_t)stride));
-	D_TRY(d_lens.alloc(n * sizeof(int32_t)));
-	D_TRY(d_fcs.alloc(n)); D_TRY(d_kind.alloc(n)); D_TRY(d_hl.alloc(n * sizeof(uint16_t)));
-	D_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
-	D_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
+	HIP_TRY(d_oct.alloc(n * (size_t)stride));
+	HIP_TRY(d_lens.alloc(n * sizeof(int32_t)));
+	HIP_TRY(d_fcs.alloc(n)); HIP_TRY(d_kind.alloc(n)); HIP_TRY(d_hl.alloc(n * sizeof(uint16_t)));
+	HIP_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(pdu_triage_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, nullptr, d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(),
 			npdus, stride, d_fcs.as<uint8_t>(), d_kind.as<uint8_t>(), d_hl.as<uint16_t>());
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
-	D_TRY(hipMemcpy(fcs_status, d_fcs.p, n, hipMemcpyDeviceToHost));
-	D_TRY(hipMemcpy(kind, d_kind.p, n, hipMemcpyDeviceToHost));
-	D_TRY(hipMemcpy(hdr_len, d_hl.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(fcs_status, d_fcs.p, n, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(kind, d_kind.p, n, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(hdr_len, d_hl.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -922,18 +663,18 @@ int demod_psk_slice_batch(int arity, const float *xy, int32_t n, uint32_t *sym, 
 	DemodTables h;
 	build_demod_tables(h, 0.6912f);
 	DevBuf d_x, d_pts, d_sym, d_err;
-	D_TRY(d_x.alloc(sizeof(cf) * (size_t)n));
-	D_TRY(d_pts.alloc(sizeof(h.psk_pts)));
-	D_TRY(d_sym.alloc(sizeof(uint32_t) * (size_t)n));
-	D_TRY(d_err.alloc(sizeof(float) * (size_t)n));
-	D_TRY(hipMemcpy(d_x.p, xy, sizeof(cf) * (size_t)n, hipMemcpyHostToDevice));
-	D_TRY(hipMemcpy(d_pts.p, h.psk_pts, sizeof(h.psk_pts), hipMemcpyHostToDevice));
+	HIP_TRY(d_x.alloc(sizeof(cf) * (size_t)n));
+	HIP_TRY(d_pts.alloc(sizeof(h.psk_pts)));
+	HIP_TRY(d_sym.alloc(sizeof(uint32_t) * (size_t)n));
+	HIP_TRY(d_err.alloc(sizeof(float) * (size_t)n));
+	HIP_TRY(hipMemcpy(d_x.p, xy, sizeof(cf) * (size_t)n, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_pts.p, h.psk_pts, sizeof(h.psk_pts), hipMemcpyHostToDevice));
 	const int waves = n < 64 * 256 ? (n + 63) / 64 : 256;
 	hipLaunchKernelGGL(psk_slice_kernel, dim3((unsigned)waves), dim3(64), 0, nullptr, arity, d_x.as<const cf>(), n, d_pts.as<const float>(), d_sym.as<uint32_t>(), d_err.as<float>());
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
-	D_TRY(hipMemcpy(sym, d_sym.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-	D_TRY(hipMemcpy(phase_error, d_err.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(sym, d_sym.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(phase_error, d_err.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -941,15 +682,15 @@ int demod_lpdu_walk_batch(const uint8_t *octets, const int32_t *lens, int32_t np
 {
 	DevBuf d_oct, d_lens, d_cnt;
 	const size_t n = (size_t)npdus;
-	D_TRY(d_oct.alloc(n * (size_t)stride));
-	D_TRY(d_lens.alloc(n * sizeof(int32_t)));
-	D_TRY(d_cnt.alloc(n * 5));
-	D_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
-	D_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
+	HIP_TRY(d_oct.alloc(n * (size_t)stride));
+	HIP_TRY(d_lens.alloc(n * sizeof(int32_t)));
+	HIP_TRY(d_cnt.alloc(n * 5));
+	HIP_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(lpdu_walk_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, nullptr, d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(), npdus, stride, d_cnt.as<uint8_t>());
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
-	D_TRY(hipMemcpy(counts, d_cnt.p, n * 5, hipMemcpyDeviceToHost));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(counts, d_cnt.p, n * 5, hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -975,27 +716,27 @@ int demod_burst_decode_batch(const float *symbols, const int32_t *modes, const i
 	}
 	DevBuf d_scr, d_fr, d_data, d_counts, d_freqs, d_pdus;
 	int counts[8] = { 0, 0, 0, 0, nframes, 0, 0, 0 };
-	D_TRY(d_scr.alloc(DEC_CONST_BYTES));
-	D_TRY(hipMemcpy(d_scr.p, h.scrambler, DEC_CONST_BYTES, hipMemcpyHostToDevice));
-	D_TRY(d_fr.alloc(sizeof(FrameRec) * fr.size()));
-	D_TRY(hipMemcpy(d_fr.p, fr.data(), sizeof(FrameRec) * fr.size(), hipMemcpyHostToDevice));
-	D_TRY(d_data.alloc(sizeof(cf) * data.size()));
-	D_TRY(hipMemcpy(d_data.p, data.data(), sizeof(cf) * data.size(), hipMemcpyHostToDevice));
-	D_TRY(d_counts.alloc(sizeof(counts)));
-	D_TRY(hipMemcpy(d_counts.p, counts, sizeof(counts), hipMemcpyHostToDevice));
-	D_TRY(d_freqs.alloc(sizeof(int32_t) * freqs.size()));
-	D_TRY(hipMemcpy(d_freqs.p, freqs.data(), sizeof(int32_t) * freqs.size(), hipMemcpyHostToDevice));
-	D_TRY(d_pdus.alloc(sizeof(hfdl_gpu_pdu) * (size_t)nframes));
-	int rc = set_big_lds((const void *)burst_decode_kernel, k5_lds_bytes());
+	HIP_TRY(d_scr.alloc(DEC_CONST_BYTES));
+	HIP_TRY(hipMemcpy(d_scr.p, h.scrambler, DEC_CONST_BYTES, hipMemcpyHostToDevice));
+	HIP_TRY(d_fr.alloc(sizeof(FrameRec) * fr.size()));
+	HIP_TRY(hipMemcpy(d_fr.p, fr.data(), sizeof(FrameRec) * fr.size(), hipMemcpyHostToDevice));
+	HIP_TRY(d_data.alloc(sizeof(cf) * data.size()));
+	HIP_TRY(hipMemcpy(d_data.p, data.data(), sizeof(cf) * data.size(), hipMemcpyHostToDevice));
+	HIP_TRY(d_counts.alloc(sizeof(counts)));
+	HIP_TRY(hipMemcpy(d_counts.p, counts, sizeof(counts), hipMemcpyHostToDevice));
+	HIP_TRY(d_freqs.alloc(sizeof(int32_t) * freqs.size()));
+	HIP_TRY(hipMemcpy(d_freqs.p, freqs.data(), sizeof(int32_t) * freqs.size(), hipMemcpyHostToDevice));
+	HIP_TRY(d_pdus.alloc(sizeof(hfdl_gpu_pdu) * (size_t)nframes));
+	int rc = set_big_lds((const void *)burst_decode_kernel, burst_decode_lds());
 	if (rc) return rc;
-	KernelTimer tm(kernel_ms != nullptr);
-	hipLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)nframes), dim3(64), k5_lds_bytes(), nullptr, d_fr.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, (int *)nullptr,
+	StageTimer tm;
+	hipLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)nframes), dim3(64), burst_decode_lds(), nullptr, d_fr.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, (int *)nullptr,
 			nframes, d_data.as<const cf>(), d_scr.as<const uint8_t>(), d_freqs.as<const int32_t>(), d_pdus.as<hfdl_gpu_pdu>(), nframes);
-	if (kernel_ms) *kernel_ms = tm.stop();
-	D_TRY(hipDeviceSynchronize());
-	D_TRY(hipGetLastError());
+	*kernel_ms = tm.stop();
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
 	std::vector<hfdl_gpu_pdu> out((size_t)nframes);
-	D_TRY(hipMemcpy(out.data(), d_pdus.p, sizeof(hfdl_gpu_pdu) * out.size(), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(out.data(), d_pdus.p, sizeof(hfdl_gpu_pdu) * out.size(), hipMemcpyDeviceToHost));
 	for (int i = 0; i < nframes; i++) lens[i] = 0;
 	for (auto &p : out) {       // PDU slots are claimed in completion order: route by channel (= frame index)
 		if (p.channel < 0 || p.channel >= nframes) continue;

@@ -1,6 +1,7 @@
 // frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h, its launch ledger, and what the
 // translation units of the shim share (namespace hfdl).  hfdl_gpu.cpp is the pipeline, frontend_create.cpp builds a front end,
-// frontend_query.cpp reads one, stages.cpp holds the one-shot stage entry points, lab.cpp the laboratory build's switches and probes.
+// frontend_query.cpp reads one, demod_host.cpp owns its demodulator state, stages.cpp holds the one-shot stage entry points, lab.cpp the
+// laboratory build's switches and probes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <deque>
@@ -132,6 +133,9 @@ struct hfdl_gpu_frontend {
 		return e;
 	}
 	hfdl::HostFftPlan fft;
+	// (its own stream, memory and events, in that order: they go between the front end's events and its memory.  Safe, because the
+	// destructor has synchronised every stream, the demodulator's collection stream among them, before the first member goes, and
+	// nothing the front end owns is queued on that stream or waits for those events afterwards.)
 	hfdl::Demod demod;
 	int4 *d_rx = nullptr, *d_grp = nullptr;      // device copies: receiver table, fold group tables (kernels.h Geometry::grp_tab)
 	float2 *d_hist[2] = { nullptr, nullptr }, *d_work = nullptr, *d_spec = nullptr, *d_taps = nullptr, *d_partial = nullptr;

@@ -367,14 +367,13 @@ extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int devic
 	return 0;
 }
 
-// The order, explicitly: every owned stream and the monitor's event are synchronised; then the members go in reverse order of
-// declaration -- events, memory, streams (frontend.h)
+// The order, explicitly: every owned stream (the demodulator's collection stream too) and the monitor's event are synchronised; then
+// the members go in reverse order of declaration -- events, memory, streams (frontend.h)
 hfdl_gpu_frontend::~hfdl_gpu_frontend()
 {
 	(void)hipSetDevice(device);
-	for (const hfdl::Stream *s : { &stream, &stream_b, &stream_d, &stream_c, &stream_f }) (void)s->sync();
+	for (const hfdl::Stream *s : { &stream, &stream_b, &stream_d, &stream_c, &stream_f, &demod.st_collect }) (void)s->sync();
 	if (mon) (void)hipEventSynchronize(mon->ev);
-	demod.release();
 }
 
 extern "C" void hfdl_gpu_frontend_destroy(hfdl_gpu_frontend *fe) { delete fe; }

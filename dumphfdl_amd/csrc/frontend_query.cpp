@@ -210,8 +210,7 @@ extern "C" int hfdl_gpu_frontend_all_channel_stats(hfdl_gpu_frontend *fe, hfdl_g
 	if (cap < fe->geo.nch) return fail(HFDL_GPU_ERANGE, "%d channels, buffer holds %d", fe->geo.nch, cap);
 	HIP_TRY(hipSetDevice(fe->device));
 	memset(out, 0, sizeof(*out) * (size_t)fe->geo.nch);
-	int rc = fe->demod.stats_all(out, fe->geo.nch);
-	if (rc) return fail(rc, "stats read failed: %s", hipGetErrorString(hipGetLastError()));
+	if (int rc = fe->demod.stats_all(out, fe->geo.nch)) return rc;
 	for (int i = 0; i < fe->geo.nch; i++) out[i].freq = fe->freqs[(size_t)i];
 	*n = fe->geo.nch;
 	return 0;
@@ -225,9 +224,7 @@ extern "C" int hfdl_gpu_frontend_channel_stats(hfdl_gpu_frontend *fe, int32_t ch
 	if (rc) return rc;
 	memset(out, 0, sizeof(*out));
 	out->freq = fe->freqs[(size_t)channel];
-	rc = fe->demod.stats(channel, out);
-	if (rc) return fail(rc, "stats read failed: %s", hipGetErrorString(hipGetLastError()));
-	return 0;
+	return fe->demod.stats(channel, out);
 }
 
 extern "C" int hfdl_gpu_frontend_counters(hfdl_gpu_frontend *fe, hfdl_gpu_frontend_counters_t *out)
@@ -290,7 +287,7 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 		return 0; }
 	case HFDL_GPU_TAP_PHASE_CYCLES: src = fe->demod.d_tap_lvl + (size_t)channel * fe->demod.cap + fe->demod.cap - 4; nf = 4; break;
 	default:
-		if (int rc = fe->demod.tap(what, channel, &src, &nf)) return fail(rc, "unknown tap %d", what);
+		if (int rc = fe->demod.tap(what, channel, &src, &nf)) return rc;
 	}
 	if (nf > cap) return fail(HFDL_GPU_ERANGE, "tap needs %zu floats, buffer holds %zu", nf, cap);
 	if (nf) HIP_TRY(hipMemcpy(dst, src, sizeof(float) * nf, hipMemcpyDeviceToHost));

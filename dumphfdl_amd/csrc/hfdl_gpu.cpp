@@ -224,12 +224,11 @@ static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, bool after_fft
 		if (rc) return rc;
 		const int slot = buf * fe->half_blocks + j0;
 		rc = fe->demod.enqueue_demod(fe->chan_slot(slot), fe->cnt_slot(slot), take, fe->stream_b, done.event(), l == 0 && fe->frames_wait_on_a, t_start);
-		if (rc) return fail(rc, "demod enqueue failed: %s", hipGetErrorString(hipGetLastError()));
+		if (rc) return rc;
 		if (fe->own_decode_stream()) HIP_TRY(hipStreamWaitEvent(fe->stream_d, done.event(), 0));
 		hipEvent_t k5_start = nullptr, k5_stop = nullptr;
 		if ((rc = fe->timers.arm(ST_DECODE, take, k5_start, k5_stop))) return rc;
-		rc = fe->demod.enqueue_decode(buf, fe->stream_d, k5_start, k5_stop);
-		if (rc) return fail(rc, "burst decoder enqueue failed: %s", hipGetErrorString(hipGetLastError()));
+		if ((rc = fe->demod.enqueue_decode(buf, fe->stream_d, k5_start, k5_stop))) return rc;
 	}
 	fe->frames_wait_on_a = false;
 	HIP_TRY(hipEventRecord(fe->ev_demod[buf], fe->stream_d));
@@ -447,9 +446,7 @@ extern "C" int hfdl_gpu_frontend_poll_pdus(hfdl_gpu_frontend *fe, hfdl_gpu_pdu *
 {
 	int rc = check_poll_args(fe, out, max, n);
 	if (rc || (rc = hfdl_gpu_frontend_sync(fe))) return rc;
-	rc = fe->demod.collect(out, max, n, fe->stream_d);
-	if (rc) return fail(rc, "pdu collection failed: %s", hipGetErrorString(hipGetLastError()));
-	return 0;
+	return fe->demod.collect(out, max, n, fe->stream_d);
 }
 
 extern "C" int hfdl_gpu_frontend_poll_pdus_ready(hfdl_gpu_frontend *fe, hfdl_gpu_pdu *out, int32_t max, int32_t *n, int32_t max_in_flight)
@@ -480,7 +477,5 @@ extern "C" int hfdl_gpu_frontend_poll_pdus_ready(hfdl_gpu_frontend *fe, hfdl_gpu
 	// newest half's decoders, which write it next, sit behind this half's on their stream.
 	const bool decoded = hipEventQuery(fe->ev_demod[buf]) == hipSuccess;
 	if (!decoded) (void)hipGetLastError();            // "not ready" is an answer, not an error to be found by a later check
-	int rc = fe->demod.collect_snapshot(decoded ? buf : buf ^ 1, out, max, n, fe->stream_d);
-	if (rc) return fail(rc, "pdu collection failed: %s", hipGetErrorString(hipGetLastError()));
-	return 0;
+	return fe->demod.collect_snapshot(decoded ? buf : buf ^ 1, out, max, n, fe->stream_d);
 }

@@ -1,10 +1,12 @@
 // hip_handles.h -- internal: the error text every translation unit of the shim shares, and move-only owners of HIP events, streams and
-// page-locked host memory.  Device memory is owned by DevBuf (kernels.h).  hipEventDestroy / hipStreamDestroy / hipHostFree are called
-// here and nowhere else (hfdl_gpu_host_free() excepted: that memory is the caller's).
+// page-locked host memory.  Device memory is owned by DevBuf (kernels.h; DevArray here names its element type).  hipFree is called there,
+// hipEventDestroy / hipStreamDestroy / hipHostFree here, and none of them anywhere else (hfdl_gpu_host_free() excepted: that memory is
+// the caller's) -- tests/test_host_logic_cpu.py reads the sources for it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "../../include/hfdl_gpu.h"
+#include "kernels.h"
 
 namespace hfdl {
 
@@ -51,6 +53,25 @@ template <typename T> struct PinnedBuf {
 	PinnedBuf &operator=(const PinnedBuf &) = delete;
 	~PinnedBuf() { if (p) (void)hipHostFree(p); }
 	hipError_t alloc(size_t count) { return hipHostMalloc((void **)&p, sizeof(T) * count, hipHostMallocDefault); }
+};
+
+// device memory of `count` T: DevBuf with the element type in its name
+template <typename T> struct DevArray : DevBuf {
+	hipError_t alloc(size_t count) { return DevBuf::alloc(sizeof(T) * count); }
+	operator T *() const { return as<T>(); }
+};
+
+// Brackets the launches of a stage entry point with events on the null stream; stop() = their kernel time in ms, copies excluded (0 if
+// the events could not be made).  hfdl_gpu_last_stage_ms() reports it (stages.cpp).
+struct StageTimer {
+	Event e0, e1;
+	StageTimer() { if (e0.create(EV_TIMING) == hipSuccess && e1.create(EV_TIMING) == hipSuccess) (void)hipEventRecord(e0, nullptr); }
+	double stop()
+	{
+		float ms = 0;
+		if (e0 && e1) { (void)hipEventRecord(e1, nullptr); (void)hipEventSynchronize(e1); if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 0; }
+		return ms;
+	}
 };
 
 }  // namespace hfdl

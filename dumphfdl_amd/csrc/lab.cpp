@@ -63,9 +63,7 @@ extern "C" int hfdl_gpu_lab_stream_read_probe(hfdl_gpu_frontend *fe, double *gb_
 extern "C" int hfdl_gpu_lab_read_constants(hfdl_gpu_frontend *fe, void *tables, size_t tables_bytes, void *constants, size_t constants_bytes)
 {
 	if (int rc = sync_for_probe(fe, tables && constants, "null argument")) return rc;
-	int rc = fe->demod.read_constants(tables, tables_bytes, constants, constants_bytes);
-	if (rc) return fail(rc, "constants read-back failed (sizes %zu / %zu): %s", tables_bytes, constants_bytes, hipGetErrorString(hipGetLastError()));
-	return 0;
+	return fe->demod.read_constants(tables, tables_bytes, constants, constants_bytes);
 }
 
 extern "C" int hfdl_gpu_lab_clock_probe_read(int which, uint64_t *records, int32_t max, int32_t *n)

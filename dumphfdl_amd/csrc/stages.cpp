@@ -9,20 +9,11 @@ using namespace hfdl;
 static thread_local double g_stage_ms = 0.0;
 extern "C" double hfdl_gpu_last_stage_ms(void) { return g_stage_ms; }
 
-// brackets the launches of a stage entry point with events on the null stream
-struct StageTimer {
-	Event e0, e1;
-	StageTimer() { g_stage_ms = 0.0; if (e0.create(EV_TIMING) == hipSuccess && e1.create(EV_TIMING) == hipSuccess) (void)hipEventRecord(e0, nullptr); }
-	void stop() { if (e0 && e1) { (void)hipEventRecord(e1, nullptr); (void)hipEventSynchronize(e1); float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) g_stage_ms = ms; } }
-};
-
-// the arguments have been checked: select the device, run the stage, name it if it fails
-template <typename Call> static int run_stage(int device, const char *what, Call call)
+// the arguments have been checked: select the device, run the stage (demod_kernels.hip; a failure leaves its own text)
+template <typename Call> static int run_stage(int device, Call call)
 {
-	int rc = select_device(device);
-	if (rc) return rc;
-	if ((rc = call())) return fail(rc, "%s failed: %s", what, hipGetErrorString(hipGetLastError()));
-	return 0;
+	const int rc = select_device(device);
+	return rc ? rc : call();
 }
 
 extern "C" int hfdl_gpu_fft_forward(int device, const float *in, float *out, int32_t n, int shifted)
@@ -40,7 +31,7 @@ extern "C" int hfdl_gpu_fft_forward(int device, const float *in, float *out, int
 	HIP_TRY(hipMemcpy(d_in.p, in, bytes, hipMemcpyHostToDevice));
 	StageTimer tm;
 	launch_fft_forward(plan.p, nullptr, d_in.p, SFMT_CF32, 0, nullptr, d_work.as<float2>(), d_out.as<float2>(), shifted != 0, nullptr);
-	tm.stop();
+	g_stage_ms = tm.stop();
 	HIP_TRY(hipDeviceSynchronize());
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost));
@@ -50,7 +41,7 @@ extern "C" int hfdl_gpu_fft_forward(int device, const float *in, float *out, int
 extern "C" int hfdl_gpu_viterbi27(int device, const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out)
 {
 	if (!soft || !out || nbits <= 0 || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	return run_stage(device, "viterbi batch", [&] { g_stage_ms = 0.0; return demod_viterbi_batch(soft, nbits, nframes, out, &g_stage_ms); });
+	return run_stage(device, [&] { g_stage_ms = 0.0; return demod_viterbi_batch(soft, nbits, nframes, out, &g_stage_ms); });
 }
 
 extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb,
@@ -58,7 +49,7 @@ extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int
 {
 	if (!symbols || !modes || !bitmask_lsb || !octets || !lens || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	for (int i = 0; i < nframes; i++) if (modes[i] < 0 || modes[i] > 7) return fail(HFDL_GPU_EINVAL, "mode out of range");
-	return run_stage(device, "burst decode", [&] { g_stage_ms = 0.0; return demod_burst_decode_batch(symbols, modes, bitmask_lsb, nframes, octets, lens, &g_stage_ms); });
+	return run_stage(device, [&] { g_stage_ms = 0.0; return demod_burst_decode_batch(symbols, modes, bitmask_lsb, nframes, octets, lens, &g_stage_ms); });
 }
 
 // decimating_shift_addition_init + decimating_shift_addition_cc (src/libcsdr_gpl.c:26-74) on the device: the NCO / decimator
@@ -95,7 +86,7 @@ extern "C" int hfdl_gpu_nco_decimate(int device, const float *in, int32_t input_
 extern "C" int hfdl_gpu_crc16_ccitt(int device, const uint8_t *data, uint32_t len, uint16_t crc_init, uint16_t *crc)
 {
 	if (!crc || (!data && len)) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	return run_stage(device, "crc16", [&] { return demod_crc16(data, len, crc_init, crc); });
+	return run_stage(device, [&] { return demod_crc16(data, len, crc_init, crc); });
 }
 
 // PDUs of a batch: at least one, each 1 .. stride octets long
@@ -110,19 +101,19 @@ extern "C" int hfdl_gpu_pdu_triage(int device, const uint8_t *octets, const int3
 {
 	if (!octets || !lens || !fcs_status || !pdu_kind || !hdr_len || npdus <= 0 || stride <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	if (int rc = check_pdu_lens(lens, npdus, stride)) return rc;
-	return run_stage(device, "pdu triage", [&] { return demod_pdu_triage_batch(octets, lens, npdus, stride, fcs_status, pdu_kind, hdr_len); });
+	return run_stage(device, [&] { return demod_pdu_triage_batch(octets, lens, npdus, stride, fcs_status, pdu_kind, hdr_len); });
 }
 
 extern "C" int hfdl_gpu_lpdu_walk(int device, const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *counts)
 {
 	if (!octets || !lens || !counts || npdus <= 0 || stride <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	if (int rc = check_pdu_lens(lens, npdus, stride)) return rc;
-	return run_stage(device, "lpdu walk", [&] { return demod_lpdu_walk_batch(octets, lens, npdus, stride, counts); });
+	return run_stage(device, [&] { return demod_lpdu_walk_batch(octets, lens, npdus, stride, counts); });
 }
 
 extern "C" int hfdl_gpu_psk_slice(int device, int32_t arity, const float *xy, int32_t n, uint32_t *sym, float *phase_error)
 {
 	if (!xy || !sym || !phase_error || n <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	if (arity < 1 || arity > 3) return fail(HFDL_GPU_EINVAL, "arity %d: HFDL uses BPSK, QPSK and 8-PSK (1..3 bits per symbol)", arity);
-	return run_stage(device, "psk slice", [&] { return demod_psk_slice_batch(arity, xy, n, sym, phase_error); });
+	return run_stage(device, [&] { return demod_psk_slice_batch(arity, xy, n, sym, phase_error); });
 }

@@ -121,6 +121,31 @@ def test_product_does_not_touch_the_oracle():
     assert "oracle" not in out
 
 
+def test_hip_resources_are_released_by_their_owners_alone():
+    """hip_handles.h: device memory, page-locked memory, events and streams are released by the destructors of their owning types
+    (DevBuf in kernels.h, the others in hip_handles.h) and nowhere else under csrc/ -- hfdl_gpu_host_free() excepted, whose memory is
+    the caller's.  No translation unit keeps a list of raw handles to free by hand: no release(), no untyped `void *priv`, and no
+    D_TRY (a HIP error without text; HIP_TRY / CREATE_TRY name the call, and CREATE_TRY reports an allocation that does not fit as
+    HFDL_GPU_ENOMEM).  The one `release()` in the sources is std::unique_ptr's, where create hands the finished front end to the
+    caller of the C interface."""
+    csrc = os.path.join(ROOT, "dumphfdl_amd", "csrc")
+    calls = ("hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy(")
+    found = {}
+    for f in sorted(os.listdir(csrc)):
+        for ln in open(os.path.join(csrc, f), errors="replace").read().splitlines():
+            for c in calls:
+                if c in ln:
+                    found.setdefault(f, set()).add(c)
+            assert "void *priv" not in ln and "D_TRY" not in ln, (f, ln)
+            if "release()" in ln:
+                assert (f, ln.strip()) == ("frontend_create.cpp", "*out = fe.release();"), (f, ln)
+    assert found.pop("kernels.h") == {"hipFree("}
+    assert found.pop("hip_handles.h") == {"hipHostFree(", "hipEventDestroy(", "hipStreamDestroy("}
+    assert found == {"frontend_query.cpp": {"hipHostFree("}}, found
+    q = open(os.path.join(csrc, "frontend_query.cpp")).read()
+    assert q.count("hipHostFree(") == 1 and "hipHostFree(" in q[q.index("hfdl_gpu_host_free("):].split("\n}\n")[0]
+
+
 @pytest.mark.parametrize("fs,off", [(250000, 37000), (250000, -101500), (1000000, 412345), (8000000, -3163000), (40000000, 19081440)])
 def test_planner_matches_oracle(sim, oracle, fs, off):
     dec, tbw, _ = oracle.geometry(fs)
