@@ -444,7 +444,122 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 	};
 	bool runaway = fabsf(s.dphi) > COSTAS_RUNAWAY_DPHI && s.fr_state == FR_A1;
 	const int pair_sel = (lane & 1) << 2;        // byte offset of the pair's second output in a lane permute
-	for (int j = jbase; j < jstop;) {
+	auto pair_step = [&](int j) {                // outputs j (off time) and j + 1 (on time) through the carrier NCO into the equaliser's window
+		// A symbol's two timing-recovery outputs at once, the off-time one in the even lanes and the on-time one in the odd lanes:
+		// one rotation (sin, cos, four products) and one two-lane move of the equaliser window serve both -- the window's newest
+		// entries are lanes 14 (even: the off-time sample) and 15 (odd: the on-time sample) of its row.  Same arithmetic per
+		// output as the single step below; only the carrier phase of each has to be stepped and wrapped on its own.
+		const int sel = ((j - jbase) << 2) + pair_sel;
+		cf oi;
+		oi.x = __int_as_float(__builtin_amdgcn_ds_bpermute(sel, __float_as_int(oq_l.x)));
+		oi.y = __int_as_float(__builtin_amdgcn_ds_bpermute(sel, __float_as_int(oq_l.y)));
+		float ph1, ph2;
+		{
+			const float ph = s.phi + s.dphi;
+			const float dn = ph - (float)(2.0 * M_PI), up = ph + (float)(2.0 * M_PI);
+			ph1 = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
+		}
+		{
+			const float ph = ph1 + s.dphi;
+			const float dn = ph - (float)(2.0 * M_PI), up = ph + (float)(2.0 * M_PI);
+			ph2 = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
+		}
+		s.phi = ph2;
+#ifdef HFDL_DM_LIBM_TRIG
+		float sp, cp;
+		sincosf((lane & 1) ? ph2 : ph1, &sp, &cp);
+#else
+		const float rev = ((lane & 1) ? ph2 : ph1) * 0.15915494309189535f;
+		const float sp = __builtin_amdgcn_sinf(rev), cp = __builtin_amdgcn_cosf(rev);
+#endif
+		cf r;
+		r.x = oi.x * cp + oi.y * sp;
+		r.y = oi.y * cp - oi.x * sp;
+		const float x2n = r.x * r.x + r.y * r.y;
+		const float x2n1 = lane_value(x2n, 0), x2n2 = lane_value(x2n, 1);
+		const float x2o1 = lane_value(c.ex2, 1), x2o2 = lane_value(c.ex2, 2);
+		const float nu = row1 ? r.y : r.x, nv = row1 ? -r.x : r.y;
+		c.eu = dpp_row_shl2(nu, c.eu);
+		c.ev = dpp_row_shl2(nv, c.ev);
+		c.ex2 = dpp_row_shl2(x2n, c.ex2);
+		s.eq_x2sum = s.eq_x2sum + x2n1 - x2o1;
+		s.eq_x2sum = s.eq_x2sum + x2n2 - x2o2;
+	};
+	// eqlms_cccf_execute, sum conj(w_i) x_i: real part reduced in row 0, imaginary part in row 1, one scan
+	auto equalise = [&]() {
+		const float p = row_scan_sum(act ? c.ewx * c.eu + c.ewy * c.ev : 0.f);
+		cf y; y.x = lane_value(p, 15); y.y = lane_value(p, 31);
+		return y;
+	};
+	// eqlms_cccf_step(d = known T symbol, d_hat = y)
+	auto train_step = [&](cf y) {
+		const float tv = t_symbol(s.T_idx) * ((s.bitmask & 1u) ? -1.0f : 1.0f);
+		const float er = tv - y.x, ei = -(0.0f - y.y);
+		const float bx = row1 ? -c.ev : c.eu, by = row1 ? c.eu : c.ev;       // the window sample (x, y) in either row
+		const float pr = er * bx - ei * by, pi = er * by + ei * bx;
+		c.ewx = c.ewx + EQ_STEP * pr / s.eq_x2sum;
+		c.ewy = c.ewy + EQ_STEP * pi / s.eq_x2sum;
+	};
+	// The in-frame run.  Tried at the start of the chunk and at the end of every iteration that leaves the framer outside the search: the
+	// searching framer's iterations pay one scalar compare for it and share no block with it.
+	auto in_frame_run = [&](int &j) {
+		if (!(s.symsync_out_idx & 1u) && j + 1 < jstop && s.fr_state >= FR_EQ_TRAIN && s.symbols_wanted > 1 && s.s_state == SAMPLER_SYMBOLS) {
+			// Inside a frame, between two framer transitions: the next symbols_wanted - 1 symbols are all handled alike (training symbols
+			// into the equaliser's update, data symbols into the stage), the framer state stands still and the timing-recovery outputs
+			// stay paired.  They run here as one tight loop -- the same statements in the same order as the general iteration below
+			// takes for each of them (pair step, equaliser, training step, decision, carrier loop, sampler, signal level), without its
+			// state tests: what selects the path is constant over the run, and the counters move once, after it.  Everything that can
+			// end the run (the frame's next transition, the chunk's last output, a full frame buffer, an equaliser still filling)
+			// is decided here, in front of it, and left to the general iteration.
+			const bool train = s.fr_state == FR_EQ_TRAIN;
+			int n_run = (jstop - j) >> 1;
+			if (n_run > s.symbols_wanted - 1) n_run = s.symbols_wanted - 1;
+			if ((!train || s.eq_full) && (!s.use_data || s.data_n + n_run <= MAX_DATA_SYMBOLS)) {
+				if (s.use_data && staged == 0) stage_at = s.data_slot * MAX_DATA_SYMBOLS + s.data_n;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE >= 2
+				const unsigned long long tR0 = __builtin_amdgcn_s_memtime();
+#endif
+				int ki = 0;
+				for (int i = 0; i < n_run; i++, j += 2) {
+					pair_step(j);
+					const cf y = equalise();
+					if (train) { train_step(y); s.T_idx++; }
+					if (TAPS && lane == 0) io.tap_symbols[nsym] = y;
+					nsym++;
+					ki = (int)__builtin_ctzll(__ballot(cum_l > j + 1));      // the input sample this symbol came from: never before the last one's
+					const float level = lane_value(lv_l, ki);
+					float perr;
+					LaneSlicer{c.px, c.py, lane}(s.cur_arity, y, &perr);
+					const float e = 0.5f * (fabsf(perr + COSTAS_ERR_LIMIT) - fabsf(perr - COSTAS_ERR_LIMIT));      // costas_cccf_adjust, :276-281
+					s.err = e;
+					s.phi += COSTAS_ALPHA * e;
+					s.dphi += COSTAS_BETA * e;
+					if (s.use_data) sh.stage[staged++] = y;
+					else if (s.training_n < T_LEN) {
+						a.training[s.training_n] = y;
+						s.training_n++;
+					}
+					s.signal_level = (s.signal_level * s.frame_symbol_cnt + level) / (s.frame_symbol_cnt + 1.0f);
+					s.frame_symbol_cnt += 1.0f;
+				}
+				if (ki >= kdone) kdone = ki + 1;      // the noise-floor clock stands still outside the search: nothing to catch up with
+				s.eq_count += 2u * (uint32_t)n_run;
+				s.symsync_out_idx += 2u * (uint32_t)n_run;
+				s.symbol_cnt += (uint64_t)n_run;
+				s.symbols_wanted -= n_run;
+				if (s.use_data) s.data_n += n_run;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE >= 2
+				{
+					const unsigned long long dt = HFDL_DM_PROBE == 2 ? __builtin_amdgcn_s_memtime() - tR0 : (unsigned long long)n_run;
+					if (train) c.pb += dt; else c.pc += dt;
+				}
+#endif
+			}
+		}
+	};
+	int j = jbase;
+	if (s.fr_state != FR_A1) in_frame_run(j);
+	while (j < jstop) {
 #ifdef HFDL_DM_PROBE
 		const unsigned long long tA0 = __builtin_amdgcn_s_memtime();
 		const int st0 = s.fr_state;
@@ -452,45 +567,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 		int jo;                                   // the output the rest of the iteration is about
 		bool on_time;
 		if (!(s.symsync_out_idx & 1u) && j + 1 < jstop && !runaway) {
-			// A symbol's two timing-recovery outputs at once, the off-time one in the even lanes and the on-time one in the odd lanes:
-			// one rotation (sin, cos, four products) and one two-lane move of the equaliser window serve both -- the window's newest
-			// entries are lanes 14 (even: the off-time sample) and 15 (odd: the on-time sample) of its row.  Same arithmetic per
-			// output as the single step below; only the carrier phase of each has to be stepped and wrapped on its own.
-			const int sel = ((j - jbase) << 2) + pair_sel;
-			cf oi;
-			oi.x = __int_as_float(__builtin_amdgcn_ds_bpermute(sel, __float_as_int(oq_l.x)));
-			oi.y = __int_as_float(__builtin_amdgcn_ds_bpermute(sel, __float_as_int(oq_l.y)));
-			float ph1, ph2;
-			{
-				const float ph = s.phi + s.dphi;
-				const float dn = ph - (float)(2.0 * M_PI), up = ph + (float)(2.0 * M_PI);
-				ph1 = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
-			}
-			{
-				const float ph = ph1 + s.dphi;
-				const float dn = ph - (float)(2.0 * M_PI), up = ph + (float)(2.0 * M_PI);
-				ph2 = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
-			}
-			s.phi = ph2;
-#ifdef HFDL_DM_LIBM_TRIG
-			float sp, cp;
-			sincosf((lane & 1) ? ph2 : ph1, &sp, &cp);
-#else
-			const float rev = ((lane & 1) ? ph2 : ph1) * 0.15915494309189535f;
-			const float sp = __builtin_amdgcn_sinf(rev), cp = __builtin_amdgcn_cosf(rev);
-#endif
-			cf r;
-			r.x = oi.x * cp + oi.y * sp;
-			r.y = oi.y * cp - oi.x * sp;
-			const float x2n = r.x * r.x + r.y * r.y;
-			const float x2n1 = lane_value(x2n, 0), x2n2 = lane_value(x2n, 1);
-			const float x2o1 = lane_value(c.ex2, 1), x2o2 = lane_value(c.ex2, 2);
-			const float nu = row1 ? r.y : r.x, nv = row1 ? -r.x : r.y;
-			c.eu = dpp_row_shl2(nu, c.eu);
-			c.ev = dpp_row_shl2(nv, c.ev);
-			c.ex2 = dpp_row_shl2(x2n, c.ex2);
-			s.eq_x2sum = s.eq_x2sum + x2n1 - x2o1;
-			s.eq_x2sum = s.eq_x2sum + x2n2 - x2o2;
+			pair_step(j);
 			s.eq_count += 2;
 			jo = j + 1; j += 2; s.symsync_out_idx += 2;
 			on_time = true;
@@ -534,21 +611,11 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 			jo = j; j++; s.symsync_out_idx++;
 		}
 		if (on_time) {
-			// eqlms_cccf_execute, sum conj(w_i) x_i: real part reduced in row 0, imaginary part in row 1, one scan
-			const float p = row_scan_sum(act ? c.ewx * c.eu + c.ewy * c.ev : 0.f);
-			cf y; y.x = lane_value(p, 15); y.y = lane_value(p, 31);
+			const cf y = equalise();
 			if (s.fr_state == FR_EQ_TRAIN) {
-				// eqlms_cccf_step(d = known T symbol, d_hat = y)
 				bool run = true;
 				if (!s.eq_full) { if (s.eq_count < (uint32_t)D_EQ) run = false; else s.eq_full = 1; }
-				if (run) {
-					const float tv = t_symbol(s.T_idx) * ((s.bitmask & 1u) ? -1.0f : 1.0f);
-					const float er = tv - y.x, ei = -(0.0f - y.y);
-					const float bx = row1 ? -c.ev : c.eu, by = row1 ? c.eu : c.ev;       // the window sample (x, y) in either row
-					const float pr = er * bx - ei * by, pi = er * by + ei * bx;
-					c.ewx = c.ewx + EQ_STEP * pr / s.eq_x2sum;
-					c.ewy = c.ewy + EQ_STEP * pi / s.eq_x2sum;
-				}
+				if (run) train_step(y);
 				s.T_idx++;
 			}
 			if (TAPS && lane == 0) io.tap_symbols[nsym] = y;
@@ -650,6 +717,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 				if (j1 < jstop) jstop = j1;
 			}
 		}
+		if (s.fr_state != FR_A1) in_frame_run(j);
 	}
 	if (staged) flush_stage();
 	if (reset_at >= 0) {
