@@ -92,8 +92,33 @@ struct LaunchTimers {
 
 // ---------------------------------------------------------------- front end
 
+// History of finished interval rows (hfdl_gpu_frontend_spectrum_history): a ring of `rows` accumulator sets in HBM.  Row i lives in
+// slot i % rows; the monitor's launch adds every block into the open row's slot (spectrum.h row_acc), so closing a row is host
+// bookkeeping alone: the next launch targets the next slot with its "start over" bit set, which is also how row i + rows takes the
+// slot over from row i.  ev[slot] rides on every launch into the slot: once a row is closed, its slot's event stands for "the row's
+// last launch has run" until the slot is re-targeted.
+struct SpectrumHistory {
+	static constexpr int CHUNK = 8;     // rows a collection copies per wait on its stream
+	int rows = 0, interval = 0;         // interval > 0: a row closes by itself after that many blocks
+	DevBuf acc, peak;                   // [rows][nrx][bins] float2 / float (peak with MAXHOLD)
+	PinnedBuf<float> host;              // bounce buffer of a collection: [CHUNK] x ([bins] float2 + [bins] float)
+	std::vector<Event> ev;              // [rows]
+	std::vector<hfdl_gpu_spectrum_row> info;    // [rows] the closed row each slot holds
+	uint64_t open = 0;                  // index of the open row = rows closed so far
+	uint64_t open_first = 0;            // the open row's first block ...
+	uint32_t open_blocks = 0;           // ... and how many it has so far (0: its slot still holds row open - rows)
+	uint64_t oldest() const { const uint64_t kept = (uint64_t)rows - (open_blocks ? 1 : 0); return open > kept ? open - kept : 0; }
+	void close()
+	{
+		info[open % (uint64_t)rows] = hfdl_gpu_spectrum_row{ open, open_first, open_blocks, 0 };
+		open++;
+		open_blocks = 0;
+	}
+};
+
 // Spectrum monitor (hfdl_gpu_frontend_spectrum_enable; spectrum.h): off = no monitor, no launch.  One launch per step behind the forward
-// FFT's last pass; `ev` rides on that dispatch, so a read waits for the newest launch without a packet of its own on the stream.
+// FFT's last pass.  A dispatch carries ONE stop event: `ev` without the history, the open row's slot event with it -- `last` is the one
+// the newest launch carried, so a read waits for the newest launch without a packet of its own on the stream either way.
 struct SpectrumMonitor {
 	int bins = 0;
 	uint32_t flags = 0;
@@ -101,8 +126,11 @@ struct SpectrumMonitor {
 	DevBuf peak;                        // [nrx][bins] float with MAXHOLD
 	PinnedBuf<float> host;              // bounce buffer of a read: [bins] float2 + [bins] float
 	Event ev;
+	hipEvent_t last = nullptr;          // null: no launch yet, or everything launched has been waited for
+	hipEvent_t newest() const { return last ? last : ev.e; }
 	uint64_t fresh = 0;                 // receivers whose accumulators the next launch overwrites (after enable / a read with reset)
 	std::vector<uint64_t> blocks, first;        // [nrx] blocks accumulated since the receiver's last reset, index of the first of them
+	std::unique_ptr<SpectrumHistory> hist;      // null: no history, no extra allocation, row_acc == nullptr
 };
 
 }  // namespace hfdl

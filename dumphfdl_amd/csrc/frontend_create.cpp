@@ -373,7 +373,7 @@ hfdl_gpu_frontend::~hfdl_gpu_frontend()
 {
 	(void)hipSetDevice(device);
 	for (const hfdl::Stream *s : { &stream, &stream_b, &stream_d, &stream_c, &stream_f, &demod.st_collect }) (void)s->sync();
-	if (mon) (void)hipEventSynchronize(mon->ev);
+	if (mon) (void)hipEventSynchronize(mon->newest());
 }
 
 extern "C" void hfdl_gpu_frontend_destroy(hfdl_gpu_frontend *fe) { delete fe; }

@@ -1,5 +1,6 @@
 // frontend_query.cpp -- what a caller reads from a front end: the error text, geometry, input-done queries, timers, statistics, stage
 // taps, counters, the spectrum monitor; and the page-locked allocator.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -313,8 +314,8 @@ extern "C" int hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t 
 	if (bins > fe->geo.n / 16) return fail(HFDL_GPU_ERANGE, "spectrum bins %d: at most fft_size / 16 = %d", bins, fe->geo.n / 16);
 	HIP_TRY(hipSetDevice(fe->device));
 	// the old monitor's buffers go once nothing queued uses them any more: wait for the monitor launches queued so far, nothing else
-	if (fe->mon) (void)hipEventSynchronize(fe->mon->ev);
-	fe->mon.reset();
+	if (fe->mon) (void)hipEventSynchronize(fe->mon->newest());
+	fe->mon.reset();                       // (and the history of interval rows with it)
 	if (bins == 0) return 0;
 	const size_t nb = (size_t)bins, K = (size_t)fe->nrx;
 	auto mon = std::make_unique<SpectrumMonitor>();
@@ -330,6 +331,12 @@ extern "C" int hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t 
 	mon->first.assign(K, 0);
 	fe->mon = std::move(mon);
 	return 0;
+}
+
+// what the device's Kahan pair becomes on the host, for a read and for a row alike: the compensation holds what the sum has gained too much
+static void mean_of(const float *h, size_t nb, uint64_t T, float *mean)
+{
+	for (size_t b = 0; b < nb; b++) mean[b] = (float)(((double)h[2 * b] - (double)h[2 * b + 1]) / (double)T);
 }
 
 extern "C" int hfdl_gpu_frontend_spectrum_read(hfdl_gpu_frontend *fe, int32_t rx, float *mean, float *peak, int32_t cap,
@@ -351,13 +358,107 @@ extern "C" int hfdl_gpu_frontend_spectrum_read(hfdl_gpu_frontend *fe, int32_t rx
 	const size_t nb = (size_t)mon->bins;
 	float *h = mon->host.p;
 	hipStream_t st = fe->demod.st_collect;
-	HIP_TRY(hipStreamWaitEvent(st, mon->ev, 0));
+	HIP_TRY(hipStreamWaitEvent(st, mon->newest(), 0));
 	HIP_TRY(hipMemcpyAsync(h, mon->acc.as<float2>() + (size_t)rx * nb, sizeof(float2) * nb, hipMemcpyDeviceToHost, st));
 	if (peak) HIP_TRY(hipMemcpyAsync(h + 2 * nb, mon->peak.as<float>() + (size_t)rx * nb, sizeof(float) * nb, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
-	for (size_t b = 0; b < nb; b++)       // Kahan: the compensation holds what the sum has gained too much
-		mean[b] = (float)(((double)h[2 * b] - (double)h[2 * b + 1]) / (double)T);
+	mean_of(h, nb, T, mean);
 	if (peak) memcpy(peak, h + 2 * nb, sizeof(float) * nb);
 	if (reset) mon->fresh |= (uint64_t)1 << rx;
+	return 0;
+}
+
+// ---------------------------------------------------------------- spectrum monitor: history of interval rows
+
+extern "C" int hfdl_gpu_frontend_spectrum_history(hfdl_gpu_frontend *fe, int32_t rows, int32_t interval_blocks)
+{
+	if (rows != 0 && (rows < 2 || rows > HFDL_GPU_SPECTRUM_ROWS_MAX)) return fail(HFDL_GPU_EINVAL, "spectrum history rows %d: 2 .. %d (or 0 = off)", rows, HFDL_GPU_SPECTRUM_ROWS_MAX);
+	if (interval_blocks < 0) return fail(HFDL_GPU_EINVAL, "spectrum history interval of %d blocks", interval_blocks);
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	SpectrumMonitor *mon = fe->mon.get();
+	if (!mon) return fail(HFDL_GPU_EINVAL, "the spectrum monitor is off: hfdl_gpu_frontend_spectrum_enable() first");
+	const size_t set = (size_t)fe->nrx * (size_t)mon->bins, R = (size_t)rows;
+	if (R * set * 12 > ((size_t)1 << 30)) return fail(HFDL_GPU_ERANGE, "spectrum history of %d rows x %d receivers x %d bands: more than 1 GiB", rows, fe->nrx, mon->bins);
+	HIP_TRY(hipSetDevice(fe->device));
+	// the old ring goes once nothing queued writes into it any more: wait for the monitor launches queued so far, nothing else
+	if (mon->hist) {
+		(void)hipEventSynchronize(mon->newest());
+		mon->last = nullptr;
+		mon->hist.reset();
+	}
+	if (rows == 0) return 0;
+	auto h = std::make_unique<SpectrumHistory>();
+	hipError_t e = h->acc.alloc(sizeof(float2) * R * set);
+	if (e == hipSuccess && (mon->flags & HFDL_GPU_SPECTRUM_MAXHOLD)) e = h->peak.alloc(sizeof(float) * R * set);
+	if (e == hipSuccess) e = h->host.alloc((size_t)SpectrumHistory::CHUNK * 3 * (size_t)mon->bins);
+	h->ev.resize(R);
+	for (size_t i = 0; i < R && e == hipSuccess; i++) e = h->ev[i].create(EV_NO_TIMING);
+	if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "spectrum history buffers: %s", hipGetErrorString(e));
+	h->rows = rows;
+	h->interval = interval_blocks;
+	h->info.resize(R);
+	mon->hist = std::move(h);              // the first block opens row 0: "start over" is set, nothing to clear on the device
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_spectrum_row_close(hfdl_gpu_frontend *fe, uint64_t *row)
+{
+	if (!fe || !row) return fail(HFDL_GPU_EINVAL, "null argument");
+	SpectrumHistory *h = fe->mon ? fe->mon->hist.get() : nullptr;
+	if (!h) return fail(HFDL_GPU_EINVAL, "the spectrum history is off: hfdl_gpu_frontend_spectrum_history() first");
+	*row = h->open;
+	if (h->open_blocks) h->close();
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_spectrum_rows(hfdl_gpu_frontend *fe, int32_t rx, uint64_t from_row, int32_t max_rows,
+		float *mean, float *peak, hfdl_gpu_spectrum_row *info, int32_t *n, uint64_t *next_row, int wait)
+{
+	if (!fe || !n || !next_row) return fail(HFDL_GPU_EINVAL, "null argument");
+	SpectrumMonitor *mon = fe->mon.get();
+	SpectrumHistory *h = mon ? mon->hist.get() : nullptr;
+	if (!h) return fail(HFDL_GPU_EINVAL, "the spectrum history is off: hfdl_gpu_frontend_spectrum_history() first");
+	if (rx < 0 || rx >= fe->nrx) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	if (max_rows < 0) return fail(HFDL_GPU_EINVAL, "max_rows %d", max_rows);
+	if (max_rows > 0 && (!mean || !info)) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (peak && !(mon->flags & HFDL_GPU_SPECTRUM_MAXHOLD)) return fail(HFDL_GPU_EINVAL, "peak asked for, but the monitor was enabled without HFDL_GPU_SPECTRUM_MAXHOLD");
+	const uint64_t R = (uint64_t)h->rows;
+	uint64_t from = std::min(std::max(from_row, h->oldest()), h->open);
+	uint64_t end = std::min(h->open, from + (uint64_t)max_rows);
+	*n = 0;
+	*next_row = from;
+	if (end == from) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	// Finished = the slot's event has fired (it rode on the row's last launch).  Launches run in order, so the rows finished are a prefix.
+	if (wait) HIP_TRY(hipEventSynchronize(h->ev[(end - 1) % R]));
+	else for (uint64_t r = from; r < end; r++) {
+		const hipError_t e = hipEventQuery(h->ev[r % R]);
+		if (e == hipSuccess) continue;
+		if (e != hipErrorNotReady) return fail(HFDL_GPU_EHIP, "hipEventQuery: %s", hipGetErrorString(e));
+		(void)hipGetLastError();           // "not yet" is an answer, as in hfdl_gpu_frontend_input_copied()
+		end = r;
+	}
+	// the collection stream has nothing to wait for: it copies beside the kernels in flight, CHUNK rows per wait
+	const size_t nb = (size_t)mon->bins, K = (size_t)fe->nrx;
+	hipStream_t st = fe->demod.st_collect;
+	for (uint64_t r0 = from; r0 < end; r0 += SpectrumHistory::CHUNK) {
+		const size_t cnt = (size_t)std::min<uint64_t>(SpectrumHistory::CHUNK, end - r0);
+		for (size_t i = 0; i < cnt; i++) {
+			const size_t at = ((size_t)((r0 + i) % R) * K + (size_t)rx) * nb;
+			float *hb = h->host.p + i * 3 * nb;
+			HIP_TRY(hipMemcpyAsync(hb, h->acc.as<float2>() + at, sizeof(float2) * nb, hipMemcpyDeviceToHost, st));
+			if (peak) HIP_TRY(hipMemcpyAsync(hb + 2 * nb, h->peak.as<float>() + at, sizeof(float) * nb, hipMemcpyDeviceToHost, st));
+		}
+		HIP_TRY(hipStreamSynchronize(st));
+		for (size_t i = 0; i < cnt; i++) {
+			const size_t o = (size_t)(r0 + i - from);
+			const float *hb = h->host.p + i * 3 * nb;
+			info[o] = h->info[(size_t)((r0 + i) % R)];
+			mean_of(hb, nb, info[o].blocks, mean + o * nb);
+			if (peak) memcpy(peak + o * nb, hb + 2 * nb, sizeof(float) * nb);
+		}
+	}
+	*n = (int32_t)(end - from);
+	*next_row = end;
 	return 0;
 }

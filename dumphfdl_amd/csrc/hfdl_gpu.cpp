@@ -277,10 +277,27 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		m.spec = fe->spec_slot(set, i); m.rx_stride = g.n; m.n = g.n; m.bins = mon->bins; m.nrx = fe->nrx; m.flags = mon->flags;
 		m.scale = (float)(1.0 / ((double)g.n * (double)g.n * ((mon->flags & SPECMON_HANN) ? 0.375 : 1.0)));
 		m.fresh = mon->fresh; m.acc = mon->acc.as<float2>(); m.peak = mon->peak.as<float>();
-		launch_spectrum_monitor(m, fe->stream_f, mon->ev);
+		SpectrumHistory *h = mon->hist.get();
+		hipEvent_t done = mon->ev;
+		if (h) {
+			// The open row's slot is the launch's second target and its event the one this dispatch carries: row i + rows overwrites
+			// the slot of row i in stream order.  One thread drives a front end (include/hfdl_gpu.h), and a collection returns only
+			// when its copies are done, so no copy of a slot is in flight while a push re-targets it.
+			const size_t slot = (size_t)(h->open % (uint64_t)h->rows), set = (size_t)fe->nrx * (size_t)mon->bins;
+			m.row_acc = h->acc.as<float2>() + slot * set;
+			if (mon->flags & SPECMON_MAXHOLD) m.row_peak = h->peak.as<float>() + slot * set;
+			m.row_fresh = h->open_blocks == 0;
+			done = h->ev[slot];
+		}
+		launch_spectrum_monitor(m, fe->stream_f, done);
+		mon->last = done;
 		for (int r = 0; r < fe->nrx; r++) {
 			if ((mon->fresh >> r) & 1) { mon->blocks[(size_t)r] = 0; mon->first[(size_t)r] = fe->blocks; }
 			mon->blocks[(size_t)r]++;
+		}
+		if (h) {
+			if (h->open_blocks++ == 0) h->open_first = fe->blocks;
+			if (h->interval > 0 && h->open_blocks == (uint32_t)h->interval) h->close();
 		}
 		mon->fresh = 0;
 	}

@@ -15,6 +15,10 @@ enum { SPECMON_HANN = 1, SPECMON_MAXHOLD = 2 };           // HFDL_GPU_SPECTRUM_*
 // into acc[r * bins + b] = { sum, compensation } (Kahan) and, with SPECMON_MAXHOLD, max them into peak[r * bins + b].  Receivers whose
 // bit is set in `fresh` start over: their accumulators are overwritten by this block, not added to (no memset is ever queued).
 // The summation order is fixed by (n, bins) alone (spectrum_kernels.hip), so a result is bit-identical from run to run.
+// Interval rows (optional, row_acc != nullptr): the thread that owns a band repeats the Kahan step and the max on row_acc / row_peak,
+// the open row's slot of the history ring, laid out [nrx][bins] like acc / peak, from the same p.  row_fresh is ONE bit for all
+// receivers (a row covers the same blocks of every receiver): set, the slot is overwritten -- that is how a row starts and how a slot
+// of the ring is taken over from the row that held it before.
 struct SpecmonJob {
 	const float2 *spec = nullptr;
 	int64_t rx_stride = 0;
@@ -24,6 +28,9 @@ struct SpecmonJob {
 	uint64_t fresh = 0;
 	float2 *acc = nullptr;
 	float *peak = nullptr;
+	float2 *row_acc = nullptr;
+	float *row_peak = nullptr;
+	uint32_t row_fresh = 0;
 };
 
 // one launch, grid y = receiver; `done` (optional) rides on the dispatch (hipExtLaunchKernelGGL): no barrier packet

@@ -10,7 +10,9 @@
 //   3. G > 512: a workgroup OWNS a band and walks it in G / 512 steps of 512 bins; a thread adds its terms (512 bins apart) up
 //      compensated (Kahan), then the 256 thread sums go through the same tree.  No floating-point atomics anywhere;
 //   4. the band's sum times 1 / (N^2 wpow) is the block's band power; the thread that holds it adds it to the accumulator with a
-//      Kahan step (two floats per band), so the error of the mean does not grow with the number of blocks.
+//      Kahan step (two floats per band), so the error of the mean does not grow with the number of blocks;
+//   5. with an interval row open (SpecmonJob::row_acc), the same thread repeats step 4 from the same p on the row's slot: a row holds
+//      the very words a read-with-reset over the same blocks would, at 8 .. 12 more bytes per band and block and no launch of its own.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "spectrum.h"
@@ -75,6 +77,17 @@ __global__ __launch_bounds__(SPECMON_THREADS) void spectrum_bands(SpecmonJob j)
 	}
 	j.acc[idx] = acc;
 	if (j.flags & SPECMON_MAXHOLD) j.peak[idx] = fresh ? p : fmaxf(j.peak[idx], p);
+	if (j.row_acc == nullptr) return;                             // uniform over the launch: the history is off
+	float2 row = make_float2(p, 0.f);
+	if (!j.row_fresh) {
+		row = j.row_acc[idx];
+		const float y = p - row.y;
+		const float u = row.x + y;
+		row.y = (u - row.x) - y;
+		row.x = u;
+	}
+	j.row_acc[idx] = row;
+	if (j.flags & SPECMON_MAXHOLD) j.row_peak[idx] = j.row_fresh ? p : fmaxf(j.row_peak[idx], p);
 }
 
 void launch_spectrum_monitor(const SpecmonJob &job, hipStream_t st, hipEvent_t done)

@@ -46,6 +46,10 @@ class ChannelStats(C.Structure):
                 ("train_bits_bad", C.c_uint32), ("train_bits_total", C.c_uint32)]
 
 
+class SpectrumRow(C.Structure):
+    _fields_ = [("row", C.c_uint64), ("first_block", C.c_uint64), ("blocks", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class FrontendCounters(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("pdus_taken", C.c_uint32), ("pdus_dropped", C.c_uint32), ("pdu_ring_capacity", C.c_uint32)]
 
@@ -74,12 +78,14 @@ EXPORTS = [
     "hfdl_gpu_last_error", "hfdl_gpu_device_count",
     "hfdl_gpu_frontend_create_multi", "hfdl_gpu_frontend_push_blocks_raw", "hfdl_gpu_frontend_channel_receiver",
     "hfdl_gpu_frontend_spectrum_enable", "hfdl_gpu_frontend_spectrum_read",
+    "hfdl_gpu_frontend_spectrum_history", "hfdl_gpu_frontend_spectrum_row_close", "hfdl_gpu_frontend_spectrum_rows",
 ]
 
 
 FOLD_BATCH_MAX = 32        # HFDL_GPU_FOLD_BATCH_MAX of include/hfdl_gpu.h
 RECEIVERS_MAX = 64         # HFDL_GPU_RECEIVERS_MAX
 SPECTRUM_HANN, SPECTRUM_MAXHOLD = 1, 2     # HFDL_GPU_SPECTRUM_*
+SPECTRUM_ROWS_MAX = 1024   # HFDL_GPU_SPECTRUM_ROWS_MAX
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
@@ -186,6 +192,10 @@ def _bind(L):
     L.hfdl_gpu_frontend_channel_receiver.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.hfdl_gpu_frontend_spectrum_enable.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
     L.hfdl_gpu_frontend_spectrum_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
+    L.hfdl_gpu_frontend_spectrum_history.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.hfdl_gpu_frontend_spectrum_row_close.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.hfdl_gpu_frontend_spectrum_rows.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int]
     return L
 
 
@@ -434,6 +444,7 @@ class Frontend:
         flags = (SPECTRUM_HANN if hann else 0) | (SPECTRUM_MAXHOLD if maxhold else 0)
         _check(self._L.hfdl_gpu_frontend_spectrum_enable(self._h, bins, flags), self._L)
         self._spec_bins, self._spec_peak = int(bins), bool(maxhold)
+        self._spec_rows = 0                    # the library drops the history of interval rows with the old monitor
 
     def spectrum_band_centres(self, rx=0):
         """Centre frequencies in Hz (float64) of the monitor's bands of receiver rx: band b spans centre +- G fs / 2N with
@@ -458,6 +469,38 @@ class Frontend:
         if T.value == 0:
             mean, peak = None, None
         return dict(mean=mean, peak=peak, blocks=T.value, first_block=first.value, freqs=self.spectrum_band_centres(rx))
+
+    def spectrum_history(self, rows, interval_blocks=0):
+        """Keep the newest `rows` (2 .. SPECTRUM_ROWS_MAX) finished interval rows on the device; rows = 0 turns the history off.  A row =
+        mean (and max-hold) over the blocks of one interval, closed by spectrum_row_close() or by itself after interval_blocks blocks.
+        Rows are numbered from 0 at every call; spectrum_enable() drops the history."""
+        _check(self._L.hfdl_gpu_frontend_spectrum_history(self._h, rows, interval_blocks), self._L)
+        self._spec_rows = int(rows)
+
+    def spectrum_row_close(self):
+        """End the open row (host bookkeeping: no device call, no wait); returns its index.  An open row without a block stays open."""
+        row = C.c_uint64(0)
+        _check(self._L.hfdl_gpu_frontend_spectrum_row_close(self._h, C.byref(row)), self._L)
+        return row.value
+
+    def spectrum_rows(self, rx=0, from_row=0, max_rows=None, wait=False):
+        """Finished rows of receiver rx from max(from_row, oldest kept) on: dict(mean [n][bins] float32, peak likewise (None without
+        maxhold), row, first_block, blocks: [n] each, next_row: the from_row of the next call).  wait=False never waits for a kernel
+        stream: only rows whose last launch has run; wait=True waits for every row closed so far.  A row is bit-identical to what
+        spectrum_read(rx, reset=True) returns for the same blocks."""
+        b = self._spec_bins
+        if not b:
+            raise GpuError("the spectrum monitor is off: spectrum_enable() first")
+        cap = getattr(self, "_spec_rows", 0) if max_rows is None else int(max_rows)
+        mean = np.zeros((max(cap, 0), b), np.float32)
+        peak = np.zeros((max(cap, 0), b), np.float32) if self._spec_peak else None
+        info = (SpectrumRow * max(cap, 1))()
+        n, nxt = C.c_int32(0), C.c_uint64(0)
+        _check(self._L.hfdl_gpu_frontend_spectrum_rows(self._h, rx, C.c_uint64(from_row), cap, _p(mean), _p(peak) if peak is not None else None,
+                                                       info, C.byref(n), C.byref(nxt), int(wait)), self._L)
+        k = n.value
+        return dict(mean=mean[:k], peak=peak[:k] if peak is not None else None, row=[info[i].row for i in range(k)],
+                    first_block=[info[i].first_block for i in range(k)], blocks=[info[i].blocks for i in range(k)], next_row=nxt.value)
 
     def close(self):
         if self._h:

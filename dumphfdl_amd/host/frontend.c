@@ -322,6 +322,38 @@ static int release_copied(hfdl_gpu_frontend *fe, struct circ_buffer *ring, size_
  * 20 ms), counted from the arrival of the newest block: a live radio delivers a block every block duration and gets its PDUs within that grace; a file reader that hiccups for
  * a millisecond beside a GPU about as fast as itself never drains a filled pipeline (round 4's fixed 0.5 ms grace did, five times
  * in a run, for 19 % of the rate). */
+/* Rows of the spectrum history the device has finished (wait = 0: never waits for a kernel stream; wait = 1, at the end of a run: every
+ * closed row), one rtl_power line each, in row order, from row `next` on.  Returns the first row not written yet.  A row the ring has
+ * overwritten before it was written is named on stderr. */
+#define SPEC_ROWS (2 * (2 * HFDL_GPU_FOLD_BATCH_MAX + HFDL_GPU_PREFETCH_MAX + 2))
+static uint64_t write_spectrum_rows(hfdl_gpu_frontend *fe, const hfdl_gpu_geometry *geo, double fs, double centerfreq, const struct timeval *t0,
+		FILE *out, float *mean, char *line, int32_t bins, uint64_t next, int wait)
+{
+	const double step = (double)(geo->fft_size / bins) * fs / (double)geo->fft_size;
+	const double low = centerfreq - (0.5 * (double)geo->fft_size + 0.5) * fs / (double)geo->fft_size;
+	for (;;) {
+		hfdl_gpu_spectrum_row info;
+		int32_t n = 0;
+		uint64_t after = next;
+		if (hfdl_gpu_frontend_spectrum_rows(fe, 0, next, 1, mean, NULL, &info, &n, &after, wait) != 0) {
+			fprintf(stderr, "spectrum monitor: %s\n", hfdl_gpu_last_error());
+			return next;
+		}
+		if (n == 0) return after;
+		for (uint64_t lost = next; lost < info.row; lost++)
+			fprintf(stderr, "spectrum monitor: interval %llu has no line: its row was overwritten before it could be written\n", (unsigned long long)lost);
+		/* stamped like the PDUs: wall clock at stream start + the signal time of the first block averaged */
+		const double t = (double)t0->tv_sec + 1e-6 * (double)t0->tv_usec + (double)info.first_block * (double)geo->input_size / fs;
+		if (hfdl_spectrum_csv_line(line, 64 + 12 * (size_t)bins, t, low, step, info.blocks, mean, bins) > 0) {
+			fputs(line, out);
+			fflush(out);
+		} else {
+			fprintf(stderr, "spectrum monitor: interval %llu has no line: it does not fit the line buffer\n", (unsigned long long)info.row);
+		}
+		next = after;
+	}
+}
+
 static void *frontend_thread(void *ctx)
 {
 	struct block *block = ctx;
@@ -352,17 +384,20 @@ static void *frontend_thread(void *ctx)
 	struct timeval t0;
 	gettimeofday(&t0, NULL);
 	const size_t need = ok ? (size_t)fb->geo.input_size : 1;
-	/* spectrum monitor: one CSV line per interval of SIGNAL (blocks pushed x block length / sample rate), read with reset */
+	/* spectrum monitor: one CSV line per interval of SIGNAL (blocks pushed x block length / sample rate): a row of the device's history */
 	FILE *spec_file = NULL;
 	float *spec_mean = NULL;
 	char *spec_line = NULL;
 	int32_t spec_bins = 0;
-	uint64_t spec_lines = 0;
+	uint64_t spec_closed = 0, spec_next = 0;     /* intervals closed so far; the first row not written yet */
 	if (ok && fb->spec_path != NULL) {
 		spec_bins = fb->spec_bins;
 		while (spec_bins > fb->geo.fft_size / 16) spec_bins /= 2;
 		spec_file = fopen(fb->spec_path, "w");       /* a run writes its own file: nothing of an earlier run stays in front of it */
-		if (spec_file == NULL || hfdl_gpu_frontend_spectrum_enable(fe, spec_bins, fb->spec_hann ? HFDL_GPU_SPECTRUM_HANN : 0u) != 0) {
+		/* the ring holds what can be pushed before a closed row's launch has run and this thread has looked again: the blocks of two
+		 * halves and the uploads ahead of them, were every one of them a row of its own, and as many again */
+		if (spec_file == NULL || hfdl_gpu_frontend_spectrum_enable(fe, spec_bins, fb->spec_hann ? HFDL_GPU_SPECTRUM_HANN : 0u) != 0
+				|| hfdl_gpu_frontend_spectrum_history(fe, SPEC_ROWS, 0) != 0) {
 			fprintf(stderr, "spectrum monitor: %s\n", spec_file ? hfdl_gpu_last_error() : "cannot open the spectrum file");
 			if (spec_file) fclose(spec_file);
 			spec_file = NULL;
@@ -506,24 +541,14 @@ static void *frontend_thread(void *ctx)
 			leased++;
 		}
 		if (spec_file != NULL) {
-			const double fs = (double)slots[0]->sample_rate, step = (double)(fb->geo.fft_size / spec_bins) * fs / (double)fb->geo.fft_size;
-			if ((double)k * (double)need / fs >= (double)(spec_lines + 1) * (double)fb->spec_interval_s) {
-				uint64_t T = 0, first = 0;
-				const int rrc = hfdl_gpu_frontend_spectrum_read(fe, 0, spec_mean, NULL, spec_bins, &T, &first, 1);
-				if (rrc != 0) fprintf(stderr, "spectrum monitor: interval %llu has no line: %s\n", (unsigned long long)spec_lines, hfdl_gpu_last_error());
-				if (rrc == 0 && T > 0) {
-					/* stamped like the PDUs: wall clock at stream start + the signal time of the first block averaged */
-					const double t = (double)t0.tv_sec + 1e-6 * (double)t0.tv_usec + (double)first * (double)need / fs;
-					const double low = (double)slots[0]->centerfreq - (0.5 * (double)fb->geo.fft_size + 0.5) * fs / (double)fb->geo.fft_size;
-					if (hfdl_spectrum_csv_line(spec_line, 64 + 12 * (size_t)spec_bins, t, low, step, T, spec_mean, spec_bins) > 0) {
-						fputs(spec_line, spec_file);
-						fflush(spec_file);
-					} else {
-						fprintf(stderr, "spectrum monitor: interval %llu has no line: it does not fit the line buffer\n", (unsigned long long)spec_lines);
-					}
-				}
-				spec_lines++;
+			/* an interval boundary closes the open row (no device call); finished rows are written as they are found, without waiting */
+			if ((double)k * (double)need / (double)slots[0]->sample_rate >= (double)(spec_closed + 1) * (double)fb->spec_interval_s) {
+				uint64_t row = 0;
+				if (hfdl_gpu_frontend_spectrum_row_close(fe, &row) != 0)
+					fprintf(stderr, "spectrum monitor: interval %llu has no line: %s\n", (unsigned long long)spec_closed, hfdl_gpu_last_error());
+				spec_closed++;
 			}
+			spec_next = write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 0);
 		}
 		const double tw2 = now_s();
 		s_push += tw2 - tw1;
@@ -559,6 +584,7 @@ shutdown:
 			npdus += (uint64_t)n;
 		} while (n == max_pdus);
 		t_last = now_s();
+		if (spec_file != NULL) (void)write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 1);
 		publish_counters(fe, stats, (int32_t)nch);
 		pthread_mutex_lock(&g_run_lock);
 		g_run.blocks = k; g_run.samples = k * (uint64_t)need; g_run.pdus = npdus;

@@ -304,6 +304,51 @@ int  hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t bins, uint
 int  hfdl_gpu_frontend_spectrum_read(hfdl_gpu_frontend *fe, int32_t rx, float *mean, float *peak, int32_t cap,
 		uint64_t *blocks, uint64_t *first_block, int reset);
 
+/* History of interval rows (off by default; needs the monitor on): the device keeps the newest `rows` finished rows, a row being the
+ * mean (and, with MAXHOLD, the max-hold) over the blocks of one interval -- what a waterfall or an rtl_power line is made of.  The
+ * caller closes intervals with a call that touches no device and collects finished rows whenever it likes, with a read that never
+ * waits for a kernel stream; an interval is not lost because it was not read at its boundary.  There is no copy on the device: the
+ * monitor's launch adds every block's band powers into the open row's slot of a ring in HBM as well as into the accumulators of
+ * hfdl_gpu_frontend_spectrum_read() (8 .. 12 more bytes per band and block, no launch of its own), and closing a row moves a host
+ * index: the next block starts the next slot over.
+ *   Rows are numbered from 0 at every hfdl_gpu_frontend_spectrum_history() call; row i covers the blocks pushed between close i - 1
+ *   and close i ("block" as for the monitor: channelize_block counts, push_baseband does not), the same blocks for every receiver.
+ *   A row's mean and peak are BIT-IDENTICAL to what hfdl_gpu_frontend_spectrum_read(rx, reset = 1) returns for the same blocks: the
+ *   same compensated sums on the device, the same division on the host.
+ *   The two are independent: spectrum_read() and its per-receiver reset behave exactly as without the history, closing a row does
+ *   not touch the read's accumulators, a read's reset does not touch the open row.
+ *   A row is finished when the monitor launch of its last block has run.  Row i + rows overwrites row i from its first block on; a
+ *   row overwritten before it was collected is gone, and the caller sees it by info[0].row > from_row -- nothing fails.
+ *   hfdl_gpu_frontend_spectrum_enable() called again (bins = 0 included) drops the history: call spectrum_history() again after it.
+ * One thread drives a front end, as everywhere in this header: no collection runs while a push re-targets a slot. */
+#define HFDL_GPU_SPECTRUM_ROWS_MAX 1024
+typedef struct {
+	uint64_t row;                    /* index of the row */
+	uint64_t first_block;            /* its first block, in the numbering of hfdl_gpu_frontend_counters().blocks */
+	uint32_t blocks;                 /* T: the blocks it covers (>= 1) */
+	uint32_t pad;
+} hfdl_gpu_spectrum_row;
+/* rows = 0: history off, its buffers freed.  rows = 2 .. HFDL_GPU_SPECTRUM_ROWS_MAX: keep the newest `rows` rows (the newest rows - 1
+ * once the open row has a block: it lives in the ring too).  interval_blocks > 0: a row closes by itself after that many blocks;
+ * 0: only hfdl_gpu_frontend_spectrum_row_close() closes rows.  Calling it again starts over at row 0 with an empty ring (it waits for
+ * the monitor launches queued so far before the old ring goes).  HFDL_GPU_EINVAL (rows outside 0, 2 .. 1024, interval_blocks < 0,
+ * null handle, monitor off) / HFDL_GPU_ERANGE (rows x receivers x bins x 12 bytes above 1 GiB) are checked before any device work;
+ * HFDL_GPU_ENOMEM leaves the history off and the monitor as it was. */
+int  hfdl_gpu_frontend_spectrum_history(hfdl_gpu_frontend *fe, int32_t rows, int32_t interval_blocks);
+/* End the open row: host bookkeeping only, no device call, no wait.  *row = the open row's index, which is the index of the row this
+ * call finishes.  An open row without a block stays open: the call makes no row, and the next close returns the same index. */
+int  hfdl_gpu_frontend_spectrum_row_close(hfdl_gpu_frontend *fe, uint64_t *row);
+/* Consecutive finished rows of receiver rx from max(from_row, oldest row kept) on, at most max_rows of them: mean[i * bins + b], peak
+ * likewise (may be NULL; HFDL_GPU_EINVAL if asked for without MAXHOLD) and info[i] of the i-th row returned; *n = rows written,
+ * *next_row = what to pass as from_row next time.  max_rows = 0 writes nothing and reports *next_row, *n = 0.
+ * wait = 0: only rows whose last launch has already run -- the call asks (hipEventQuery) and never waits for a kernel stream; the open
+ * row and closed rows still in flight come with a later call.  wait != 0: waits for every closed row it returns (like
+ * spectrum_read(), for the device to catch up to that row's last block).  The rows are copied on the collection stream through a
+ * page-locked buffer beside the kernels in flight; the call returns when that copy is done.  HFDL_GPU_EINVAL (null handle, n or
+ * next_row, history off, rx out of range, max_rows < 0, mean or info null with max_rows > 0) is checked before any device work. */
+int  hfdl_gpu_frontend_spectrum_rows(hfdl_gpu_frontend *fe, int32_t rx, uint64_t from_row, int32_t max_rows,
+		float *mean, float *peak, hfdl_gpu_spectrum_row *info, int32_t *n, uint64_t *next_row, int wait);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */
