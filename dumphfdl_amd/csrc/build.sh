@@ -30,6 +30,9 @@ for o in $SHIM_OBJS; do
 done
 for p in $pids; do wait $p; done          # set -e: a failed compile stops the build here instead of linking stale objects
 # -Bsymbolic: calls between the library's own entry points stay inside THIS library when the product and the laboratory build
-# are loaded into one process
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUT $objs
+# are loaded into one process.  The product library is linked without a static symbol table (-s; the dynamic one, which is what a
+# caller binds to, stays): a change to the link alone, every object file is what it was.  The laboratory build keeps its table for
+# profiles and backtraces.
+[ "$1" = "lab" ] && STRIP= || STRIP=-Wl,-s
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic $STRIP -o $OUT $objs
 echo "built $(readlink -f $OUT)"

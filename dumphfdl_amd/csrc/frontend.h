@@ -13,6 +13,7 @@
 #include "planner.h"
 #include "demod.h"
 #include "spectrum.h"
+#include "export_ring.h"
 
 namespace hfdl {
 
@@ -133,6 +134,23 @@ struct SpectrumMonitor {
 	std::unique_ptr<SpectrumHistory> hist;      // null: no history, no extra allocation, row_acc == nullptr
 };
 
+// Channel baseband export (hfdl_gpu_frontend_export_enable): off = none, no launch.  One launch per closed half on stream A, behind the
+// half's inverse FFT / NCO launch, packs the selected channels' rows of the half's blocks into a ring in HBM (spectrum.h ExportJob);
+// block b lives in slot b % R.  ev[i] rides on the dispatch of the launch on record i (export_ring.h), so "has block b been written"
+// is a hipEventQuery and a collection never waits for a kernel stream.
+struct ChannelExport {
+	int nsel = 0, format = 0;
+	float scale = 1.f;
+	ExportRing ring;
+	DevBuf channels;                    // [nsel] int32
+	DevBuf samples, counts, power, clipped;     // [R][nsel][P] float2 / short2; [R][nsel] int32 / float / uint32
+	size_t chunk = 1;                   // blocks a collection copies per wait on its stream
+	PinnedBuf<char> host;               // its bounce buffer: [chunk] samples, then [chunk] counts, power, clipped
+	std::vector<Event> ev;              // [R]
+	std::vector<uint64_t> last_of;      // [R] last block of the launch on each record
+	hipEvent_t newest = nullptr;        // what the newest launch carried (null: no launch yet)
+};
+
 }  // namespace hfdl
 
 // Members are destroyed in reverse order of declaration: events first, then memory, then the streams (the destructor has synchronised
@@ -188,6 +206,7 @@ struct hfdl_gpu_frontend {
 	hfdl::NcoState *d_nco_snap = nullptr;     // [half_blocks][nch] the state each block of the half starts from
 	float2 *d_ph = nullptr, *d_ph_cont = nullptr;      // [half_blocks] NCO phasor tables [outs][nch] and the riders' segment hand-over [nch]
 	std::unique_ptr<hfdl::SpectrumMonitor> mon;        // null: off
+	std::unique_ptr<hfdl::ChannelExport> exp;          // null: off
 
 	// ---- events
 	// demodulator launch j of the half in buffer 0 / 1 done (the decoder may start), the LAST launch of the half at [0]: chan_out is free

@@ -462,3 +462,92 @@ extern "C" int hfdl_gpu_frontend_spectrum_rows(hfdl_gpu_frontend *fe, int32_t rx
 	*next_row = end;
 	return 0;
 }
+
+// ---------------------------------------------------------------- channel baseband export
+
+static_assert(HFDL_GPU_EXPORT_CF32 == EXPORT_CF32 && HFDL_GPU_EXPORT_CS16 == EXPORT_CS16, "include/hfdl_gpu.h and spectrum.h name the same formats");
+
+extern "C" int hfdl_gpu_frontend_export_enable(hfdl_gpu_frontend *fe, const int32_t *channels, int32_t nsel, int format, float scale, int32_t ring_blocks)
+{
+	if (!fe || (!channels && nsel > 0)) return fail(HFDL_GPU_EINVAL, "null argument");
+	const size_t S = (size_t)nsel, R = (size_t)ring_blocks, P = (size_t)fe->geo.outs - 1;
+	const size_t es = format == HFDL_GPU_EXPORT_CS16 ? sizeof(short2) : sizeof(float2);
+	if (nsel > 0) {
+		bool ok = nsel <= fe->geo.nch && (format == HFDL_GPU_EXPORT_CF32 || format == HFDL_GPU_EXPORT_CS16) && ring_blocks >= 2 && ring_blocks <= HFDL_GPU_EXPORT_RING_MAX
+			&& (format == HFDL_GPU_EXPORT_CF32 || (scale > 0.f && scale <= 3.402823466e38f));
+		std::vector<bool> seen((size_t)fe->geo.nch);
+		for (size_t i = 0; ok && i < S; i++) {
+			ok = channels[i] >= 0 && channels[i] < fe->geo.nch && !seen[(size_t)channels[i]];
+			if (ok) seen[(size_t)channels[i]] = true;
+		}
+		if (!ok) return fail(HFDL_GPU_EINVAL, "export: bad channels, format, scale or ring");
+		if (R * S * (P * es + 12) > ((size_t)1 << 30)) return fail(HFDL_GPU_ERANGE, "export ring above 1 GiB");
+	} else if (nsel < 0) return fail(HFDL_GPU_EINVAL, "export: nsel %d", nsel);
+	HIP_TRY(hipSetDevice(fe->device));
+	std::unique_ptr<ChannelExport> x;
+	if (nsel > 0) {
+		x = std::make_unique<ChannelExport>();
+		// a collection copies up to 4 MiB of samples per wait on its stream, a block at least
+		x->chunk = std::max<size_t>(1, std::min(R, ((size_t)4 << 20) / (S * P * es)));
+		hipError_t e = x->channels.alloc(sizeof(int32_t) * S);
+		if (e == hipSuccess) e = x->samples.alloc(R * S * P * es);
+		if (e == hipSuccess) e = x->counts.alloc(R * S * 4);
+		if (e == hipSuccess) e = x->power.alloc(R * S * 4);
+		if (e == hipSuccess) e = x->clipped.alloc(R * S * 4);
+		if (e == hipSuccess) e = x->host.alloc(x->chunk * S * (P * es + 12));
+		x->ev.resize(R);
+		for (size_t i = 0; i < R && e == hipSuccess; i++) e = x->ev[i].create(EV_NO_TIMING);
+		if (e == hipSuccess) e = hipMemcpy(x->channels.p, channels, sizeof(int32_t) * S, hipMemcpyHostToDevice);
+		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "export buffers: %s", hipGetErrorString(e));
+		x->nsel = nsel; x->format = format; x->scale = scale;
+		x->last_of.resize(R);
+		x->ring.start((uint32_t)ring_blocks, fe->blocks);      // a block waiting in the half being filled is older: the hook leaves it out
+	}
+	// the old ring goes once nothing queued writes into it any more: wait for the export launches queued so far, nothing else
+	if (fe->exp && fe->exp->newest) (void)hipEventSynchronize(fe->exp->newest);
+	fe->exp = std::move(x);
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_export_read(hfdl_gpu_frontend *fe, uint64_t from_block, int32_t max_blocks, void *samples, int32_t *counts,
+		float *power, uint32_t *clipped, hfdl_gpu_export_block *info, int32_t *n, uint64_t *next_block, int wait)
+{
+	if (!fe || !n || !next_block) return fail(HFDL_GPU_EINVAL, "null argument");
+	ChannelExport *x = fe->exp.get();
+	if (!x || max_blocks < 0 || (max_blocks > 0 && (!samples || !counts || !info))) return fail(HFDL_GPU_EINVAL, "export off, or bad arguments");
+	HIP_TRY(hipSetDevice(fe->device));
+	ExportRing &ring = x->ring;
+	// Finished = the event that rode on the block's launch has fired.  wait: for the newest launch queued -- nothing is closed for it.
+	if (wait && x->newest) HIP_TRY(hipEventSynchronize(x->newest));
+	hipError_t bad = hipSuccess;
+	ring.settle(x->last_of.data(), [&](uint32_t at) {
+		const hipError_t e = hipEventQuery(x->ev[at]);
+		if (e == hipSuccess) return true;
+		if (e == hipErrorNotReady) (void)hipGetLastError(); else bad = e;       // "not yet" is an answer, as in hfdl_gpu_frontend_input_copied()
+		return false;
+	});
+	if (bad != hipSuccess) return fail(HFDL_GPU_EHIP, "hipEventQuery: %s", hipGetErrorString(bad));
+	uint64_t from = 0, end = 0;
+	ring.range(from_block, (uint64_t)max_blocks, from, end);
+	// the collection stream has nothing to wait for: it copies beside the kernels in flight, a run of consecutive slots per wait
+	const size_t S = (size_t)x->nsel, row = S * ((size_t)fe->geo.outs - 1) * (x->format == HFDL_GPU_EXPORT_CS16 ? sizeof(short2) : sizeof(float2));
+	hipStream_t st = fe->demod.st_collect;
+	for (uint64_t b = from, run = 0; b < end; b += run) {
+		const size_t slot = ring.slot(b), o = (size_t)(b - from);
+		run = std::min<uint64_t>(std::min<uint64_t>(x->chunk, end - b), ring.R - slot);
+		char *h = x->host.p, *meta = h + x->chunk * row;
+		const void *src[3] = { x->counts.p, power ? x->power.p : nullptr, clipped ? x->clipped.p : nullptr };
+		void *dst[3] = { counts + o * S, power ? power + o * S : nullptr, clipped ? clipped + o * S : nullptr };
+		HIP_TRY(hipMemcpyAsync(h, (const char *)x->samples.p + slot * row, run * row, hipMemcpyDeviceToHost, st));
+		for (int k = 0; k < 3; k++)
+			if (src[k]) HIP_TRY(hipMemcpyAsync(meta + k * x->chunk * S * 4, (const char *)src[k] + slot * S * 4, run * S * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		memcpy((char *)samples + o * row, h, run * row);
+		for (int k = 0; k < 3; k++)
+			if (src[k]) memcpy(dst[k], meta + k * x->chunk * S * 4, run * S * 4);
+		for (uint64_t i = 0; i < run; i++) info[o + i].block = b + i;
+	}
+	*n = (int32_t)(end - from);
+	*next_block = end;
+	return 0;
+}

@@ -348,6 +348,20 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	if (int rc = fe->timers.arm(ST_IFFT, nblk, fe->chan[half], ifft_start)) return rc;
 	launch_ifft_nco(g, fe->d_partial, fe->partial_stride(), fe->d_cc, fe->snap_slot(half, 0), fe->ph_slot(half, 0), fe->ph_stride(), fe->d_tw_m,
 			fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, fe->stream, fe->chan[half].event(), ifft_start);
+	if (ChannelExport *x = fe->exp.get()) {
+		// the channel export: one launch behind the inverse FFT, whose timed pair and done event stay where they are.  Stream order alone
+		// makes its read safe: the next inverse FFT into this half is behind it on this stream.  The half's blocks are the newest nblk.
+		const uint32_t skip = x->ring.skip_of_half(fe->blocks - (uint64_t)nblk, (uint32_t)nblk);
+		if (skip < (uint32_t)nblk) {
+			ExportJob e;
+			e.chan = fe->chan_slot(slot0 + (int)skip); e.cnt = fe->cnt_slot(slot0 + (int)skip); e.channels = x->channels.as<int32_t>();
+			e.nch = g.nch; e.outs = g.outs; e.P = g.outs - 1; e.nsel = x->nsel; e.nblk = nblk - (int)skip; e.format = x->format; e.scale = x->scale;
+			e.slot0 = x->ring.slot(fe->blocks - (uint64_t)e.nblk); e.R = x->ring.R;
+			e.samples = x->samples.p; e.counts = x->counts.as<int32_t>(); e.power = x->power.as<float>(); e.clipped = x->clipped.as<uint32_t>();
+			x->newest = x->ev[x->ring.push_launch(x->last_of.data(), fe->blocks - 1)];
+			launch_export_pack(e, fe->stream, x->newest);
+		}
+	}
 	HIP_TRY(hipGetLastError());
 	fe->last_slot = slot0 + nblk - 1;
 	fe->last_index = nblk - 1;

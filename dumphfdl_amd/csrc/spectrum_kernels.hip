@@ -1,4 +1,5 @@
-// spectrum_kernels.hip -- the spectrum monitor: band powers of the spectra the forward FFT leaves in HBM (gfx950).
+// spectrum_kernels.hip -- the spectrum monitor: band powers of the spectra the forward FFT leaves in HBM (gfx950); and, at the end of
+// the file, the channel export's packing kernel.
 //
 // HBM-bound: a step reads nrx * N * 8 bytes once, in 16-byte loads (two bins per thread), and touches nrx * bins * 8 .. 12 bytes of
 // accumulators.  Compiled without FMA contraction (build.sh), so the arithmetic below is what tests/spectrum_f64.py emulates in fp32.
@@ -96,6 +97,76 @@ void launch_spectrum_monitor(const SpecmonJob &job, hipStream_t st, hipEvent_t d
 	const dim3 grid(g > SPECMON_TILE ? job.bins : job.n / SPECMON_TILE, job.nrx);
 	if (job.flags & SPECMON_HANN) hipExtLaunchKernelGGL(spectrum_bands<true>, grid, dim3(SPECMON_THREADS), 0, st, nullptr, done, 0, job);
 	else hipExtLaunchKernelGGL(spectrum_bands<false>, grid, dim3(SPECMON_THREADS), 0, st, nullptr, done, 0, job);
+}
+
+// ---------------------------------------------------------------- channel baseband export
+//
+// 256 threads per (selected channel, block).  Copy / convert P samples, and the row's mean power in a fixed order:
+//   1. a term is (re re) + (im im);
+//   2. thread t adds its terms i = t, t + 256, ... < n one after the other, starting from 0.0f;
+//   3. the xor butterfly over the 64 lanes (masks 1, 2, .. 32): a binary tree over adjacent lanes;
+//   4. the four wave sums pairwise through LDS, (w0 + w1) + (w2 + w3);
+//   5. one division by (float)n.
+// No floating-point atomics; plain vector stores only.
+
+// one component as int16: one fp32 multiply, round half to even, clamp to +-32767; NaN is tested for itself and stores 0
+static __device__ __forceinline__ short export_cs16(float v, float scale, uint32_t &clip)
+{
+	if (v != v) { clip++; return 0; }
+	const float r = rintf(v * scale);
+	if (r > 32767.f) { clip++; return 32767; }
+	if (r < -32767.f) { clip++; return -32767; }
+	return (short)(int)r;
+}
+
+template <bool CS16>
+__global__ __launch_bounds__(EXPORT_THREADS) void export_pack_kernel(ExportJob j)
+{
+	__shared__ float wsum[EXPORT_THREADS / 64];
+	__shared__ uint32_t wclip[EXPORT_THREADS / 64];
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	const int s = blockIdx.x, b = blockIdx.y;
+	const int c = j.channels[s];
+	const size_t in_row = (size_t)b * (size_t)j.nch + (size_t)c;
+	const int P = j.P;
+	const int n = min(max(j.cnt[in_row], 0), P);
+	const float2 *__restrict__ x = j.chan + in_row * (size_t)j.outs;
+	const size_t row = (size_t)((j.slot0 + (uint32_t)b) % j.R) * (size_t)j.nsel + (size_t)s;
+	float acc = 0.0f;
+	uint32_t clip = 0;
+	for (int i = t; i < P; i += EXPORT_THREADS) {
+		float2 v = make_float2(0.0f, 0.0f);
+		if (i < n) {
+			v = x[i];
+			acc = acc + ((v.x * v.x) + (v.y * v.y));
+		}
+		if (CS16) {
+			short2 q;
+			q.x = export_cs16(v.x, j.scale, clip);
+			q.y = export_cs16(v.y, j.scale, clip);
+			static_cast<short2 *>(j.samples)[row * (size_t)P + (size_t)i] = q;
+		} else {
+			static_cast<float2 *>(j.samples)[row * (size_t)P + (size_t)i] = v;
+		}
+	}
+	for (int o = 1; o < 64; o <<= 1) {
+		acc += __shfl_xor(acc, o);
+		if (CS16) clip += __shfl_xor(clip, o);
+	}
+	if (lane == 0) { wsum[wave] = acc; wclip[wave] = clip; }
+	__syncthreads();
+	if (t != 0) return;
+	const float p = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+	j.counts[row] = n;
+	j.power[row] = n ? p / (float)n : 0.0f;
+	j.clipped[row] = CS16 ? (wclip[0] + wclip[1]) + (wclip[2] + wclip[3]) : 0u;
+}
+
+void launch_export_pack(const ExportJob &job, hipStream_t st, hipEvent_t done)
+{
+	const dim3 grid(job.nsel, job.nblk);
+	if (job.format == EXPORT_CS16) hipExtLaunchKernelGGL(export_pack_kernel<true>, grid, dim3(EXPORT_THREADS), 0, st, nullptr, done, 0, job);
+	else hipExtLaunchKernelGGL(export_pack_kernel<false>, grid, dim3(EXPORT_THREADS), 0, st, nullptr, done, 0, job);
 }
 
 }  // namespace hfdl

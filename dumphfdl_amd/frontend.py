@@ -79,6 +79,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_create_multi", "hfdl_gpu_frontend_push_blocks_raw", "hfdl_gpu_frontend_channel_receiver",
     "hfdl_gpu_frontend_spectrum_enable", "hfdl_gpu_frontend_spectrum_read",
     "hfdl_gpu_frontend_spectrum_history", "hfdl_gpu_frontend_spectrum_row_close", "hfdl_gpu_frontend_spectrum_rows",
+    "hfdl_gpu_frontend_export_enable", "hfdl_gpu_frontend_export_read",
 ]
 
 
@@ -86,6 +87,8 @@ FOLD_BATCH_MAX = 32        # HFDL_GPU_FOLD_BATCH_MAX of include/hfdl_gpu.h
 RECEIVERS_MAX = 64         # HFDL_GPU_RECEIVERS_MAX
 SPECTRUM_HANN, SPECTRUM_MAXHOLD = 1, 2     # HFDL_GPU_SPECTRUM_*
 SPECTRUM_ROWS_MAX = 1024   # HFDL_GPU_SPECTRUM_ROWS_MAX
+EXPORT_CF32, EXPORT_CS16 = 0, 1            # HFDL_GPU_EXPORT_*
+EXPORT_RING_MAX = 4096     # HFDL_GPU_EXPORT_RING_MAX
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
@@ -196,6 +199,9 @@ def _bind(L):
     L.hfdl_gpu_frontend_spectrum_row_close.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.hfdl_gpu_frontend_spectrum_rows.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int]
+    L.hfdl_gpu_frontend_export_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_int32]
+    L.hfdl_gpu_frontend_export_read.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int]
     return L
 
 
@@ -501,6 +507,34 @@ class Frontend:
         k = n.value
         return dict(mean=mean[:k], peak=peak[:k] if peak is not None else None, row=[info[i].row for i in range(k)],
                     first_block=[info[i].first_block for i in range(k)], blocks=[info[i].blocks for i in range(k)], next_row=nxt.value)
+
+    def export_enable(self, channels, fmt="cf32", scale=1.0, ring_blocks=64):
+        """Channel baseband export (include/hfdl_gpu.h): from the next pushed block on, the device keeps the newest `ring_blocks`
+        (2 .. EXPORT_RING_MAX) blocks of the channelizer's output of `channels` (distinct global indices; their order is the order of the
+        exported rows).  fmt "cf32", or "cs16" = int16 of rint(v * scale).  No channels: off.  Calling it again starts over."""
+        ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+        f = {"cf32": EXPORT_CF32, "cs16": EXPORT_CS16}.get(fmt, fmt)
+        _check(self._L.hfdl_gpu_frontend_export_enable(self._h, _p(ch) if len(ch) else None, len(ch), f, scale, ring_blocks), self._L)
+        self._export = (len(ch), f, int(ring_blocks))
+
+    def export_read(self, from_block=0, max_blocks=None, wait=False):
+        """Finished blocks of the export from max(from_block, oldest kept) on: (samples [n, nsel, P] complex64 -- or int16 [n, nsel, P, 2]
+        for cs16 --, counts [n, nsel] int32 valid samples of each row, power [n, nsel] float32, clipped [n, nsel] uint32, blocks [n]
+        their indices, next_block: the from_block of the next call).  wait=False never waits for a kernel stream: only blocks whose
+        launch has run; wait=True waits for the newest export launch queued and closes nothing (blocks of an open half come later)."""
+        nsel, f, ring = getattr(self, "_export", (0, 0, 0))
+        if not nsel:
+            raise GpuError("the channel export is off: export_enable() first")
+        cap = ring if max_blocks is None else int(max_blocks)
+        k, P = max(cap, 0), self.geometry.max_outputs_per_block
+        samples = np.zeros((k, nsel, P, 2), np.int16) if f == EXPORT_CS16 else np.zeros((k, nsel, P), np.complex64)
+        counts, power, clipped = np.zeros((k, nsel), np.int32), np.zeros((k, nsel), np.float32), np.zeros((k, nsel), np.uint32)
+        info = np.zeros(max(k, 1), np.uint64)
+        n, nxt = C.c_int32(0), C.c_uint64(0)
+        _check(self._L.hfdl_gpu_frontend_export_read(self._h, C.c_uint64(from_block), cap, _p(samples), _p(counts), _p(power), _p(clipped), _p(info),
+                                                     C.byref(n), C.byref(nxt), int(wait)), self._L)
+        m = n.value
+        return samples[:m], counts[:m], power[:m], clipped[:m], [int(b) for b in info[:m]], nxt.value
 
     def close(self):
         if self._h:

@@ -23,6 +23,10 @@ struct gpu_fft_block {
 	char *spec_path;                 /* spectrum monitor as set when fft_create() ran (hfdl_frontend_set_spectrum); NULL = off */
 	int32_t spec_bins, spec_interval_s;
 	int spec_hann;
+	char *iqx_dir;                   /* channel baseband export as set when fft_create() ran (hfdl_frontend_set_iq_export); NULL = off */
+	int32_t *iqx_freqs, iqx_nfreqs;
+	int iqx_format;
+	float iqx_scale;
 };
 
 static int g_device = 0;
@@ -36,6 +40,26 @@ int hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t interval_
 	free(g_spectrum.path);
 	g_spectrum.path = path ? strdup(path) : NULL;
 	g_spectrum.bins = bins; g_spectrum.interval_s = interval_s; g_spectrum.hann = hann;
+	return 0;
+}
+
+/* channel baseband export of the next front end (hfdl_frontend_set_iq_export): dir NULL = off */
+static struct { char *dir; int32_t *freqs, nfreqs; int format; float scale; } g_iqx;
+static int32_t *copy_freqs(const int32_t *freqs, int32_t n)
+{
+	int32_t *c = hfdl_xcalloc(n > 0 ? (size_t)n : 1, sizeof(int32_t));
+	if (n > 0) memcpy(c, freqs, (size_t)n * sizeof(int32_t));
+	return c;
+}
+int hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t nfreqs, int format, float scale)
+{
+	if (dir != NULL && (nfreqs < 0 || (nfreqs > 0 && freqs == NULL) || (format != HFDL_GPU_EXPORT_CF32 && format != HFDL_GPU_EXPORT_CS16)
+			|| (format == HFDL_GPU_EXPORT_CS16 && !(scale > 0.f && isfinite(scale))))) return -1;
+	free(g_iqx.dir);
+	free(g_iqx.freqs);
+	g_iqx.dir = dir ? strdup(dir) : NULL;
+	g_iqx.freqs = dir ? copy_freqs(freqs, nfreqs) : NULL;
+	g_iqx.nfreqs = dir ? nfreqs : 0; g_iqx.format = format; g_iqx.scale = scale;
 	return 0;
 }
 
@@ -354,6 +378,92 @@ static uint64_t write_spectrum_rows(hfdl_gpu_frontend *fe, const hfdl_gpu_geomet
 	}
 }
 
+/* Channel baseband export: one file per selected channel; finished blocks are collected IQX_CHUNK at a time (wait = 0: never waits for
+ * a kernel stream; wait = 1, at the end of a run: everything queued) and each block's valid samples appended to its channel's file. */
+#define IQX_CHUNK 4
+struct iq_export {
+	int32_t nsel, row;               /* selected channels; samples a row holds (geometry.max_outputs_per_block) */
+	size_t es;                       /* bytes per sample */
+	FILE **files;
+	char *samples;
+	int32_t *counts;
+	hfdl_gpu_export_block info[IQX_CHUNK];
+	uint64_t next;                   /* the first block not written yet */
+	uint64_t lost;                   /* blocks the ring overwrote before they could be written: named once, counted, the total reported at the end */
+};
+
+static void write_iq_export(hfdl_gpu_frontend *fe, struct iq_export *x, int wait)
+{
+	for (;;) {
+		int32_t n = 0;
+		uint64_t after = x->next;
+		if (hfdl_gpu_frontend_export_read(fe, x->next, IQX_CHUNK, x->samples, x->counts, NULL, NULL, x->info, &n, &after, wait) != 0) {
+			fprintf(stderr, "iq export: %s\n", hfdl_gpu_last_error());
+			return;
+		}
+		const uint64_t first = n > 0 ? x->info[0].block : after;
+		if (first > x->next) {
+			if (x->lost == 0)
+				fprintf(stderr, "iq export: blocks from block %llu on were overwritten before they could be written; the files continue, the count follows at the end\n", (unsigned long long)x->next);
+			x->lost += first - x->next;
+		}
+		for (int32_t i = 0; i < n; i++)
+			for (int32_t s = 0; s < x->nsel; s++) {
+				const size_t r = (size_t)i * (size_t)x->nsel + (size_t)s, cnt = (size_t)x->counts[r];
+				if (fwrite(x->samples + r * (size_t)x->row * x->es, x->es, cnt, x->files[s]) != cnt) fprintf(stderr, "iq export: short write\n");
+			}
+		x->next = after;
+		if (n < IQX_CHUNK) return;
+	}
+}
+
+static void iq_export_close(struct iq_export *x)
+{
+	if (x->lost > 0) fprintf(stderr, "iq export: %llu blocks lost\n", (unsigned long long)x->lost);
+	for (int32_t s = 0; x->files != NULL && s < x->nsel; s++)
+		if (x->files[s] != NULL) fclose(x->files[s]);
+	free(x->files);
+	free(x->samples);
+	free(x->counts);
+	memset(x, 0, sizeof(*x));
+}
+
+/* selects the channels, opens their files and turns the export on; 0, or -1 with the reason on stderr */
+static int iq_export_open(hfdl_gpu_frontend *fe, const struct gpu_fft_block *fb, struct hfdl_channel_slot **slots, size_t nch, struct iq_export *x)
+{
+	const int32_t nsel = fb->iqx_nfreqs > 0 ? fb->iqx_nfreqs : (int32_t)nch;
+	int32_t *sel = hfdl_xcalloc((size_t)nsel, sizeof(int32_t));
+	int rc = 0;
+	for (int32_t s = 0; s < nsel && rc == 0; s++) {
+		size_t c = fb->iqx_nfreqs > 0 ? 0 : (size_t)s;
+		while (fb->iqx_nfreqs > 0 && c < nch && slots[c]->frequency != fb->iqx_freqs[s]) c++;
+		if (c == nch) { fprintf(stderr, "iq export: %d Hz is not a registered channel\n", fb->iqx_freqs[s]); rc = -1; }
+		sel[s] = (int32_t)c;
+	}
+	x->nsel = nsel;
+	x->row = fb->geo.max_outputs_per_block;
+	x->es = fb->iqx_format == HFDL_GPU_EXPORT_CS16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
+	x->files = hfdl_xcalloc((size_t)nsel, sizeof(FILE *));
+	x->samples = hfdl_xcalloc((size_t)IQX_CHUNK * (size_t)nsel * (size_t)x->row, x->es);
+	x->counts = hfdl_xcalloc((size_t)IQX_CHUNK * (size_t)nsel, sizeof(int32_t));
+	for (int32_t s = 0; s < nsel && rc == 0; s++) {
+		const size_t cap = strlen(fb->iqx_dir) + 32;
+		char *path = hfdl_xcalloc(cap, 1);
+		snprintf(path, cap, "%s/%d.%s", fb->iqx_dir, slots[sel[s]]->frequency, fb->iqx_format == HFDL_GPU_EXPORT_CS16 ? "cs16" : "cf32");
+		if ((x->files[s] = fopen(path, "wb")) == NULL) { fprintf(stderr, "iq export: cannot open %s\n", path); rc = -1; }
+		free(path);
+	}
+	/* the ring holds what can be pushed before a block's launch has run and this thread has looked again (SPEC_ROWS), halved until
+	 * it fits the library's cap on a ring */
+	int32_t ring = SPEC_ROWS;
+	if (rc == 0) {
+		while ((rc = hfdl_gpu_frontend_export_enable(fe, sel, nsel, fb->iqx_format, fb->iqx_scale, ring)) == HFDL_GPU_ERANGE && ring > 2) ring /= 2;
+		if (rc != 0) fprintf(stderr, "iq export: %s\n", hfdl_gpu_last_error());
+	}
+	free(sel);
+	return rc == 0 ? 0 : -1;
+}
+
 static void *frontend_thread(void *ctx)
 {
 	struct block *block = ctx;
@@ -407,6 +517,13 @@ static void *frontend_thread(void *ctx)
 			spec_mean = hfdl_xcalloc((size_t)spec_bins, sizeof(float));
 			spec_line = hfdl_xcalloc(64 + 12 * (size_t)spec_bins, 1);
 		}
+	}
+	struct iq_export iqx;
+	memset(&iqx, 0, sizeof(iqx));
+	if (ok && fb->iqx_dir != NULL && iq_export_open(fe, fb, slots, nch, &iqx) != 0) {
+		iq_export_close(&iqx);
+		do_exit = 1;
+		ok = 0;
 	}
 	const size_t elem = hfdl_ring_elem_size(ring->buf);
 	const int gfmt = gpu_format_of(hfdl_ring_format(ring->buf));
@@ -550,6 +667,7 @@ static void *frontend_thread(void *ctx)
 			}
 			spec_next = write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 0);
 		}
+		if (iqx.files != NULL) write_iq_export(fe, &iqx, 0);
 		const double tw2 = now_s();
 		s_push += tw2 - tw1;
 		/* collect what is known to be complete without draining anything and WITHOUT waiting: what this thread may queue ahead is
@@ -585,6 +703,7 @@ shutdown:
 		} while (n == max_pdus);
 		t_last = now_s();
 		if (spec_file != NULL) (void)write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 1);
+		if (iqx.files != NULL) write_iq_export(fe, &iqx, 1);
 		publish_counters(fe, stats, (int32_t)nch);
 		pthread_mutex_lock(&g_run_lock);
 		g_run.blocks = k; g_run.samples = k * (uint64_t)need; g_run.pdus = npdus;
@@ -598,6 +717,7 @@ shutdown:
 	}
 	block_connection_one2many_shutdown(down);
 	if (fe) hfdl_gpu_frontend_destroy(fe);
+	iq_export_close(&iqx);
 	if (spec_file) fclose(spec_file);
 	free(spec_mean);
 	free(spec_line);
@@ -628,6 +748,9 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 	fb->device = g_device;
 	fb->spec_path = g_spectrum.path ? strdup(g_spectrum.path) : NULL;
 	fb->spec_bins = g_spectrum.bins; fb->spec_interval_s = g_spectrum.interval_s; fb->spec_hann = g_spectrum.hann;
+	fb->iqx_dir = g_iqx.dir ? strdup(g_iqx.dir) : NULL;
+	fb->iqx_freqs = g_iqx.dir ? copy_freqs(g_iqx.freqs, g_iqx.nfreqs) : NULL;
+	fb->iqx_nfreqs = g_iqx.nfreqs; fb->iqx_format = g_iqx.format; fb->iqx_scale = g_iqx.scale;
 	fb->block.producer.type = PRODUCER_MULTI;
 	fb->block.producer.max_tu = (size_t)fb->geo.fft_size;
 	fb->block.consumer.type = CONSUMER_SINGLE;
@@ -641,5 +764,7 @@ void fft_destroy(struct block *fft_block)
 	if (fft_block == NULL) return;
 	struct gpu_fft_block *fb = container_of(fft_block, struct gpu_fft_block, block);
 	free(fb->spec_path);
+	free(fb->iqx_dir);
+	free(fb->iqx_freqs);
 	free(fb);
 }

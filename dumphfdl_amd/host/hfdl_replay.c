@@ -3,7 +3,8 @@
  *
  *   hfdl_replay --iq-file FILE --sample-rate HZ --sample-format CF32|CS16|CU8 --centerfreq KHZ [--device N]
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
- *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]] FREQ_KHZ...
+ *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
+ *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]] FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -13,6 +14,8 @@
  * --spectrum-file PATH   every S seconds of signal (default 1) write one rtl_power-compatible CSV line of N band powers (default
  *               1024; a power of two, 16 .. 4096) over the whole span to PATH: date, time, Hz low, Hz high, Hz step, samples, dB...
  *               (hfdl_frontend_set_spectrum, include/hfdl_host.h); --spectrum-hann: Hann instead of the rectangular window.
+ * --iq-export-dir DIR    append the baseband I/Q of every channel of the list to DIR/<freq_hz>.cf32 (or .cs16 = int16 of rint(v * X),
+ *               X = 32767 by default), one file per channel (hfdl_frontend_set_iq_export, include/hfdl_host.h); DIR must exist.
  *
  * --statsd-print stands in for dumphfdl's src/statsd.c: the strong statsd_* hooks below print one "STATSD" line per
  * counter total at exit and one per noise-floor gauge as it arrives (metric names as in doc/STATSD_METRICS.md).
@@ -84,6 +87,9 @@ int main(int argc, char **argv)
 	int nfreq = 0, shard_rank = 0, shard_world = 1;
 	const char *spec_path = NULL;
 	int spec_bins = 1024, spec_interval = 1, spec_hann = 0;
+	const char *iqx_dir = NULL;
+	int iqx_format = 0;                  /* 0 = cf32, 1 = cs16 */
+	float iqx_scale = 32767.f;
 	for (int i = 1; i < argc; i++) {
 		if (!strcmp(argv[i], "--iq-file") && i + 1 < argc) cfg->source = argv[++i];
 		else if (!strcmp(argv[i], "--sample-rate") && i + 1 < argc) cfg->sample_rate = atoi(argv[++i]);
@@ -97,6 +103,13 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--spectrum-bins") && i + 1 < argc) spec_bins = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "--spectrum-interval") && i + 1 < argc) spec_interval = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "--spectrum-hann")) spec_hann = 1;
+		else if (!strcmp(argv[i], "--iq-export-dir") && i + 1 < argc) iqx_dir = argv[++i];
+		else if (!strcmp(argv[i], "--iq-export-format") && i + 1 < argc) {
+			const char *f = argv[++i];
+			if (strcmp(f, "cf32") && strcmp(f, "cs16")) { fprintf(stderr, "--iq-export-format wants cf32 or cs16\n"); return 1; }
+			iqx_format = !strcmp(f, "cs16");
+		}
+		else if (!strcmp(argv[i], "--iq-export-scale") && i + 1 < argc) iqx_scale = (float)atof(argv[++i]);
 		else if (!strcmp(argv[i], "--loop") && i + 1 < argc) hfdl_file_input_set_loops(atoi(argv[++i]));
 		else if (!strcmp(argv[i], "--shard") && i + 1 < argc) {
 			if (sscanf(argv[++i], "%d/%d", &shard_rank, &shard_world) != 2 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) {
@@ -137,6 +150,10 @@ int main(int argc, char **argv)
 	float tbw = compute_filter_relative_transition_bw(cfg->sample_rate, HFDL_CHANNEL_TRANSITION_BW_HZ);
 	if (spec_path != NULL && hfdl_frontend_set_spectrum(spec_path, spec_bins, spec_interval, spec_hann) != 0) {
 		fprintf(stderr, "--spectrum-bins wants a power of two from 16 to 4096, --spectrum-interval at least 1\n");
+		return 1;
+	}
+	if (iqx_dir != NULL && hfdl_frontend_set_iq_export(iqx_dir, NULL, 0, iqx_format, iqx_scale) != 0) {
+		fprintf(stderr, "--iq-export-scale wants a finite number above 0\n");
 		return 1;
 	}
 	struct block *fft = fft_create(decimation, tbw);

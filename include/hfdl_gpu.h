@@ -349,6 +349,45 @@ int  hfdl_gpu_frontend_spectrum_row_close(hfdl_gpu_frontend *fe, uint64_t *row);
 int  hfdl_gpu_frontend_spectrum_rows(hfdl_gpu_frontend *fe, int32_t rx, uint64_t from_row, int32_t max_rows,
 		float *mean, float *peak, hfdl_gpu_spectrum_row *info, int32_t *n, uint64_t *next_row, int wait);
 
+/* Channel baseband export (off by default: nothing is allocated or launched): the channelizer's output of SELECTED channels, every
+ * sample of it, as a stream the caller collects without waiting -- for recording a channel, feeding another decoder, or looking at a
+ * constellation.  Behind the inverse FFT / NCO launch of every closed half, one launch packs the selected channels' rows of the half's
+ * blocks into a ring of ring_blocks blocks in HBM; block b (in the numbering of hfdl_gpu_frontend_counters().blocks; "block" as for the
+ * spectrum monitor: a push or a channelize_block, not push_baseband) lives in slot b mod ring_blocks, so a block not collected
+ * within ring_blocks blocks is overwritten, and a half larger than the ring overwrites its own oldest blocks.  Per block and selected
+ * channel s (channel channels[s], P = geometry.max_outputs_per_block):
+ *   samples[s][0 .. P)   the counts[s] valid samples -- bit for bit what HFDL_GPU_TAP_CHAN_OUT reads -- then zeros.  CF32: float re, im.
+ *                        CS16: int16 re, im; per component r = rintf(v * scale) (one fp32 multiply, round half to even), |r| > 32767
+ *                        stored as +-32767, NaN stored as 0, both counted in clipped[s];
+ *   power[s]             mean of re^2 + im^2 over the valid samples in fp32 (0 without any), summed in a fixed order: bit-identical
+ *                        from run to run and independent of how the caller pushes, polls or batches. */
+#define HFDL_GPU_EXPORT_CF32 0
+#define HFDL_GPU_EXPORT_CS16 1
+#define HFDL_GPU_EXPORT_RING_MAX 4096
+typedef struct { uint64_t block; } hfdl_gpu_export_block;      /* index in the numbering of counters().blocks */
+/* channels[nsel]: distinct global channel indices in any order -- the order of the exported rows; nsel = 0 turns the export off and
+ * frees its buffers.  ring_blocks: 2 .. HFDL_GPU_EXPORT_RING_MAX.  scale: CS16 only, finite and > 0.  The first exported block is the
+ * first one pushed after the call (a block already waiting in the half being filled is not exported; no half is closed).  Calling it
+ * again starts over with an empty ring (it waits for the export launches queued so far before the old ring goes).  HFDL_GPU_EINVAL
+ * (null handle, null channels with nsel > 0, nsel < 0 or above the channel count, a channel out of range or repeated, unknown
+ * format, bad scale, ring_blocks out of range) / HFDL_GPU_ERANGE (ring above 1 GiB) are checked before any device work;
+ * HFDL_GPU_ENOMEM leaves the export as it was. */
+int  hfdl_gpu_frontend_export_enable(hfdl_gpu_frontend *fe, const int32_t *channels, int32_t nsel,
+		int format, float scale, int32_t ring_blocks);
+/* Consecutive finished blocks from max(from_block, oldest block kept) on, at most max_blocks: samples[i][s][P] elements of the enabled
+ * format, counts[i * nsel + s], power and clipped likewise (each may be NULL), info[i].block; *n = blocks written, *next_block = what
+ * to pass as from_block next time.  A block overwritten before it was collected shows as info[0].block > from_block -- nothing fails.
+ * max_blocks = 0 writes nothing and reports *next_block, *n = 0.  A block is finished when the export launch of its half has run.
+ * wait = 0: only such blocks -- the call asks (hipEventQuery) and never waits for a kernel stream.  wait != 0: waits for the newest
+ * export launch ALREADY QUEUED; it closes nothing, so blocks still in the half being filled come with a later call (after a sync, a
+ * poll, or the push that fills the half).  The copy runs on the collection stream through a page-locked buffer beside the kernels in
+ * flight; the call returns when it is done.  One thread drives a front end: no copy of a slot is in flight while a push re-targets
+ * it.  HFDL_GPU_EINVAL (null handle, n or next_block, export off, max_blocks < 0, samples, counts or info null with max_blocks > 0)
+ * is checked before any device work. */
+int  hfdl_gpu_frontend_export_read(hfdl_gpu_frontend *fe, uint64_t from_block, int32_t max_blocks,
+		void *samples, int32_t *counts, float *power, uint32_t *clipped, hfdl_gpu_export_block *info,
+		int32_t *n, uint64_t *next_block, int wait);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */

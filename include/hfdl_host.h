@@ -205,6 +205,15 @@ void          hfdl_frontend_set_device(int device);
  * interval whose read or line fails is reported on stderr and has no line).  bins: a power of two, 16 .. 4096 (cut down to
  * fft_size / 16 on a small geometry); interval_s >= 1; hann != 0: Hann window.  path NULL: off.  Returns 0, or -1 for bad arguments. */
 int           hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t interval_s, int hann);
+/* Channel baseband export of the front end created by the next fft_create() (include/hfdl_gpu.h, "Channel baseband export"); not in
+ * the reference, whose DATADUMPS build writes a channel's samples to a file in the same spirit.  The front-end thread appends every
+ * block's valid samples of each selected channel to `dir`/<freq_hz>.cf32 (format 0: float re, im) or `dir`/<freq_hz>.cs16 (format 1:
+ * int16 re, im = rint(v * scale), clamped to +-32767), one file per channel, created or truncated when the front end starts; `dir` must
+ * exist.  It collects after every push without waiting and once more, waiting, after the final drain; blocks the device's ring has
+ * overwritten before they were collected are named on stderr once and their count reported when the front end stops; the file simply continues.  freqs[nfreqs]:
+ * channel frequencies in Hz as registered with hfdl_channel_create(); nfreqs = 0 selects every registered channel.  scale: format 1
+ * only, finite and > 0.  dir NULL: off.  Returns 0, or -1 for bad arguments. */
+int           hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t nfreqs, int format, float scale);
 /* The line: "date, time, Hz low, Hz high, Hz step, samples, dB, dB, ...\n" -- date / time = UTC of t_unix, Hz low / high = lower edge of
  * the first / upper edge of the last band, Hz step = width of a band, samples = blocks averaged, dB = 10 log10(mean[b]) (dBFS; -200
  * for an empty band).  No device is needed.  Returns the length written (without the terminating 0), -1 if it does not fit. */
