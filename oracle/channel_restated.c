@@ -335,6 +335,14 @@ static void symsync_init(symsync_t *s, float lf_bw)
 	symsync_reset(s);
 }
 
+void orc_symsync_loop_filter(float *b0, float *a1, float *rate_adjustment)
+{
+	symsync_t *s = malloc(sizeof(*s));
+	symsync_init(s, SYMSYNC_LF_BW);
+	*b0 = s->lf_b0; *a1 = s->lf_a1; *rate_adjustment = s->rate_adjustment;
+	free(s);
+}
+
 static orc_cf bank_dot(const float *h, const orc_cf *w)
 {
 	return dot_rc(h, w, SS_TAPS);

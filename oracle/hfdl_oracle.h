@@ -195,6 +195,7 @@ int32_t orc_resamp_run(float rate, const orc_cf *x, int32_t n, orc_cf *y, uint32
 void orc_resamp_filter(float rate, float *h /* 256*14 */, uint32_t *step);
 void orc_symsync_filters(float *mf /*16*18*/, float *dmf /*16*18*/);
 void orc_eq_initial_taps(float *w15);
+void orc_symsync_loop_filter(float *b0, float *a1, float *rate_adjustment);   /* symsync_crcf_set_lf_bw(0.001), normalised by a0 */
 
 /* ---------------- whole front end (src/main.c:699-774 wiring) ---------------- */
 typedef struct orc_frontend orc_frontend;

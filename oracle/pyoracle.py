@@ -138,6 +138,7 @@ def lib():
         L.orc_resamp_filter.argtypes = [C.c_float, C.c_void_p, C.POINTER(C.c_uint32)]
         L.orc_symsync_filters.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_eq_initial_taps.argtypes = [C.c_void_p]
+        L.orc_symsync_loop_filter.argtypes = [C.POINTER(C.c_float)] * 3
         L.orc_frontend_create.restype = C.c_void_p
         L.orc_frontend_create.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
         L.orc_frontend_create_mt.restype = C.c_void_p

@@ -88,6 +88,27 @@ int sim_taps(Sim *s, float *rs, float *mf, float *sym, float *lvl, int *counts)
 	return 0;
 }
 
+// the channel's integer counters as hfdl_gpu_frontend_all_channel_stats reports them: A1 / A2 / M1 found, M1 not found, frames, training
+// bits total and bad
+void sim_counters(const Sim *s, uint32_t *out)
+{
+	const ChanScalars &c = s->st.s;
+	out[0] = c.cnt_a1_found; out[1] = c.cnt_a2_found; out[2] = c.cnt_m1_found; out[3] = c.cnt_m1_not_found; out[4] = c.cnt_frames;
+	out[5] = c.cum_train_total; out[6] = c.cum_train_bad;
+}
+
+// one decision of the carrier loop's slicer: nearest = 0 the arg() + reference ladder (psk_slice), 1 the nearest-point form the fast
+// build runs (serial_demod.h NearestSlicer); returns the Gray symbol
+uint32_t sim_slice(int arity, float re, float im, int nearest, float *phase_error)
+{
+	static DemodTables tab;
+	static bool made = false;
+	if (!made) { build_demod_tables(tab, 0.6912f); made = true; }
+	cf x; x.x = re; x.y = im;
+	if (nearest) return NearestSlicer{&tab.psk_pts[0][0]}(arity, x, phase_error);
+	return TableSlicer{&tab.psk_pts[0][0]}(arity, x, phase_error);
+}
+
 void sim_psk_soft(int arity, float re, float im, uint8_t *soft)
 {
 	static DemodTables tab;

@@ -130,7 +130,7 @@ HFDL_FN int demod_block_serial(ChanScalars &s, ChanArrays &a, const DemodConst &
 		for (int q = 0; q < D_RS_TAPS - 1; q++) a.rs_hist[q] = tmp[q];
 	}
 	s.rs_phase = (uint32_t)((uint64_t)s.rs_phase + (uint64_t)n_out * T.rs_step - total);
-	if (io.tap_counts) io.tap_counts[0] = n_out;
+	if (io.tap_counts) { io.tap_counts[0] = n_out; io.tap_counts[1] = 0; }      // (a launch without an output has no symbols either)
 	if (n_out < 1) return 0;
 
 	// ---- A: AGC (agc_crcf_execute, src/hfdl.c:686)
