@@ -71,6 +71,7 @@ struct Demod {
 
 #ifdef HFDL_LAB
 int demod_clock_probe_read(unsigned long long *out, int max, int *n);      // laboratory: {tag, shader cycles, 100 MHz ticks, start tick} per probed launch
+int demod_burst_soft_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes, uint8_t *vin, int32_t *vin_lens);   // laboratory: the Viterbi input of every frame, [nframes][HFDL_GPU_LAB_VIN_MAX]
 #endif
 // kernel_ms: time of the kernel launch alone (StageTimer)
 int demod_viterbi_batch(const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out, double *kernel_ms);

@@ -25,6 +25,9 @@
 #include "demod_tables.h"
 #include "demod.h"
 #include "demod_launch.h"
+#ifdef HFDL_LAB
+#include "../../include/hfdl_gpu_lab.h"
+#endif
 
 namespace hfdl {
 
@@ -348,32 +351,15 @@ __device__ __forceinline__ void viterbi27_wave(const uint8_t *vin, int nbits, ui
 
 constexpr int K5_TABLE_BYTES = 15360;      // >= 168*30*3 coded bits, 256-aligned
 
-__global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__restrict__ frames, int *counts, const int *nframes_ptr, int *stale_count, int frame_cap,
-		const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler, const int32_t *__restrict__ freqs,
-		hfdl_gpu_pdu *__restrict__ pdus, int pdu_cap)
+// The soft half of the burst decoder -- descrambler, soft de-map, de-interleaver push and pop, rate-1/4 combine -- for one frame and
+// one wave: fills vin (LDS) with what the Viterbi decoder is fed and returns its length.  l_scr / l_psk: the staged constants;
+// table: K5_TABLE_BYTES of LDS; nsym, ncoded, cols: symbols, coded bits and de-interleaver columns of the mode.  The caller synchronises
+// before reading vin.
+__device__ __forceinline__ int burst_soft_wave(const int mode, const int nsym, const int ncoded, const int cols, const cf *sym, const float mask_flip,
+		const uint8_t *l_scr, const float *l_psk, uint8_t *table, uint8_t *vin)
 {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-	__builtin_amdgcn_s_setprio(2);          // one wavefront per frame beside the fold: first in line when it has something to issue (see demod_kernel)
-	const int f = blockIdx.x, lane = threadIdx.x;
-	int nframes = *nframes_ptr;
-	if (f == 0 && lane == 0 && stale_count) *stale_count = 0;      // the counter of the launch after next: its last users finished before this launch began
-	if (nframes > frame_cap) nframes = frame_cap;
-	if (f >= nframes) return;
-	uint8_t *table = lds;
-	uint8_t *vin = lds + K5_TABLE_BYTES;
-	uint64_t *decw = (uint64_t *)(lds + 2 * K5_TABLE_BYTES);
-	uint8_t *l_scr = lds + 2 * K5_TABLE_BYTES + viterbi_lds_bytes(7560);             // 128 bytes, then the constellation table
-	float *l_psk = (float *)(l_scr + DEC_PSK_OFFSET);
-
-	const FrameRec fr = frames[f];
-	const ModeParams mp = mode_params(fr.mode);
-	const int nsym = mp.segments * 30, ncoded = nsym * mp.arity, cols = ncoded / 40;
-	const cf *sym = data_all + ((size_t)fr.channel * 2 + fr.slot) * MAX_DATA_SYMBOLS;
-	const float mask_flip = fr.bitmask_lsb ? -1.0f : 1.0f;
-	l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
-	if (lane + 64 < 120) l_scr[lane + 64] = scrambler[lane + 64];
-	if (lane < 32) l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
-	__syncthreads();
+	const int lane = threadIdx.x;
+	const ModeParams mp = mode_params(mode);
 	// descramble + soft de-map + de-interleaver push (src/hfdl.c:1008-1019, 378-392); four symbol loads per lane in flight
 	// (this kernel runs beside the fold, where a dependent global load costs microseconds)
 	for (int base = 0; base < nsym; base += 256) {
@@ -410,6 +396,36 @@ __global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__rest
 			vin[j] = table[((9 * j) % 40) * cols + j / 40];
 		}
 	}
+	return vin_len;
+}
+
+__global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__restrict__ frames, int *counts, const int *nframes_ptr, int *stale_count, int frame_cap,
+		const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler, const int32_t *__restrict__ freqs,
+		hfdl_gpu_pdu *__restrict__ pdus, int pdu_cap)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	__builtin_amdgcn_s_setprio(2);          // one wavefront per frame beside the fold: first in line when it has something to issue (see demod_kernel)
+	const int f = blockIdx.x, lane = threadIdx.x;
+	int nframes = *nframes_ptr;
+	if (f == 0 && lane == 0 && stale_count) *stale_count = 0;      // the counter of the launch after next: its last users finished before this launch began
+	if (nframes > frame_cap) nframes = frame_cap;
+	if (f >= nframes) return;
+	uint8_t *table = lds;
+	uint8_t *vin = lds + K5_TABLE_BYTES;
+	uint64_t *decw = (uint64_t *)(lds + 2 * K5_TABLE_BYTES);
+	uint8_t *l_scr = lds + 2 * K5_TABLE_BYTES + viterbi_lds_bytes(7560);             // 128 bytes, then the constellation table
+	float *l_psk = (float *)(l_scr + DEC_PSK_OFFSET);
+
+	const FrameRec fr = frames[f];
+	const ModeParams mp = mode_params(fr.mode);
+	const int nsym = mp.segments * 30, ncoded = nsym * mp.arity, cols = ncoded / 40;
+	const cf *sym = data_all + ((size_t)fr.channel * 2 + fr.slot) * MAX_DATA_SYMBOLS;
+	const float mask_flip = fr.bitmask_lsb ? -1.0f : 1.0f;
+	l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
+	if (lane + 64 < 120) l_scr[lane + 64] = scrambler[lane + 64];
+	if (lane < 32) l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
+	__syncthreads();
+	const int vin_len = burst_soft_wave(fr.mode, nsym, ncoded, cols, sym, mask_flip, l_scr, l_psk, table, vin);
 	// claim a slot of the PDU ring: counts[1] = PDUs ever produced, counts[3] = PDUs the host has taken (both mod 2^32);
 	// a full ring drops the PDU (counts[2]) without leaving a hole
 	int slot = -1;
@@ -460,6 +476,35 @@ __global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__rest
 		out->lpdu_pad[0] = out->lpdu_pad[1] = out->lpdu_pad[2] = 0;
 	}
 }
+
+#ifdef HFDL_LAB
+// laboratory tap on the Viterbi input (hfdl_gpu_lab_burst_soft): burst_decode_kernel's own staging and soft half, one wave per frame,
+// vin copied out to row f of vin_out ([nframes][HFDL_GPU_LAB_VIN_MAX])
+__global__ __launch_bounds__(64) void burst_soft_kernel(const FrameRec *__restrict__ frames, const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler,
+		uint8_t *__restrict__ vin_out, int32_t *__restrict__ vin_lens)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+	const int f = blockIdx.x, lane = threadIdx.x;
+	uint8_t *table = lds;
+	uint8_t *vin = lds + K5_TABLE_BYTES;
+	uint8_t *l_scr = lds + 2 * K5_TABLE_BYTES;
+	float *l_psk = (float *)(l_scr + DEC_PSK_OFFSET);
+	const FrameRec fr = frames[f];
+	const ModeParams mp = mode_params(fr.mode);
+	const int nsym = mp.segments * 30, ncoded = nsym * mp.arity, cols = ncoded / 40;
+	const cf *sym = data_all + ((size_t)fr.channel * 2 + fr.slot) * MAX_DATA_SYMBOLS;
+	const float mask_flip = fr.bitmask_lsb ? -1.0f : 1.0f;
+	l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
+	if (lane + 64 < 120) l_scr[lane + 64] = scrambler[lane + 64];
+	if (lane < 32) l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
+	__syncthreads();
+	const int vin_len = burst_soft_wave(fr.mode, nsym, ncoded, cols, sym, mask_flip, l_scr, l_psk, table, vin);
+	__syncthreads();
+	uint8_t *dst = vin_out + (size_t)f * HFDL_GPU_LAB_VIN_MAX;
+	for (int j = lane; j < vin_len && j < HFDL_GPU_LAB_VIN_MAX; j += 64) dst[j] = vin[j];
+	if (lane == 0) vin_lens[f] = vin_len;
+}
+#endif
 
 __global__ __launch_bounds__(64) void viterbi_batch_kernel(const uint8_t *__restrict__ soft, int nbits, uint8_t *__restrict__ out)
 {
@@ -745,5 +790,44 @@ int demod_burst_decode_batch(const float *symbols, const int32_t *modes, const i
 	}
 	return 0;
 }
+
+#ifdef HFDL_LAB
+// hfdl_gpu_lab_burst_soft: frames laid out as demod_burst_decode_batch lays them out, through burst_soft_kernel
+int demod_burst_soft_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes, uint8_t *vin, int32_t *vin_lens)
+{
+	DemodTables h;
+	build_demod_tables(h, 0.6912f);
+	std::vector<FrameRec> fr((size_t)nframes);
+	std::vector<cf> data((size_t)nframes * 2 * MAX_DATA_SYMBOLS);
+	size_t off = 0;
+	for (int i = 0; i < nframes; i++) {
+		const size_t nsym = (size_t)mode_params(modes[i]).segments * 30;
+		std::memcpy(&data[(size_t)i * 2 * MAX_DATA_SYMBOLS], symbols + 2 * off, sizeof(cf) * nsym);
+		off += nsym;
+		FrameRec &f = fr[(size_t)i];
+		std::memset(&f, 0, sizeof(f));
+		f.channel = i; f.slot = 0; f.mode = modes[i]; f.bitmask_lsb = bitmask_lsb[i] & 1;
+	}
+	const size_t out_bytes = (size_t)nframes * HFDL_GPU_LAB_VIN_MAX;
+	DevBuf d_scr, d_fr, d_data, d_vin, d_lens;
+	HIP_TRY(d_scr.alloc(DEC_CONST_BYTES));
+	HIP_TRY(hipMemcpy(d_scr.p, h.scrambler, DEC_CONST_BYTES, hipMemcpyHostToDevice));
+	HIP_TRY(d_fr.alloc(sizeof(FrameRec) * fr.size()));
+	HIP_TRY(hipMemcpy(d_fr.p, fr.data(), sizeof(FrameRec) * fr.size(), hipMemcpyHostToDevice));
+	HIP_TRY(d_data.alloc(sizeof(cf) * data.size()));
+	HIP_TRY(hipMemcpy(d_data.p, data.data(), sizeof(cf) * data.size(), hipMemcpyHostToDevice));
+	HIP_TRY(d_vin.alloc(out_bytes));
+	HIP_TRY(hipMemset(d_vin.p, 0, out_bytes));
+	HIP_TRY(d_lens.alloc(sizeof(int32_t) * (size_t)nframes));
+	HIP_TRY(hipMemset(d_lens.p, 0, sizeof(int32_t) * (size_t)nframes));
+	hipLaunchKernelGGL(burst_soft_kernel, dim3((unsigned)nframes), dim3(64), 2 * K5_TABLE_BYTES + DEC_CONST_BYTES, nullptr, d_fr.as<const FrameRec>(), d_data.as<const cf>(),
+			d_scr.as<const uint8_t>(), d_vin.as<uint8_t>(), d_lens.as<int32_t>());
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(vin, d_vin.p, out_bytes, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(vin_lens, d_lens.p, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToHost));
+	return 0;
+}
+#endif
 
 }  // namespace hfdl

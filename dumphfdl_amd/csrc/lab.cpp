@@ -76,6 +76,15 @@ extern "C" int hfdl_gpu_lab_clock_probe_read(int which, uint64_t *records, int32
 	return 0;
 }
 
+extern "C" int hfdl_gpu_lab_burst_soft(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes,
+		uint8_t *vin, int32_t *vin_lens)
+{
+	if (!symbols || !modes || !bitmask_lsb || !vin || !vin_lens || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
+	for (int i = 0; i < nframes; i++) if (modes[i] < 0 || modes[i] > 7) return fail(HFDL_GPU_EINVAL, "mode out of range");
+	if (int rc = select_device(device)) return rc;
+	return demod_burst_soft_batch(symbols, modes, bitmask_lsb, nframes, vin, vin_lens);
+}
+
 extern "C" int hfdl_gpu_lab_fold_variant_count(void) { return fold_variant_count(); }
 
 extern "C" int hfdl_gpu_lab_fold_variant_describe(int variant, int32_t desc[6])

@@ -92,7 +92,8 @@ EXPORT_RING_MAX = 4096     # HFDL_GPU_EXPORT_RING_MAX
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
-               "hfdl_gpu_lab_read_constants", "hfdl_gpu_lab_clock_probe_read"]
+               "hfdl_gpu_lab_read_constants", "hfdl_gpu_lab_clock_probe_read", "hfdl_gpu_lab_burst_soft"]
+LAB_VIN_MAX = 15120        # HFDL_GPU_LAB_VIN_MAX of include/hfdl_gpu_lab.h
 
 
 def fold_variants():
@@ -139,6 +140,7 @@ def load_lab():
     L.hfdl_gpu_lab_stream_read_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.hfdl_gpu_lab_read_constants.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.hfdl_gpu_lab_clock_probe_read.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    L.hfdl_gpu_lab_burst_soft.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     _lab = L
     return L
 
@@ -641,6 +643,19 @@ def burst_decode(symbol_list, modes, bitmask_lsb=None, device=0):
     lens = np.zeros(n, np.int32)
     _check(load().hfdl_gpu_burst_decode(device, _p(sym), _p(modes), _p(bm), n, _p(octets), _p(lens)))
     return [bytes(octets[i, :lens[i]]) for i in range(n)]
+
+
+def lab_burst_soft(symbol_list, modes, bitmask_lsb=None, device=0):
+    """burst_decode's frames stopped in front of the Viterbi decoder (laboratory build): the soft bytes it is fed, one uint8 array per frame."""
+    L = load_lab()
+    n = len(symbol_list)
+    modes = np.ascontiguousarray(modes, dtype=np.int32)
+    bm = np.zeros(n, np.int32) if bitmask_lsb is None else np.ascontiguousarray(bitmask_lsb, dtype=np.int32)
+    sym = np.ascontiguousarray(np.concatenate([np.asarray(s, np.complex64) for s in symbol_list]), dtype=np.complex64)
+    vin = np.zeros((n, LAB_VIN_MAX), np.uint8)
+    lens = np.zeros(n, np.int32)
+    _check(L.hfdl_gpu_lab_burst_soft(device, _p(sym), _p(modes), _p(bm), n, _p(vin), _p(lens)), L)
+    return [vin[i, :lens[i]].copy() for i in range(n)]
 
 
 def last_stage_ms():

@@ -46,6 +46,12 @@ int  hfdl_gpu_lab_read_constants(hfdl_gpu_frontend *fe, void *tables, size_t tab
 int  hfdl_gpu_lab_clock_probe_read(int which, uint64_t *records, int32_t max, int32_t *n);
 /* what the board's HBM delivers to a read-only streaming kernel with the fold's access pattern (reads the resident taps) */
 int  hfdl_gpu_lab_stream_read_probe(hfdl_gpu_frontend *fe, double *gb_per_s);
+/* What the burst decoder feeds its Viterbi decoder: the frames of hfdl_gpu_burst_decode (same arguments, same layout on the device) through
+ * the decoder's own descrambler, soft de-map, de-interleaver and rate-1/4 combine, stopped in front of the Viterbi.  vin: nframes rows of
+ * HFDL_GPU_LAB_VIN_MAX bytes, row i holds vin_lens[i] soft bytes (two per decoded bit), the rest zero. */
+#define HFDL_GPU_LAB_VIN_MAX 15120        /* 168 segments x 30 symbols x 3 bits */
+int  hfdl_gpu_lab_burst_soft(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes,
+		uint8_t *vin, int32_t *vin_lens);
 
 #ifdef __cplusplus
 }

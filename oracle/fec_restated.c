@@ -375,7 +375,8 @@ void orc_modem_demod_soft(int arity, orc_cf x, uint8_t *soft)
 
 /* ---- decode_user_data (src/hfdl.c:993-1056) ---- */
 
-int32_t orc_decode_user_data(int mode, const orc_cf *symbols, int bitmask_lsb, uint8_t *octets)
+/* the part in front of the Viterbi decoder: vin receives orc_mode_viterbi_bits(mode) * 2 soft bytes; returns that count */
+int32_t orc_user_data_soft(int mode, const orc_cf *symbols, int bitmask_lsb, uint8_t *vin)
 {
 	const orc_mode_params *p = &orc_modes[mode];
 	int32_t nsym = orc_mode_num_symbols(mode), ncoded = orc_mode_coded_bits(mode);
@@ -392,7 +393,6 @@ int32_t orc_decode_user_data(int mode, const orc_cf *symbols, int bitmask_lsb, u
 		for (int j = 0; j < p->arity; j++) table[push_pos[k++]] = soft[j];
 	}
 	int32_t vin_len = (p->code_rate == 4) ? ncoded / 2 : ncoded;
-	uint8_t *vin = malloc((size_t)vin_len);
 	if (p->code_rate == 4) {
 		for (int32_t i = 0; i < vin_len; i++) {
 			uint8_t a = table[pop_pos[2 * i]], b = table[pop_pos[2 * i + 1]];
@@ -401,9 +401,17 @@ int32_t orc_decode_user_data(int mode, const orc_cf *symbols, int bitmask_lsb, u
 	} else {
 		for (int32_t i = 0; i < vin_len; i++) vin[i] = table[pop_pos[i]];
 	}
+	free(scr); free(table); free(push_pos); free(pop_pos);
+	return vin_len;
+}
+
+int32_t orc_decode_user_data(int mode, const orc_cf *symbols, int bitmask_lsb, uint8_t *octets)
+{
+	uint8_t *vin = malloc((size_t)orc_mode_coded_bits(mode));
+	int32_t vin_len = orc_user_data_soft(mode, symbols, bitmask_lsb, vin);
 	int32_t nbits = vin_len / 2, noct = (nbits + 7) / 8;
 	orc_viterbi27_decode(vin, nbits, octets);
 	for (int32_t i = 0; i < noct; i++) octets[i] = orc_reverse_byte(octets[i]);
-	free(scr); free(table); free(push_pos); free(pop_pos); free(vin);
+	free(vin);
 	return noct;
 }

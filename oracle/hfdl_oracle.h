@@ -103,6 +103,7 @@ void    orc_scrambler_bits(uint8_t *bits, int32_t n);      /* src/hfdl.c:300-347
 void    orc_deinterleave_maps(int mode, int32_t *push_pos, int32_t *pop_pos);
 /* soft symbols (after eq) -> octets: src/hfdl.c:993-1056. bitmask_lsb = c->bitmask&1 */
 int32_t orc_decode_user_data(int mode, const orc_cf *symbols, int bitmask_lsb, uint8_t *octets);
+int32_t orc_user_data_soft(int mode, const orc_cf *symbols, int bitmask_lsb, uint8_t *vin);      /* its first half: the Viterbi decoder's input */
 /* liquid modem soft demod restatement (a16) */
 void    orc_modem_demod_soft(int arity, orc_cf x, uint8_t *soft);
 orc_cf  orc_modem_modulate(int arity, uint32_t sym);                 /* modem_modulate_psk: cexpjf(gray_decode(sym) * 2 * pi / M) */

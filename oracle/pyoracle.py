@@ -115,6 +115,8 @@ def lib():
         L.orc_firdes_bandpass_c.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
         L.orc_decode_user_data.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.orc_decode_user_data.restype = C.c_int32
+        L.orc_user_data_soft.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.orc_user_data_soft.restype = C.c_int32
         L.orc_deinterleave_maps.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.orc_scrambler_bits.argtypes = [C.c_void_p, C.c_int32]
         L.orc_modem_demod_soft.argtypes = [C.c_int, Cf, C.c_void_p]
@@ -300,6 +302,14 @@ def decode_user_data(mode, symbols, bitmask_lsb=0):
     symbols = cf(symbols)
     out = np.zeros(960, np.uint8)
     n = lib().orc_decode_user_data(mode, _p(symbols), bitmask_lsb, _p(out))
+    return out[:n].copy()
+
+
+def user_data_soft(mode, symbols, bitmask_lsb=0):
+    """The bytes decode_user_data feeds its Viterbi decoder (descrambler, soft de-map, de-interleaver, rate-1/4 combine)."""
+    symbols = cf(symbols)
+    out = np.zeros(15120, np.uint8)
+    n = lib().orc_user_data_soft(mode, _p(symbols), bitmask_lsb, _p(out))
     return out[:n].copy()
 
 

@@ -51,6 +51,28 @@ def viterbi_live_vectors():
     np.savez_compressed(os.path.join(HERE, "viterbi_live_ref.npz"), **out)
 
 
+def viterbi_ragged_vectors():
+    """Sizes no HFDL frame has: nbits 1 .. 130 (below one 60-step trip, below the 6-step look-ahead, every residue of 6, 8, 48 and 60),
+    two cases each -- uniform random bytes, and coded bits + N(0, 90) clipped -- and one random case each side of 540 and 7560.
+    Read back by tests/fec_model.py ragged_cases()."""
+    rng = np.random.default_rng(20261018)
+    sizes, softs, outs = [], [], []
+
+    def case(nbits, soft):
+        sizes.append(nbits)
+        softs.append(soft)
+        outs.append(np.frombuffer(bytes(O.ref_viterbi27(soft, nbits)), np.uint8))
+    for nbits in range(1, 131):
+        bits = rng.integers(0, 2, nbits).astype(np.uint8)
+        coded = synth.conv_encode(bits).astype(float) * 255
+        case(nbits, rng.integers(0, 256, 2 * nbits).astype(np.uint8))
+        case(nbits, np.clip(coded + rng.normal(0, 90, len(coded)), 0, 255).astype(np.uint8))
+    for nbits in (539, 541, 7559, 7561):
+        case(nbits, rng.integers(0, 256, 2 * nbits).astype(np.uint8))
+    # one array each (a zip member per case would cost more than the cases): case i has 2 * nbits[i] soft bytes and ceil(nbits[i] / 8) octets
+    np.savez_compressed(os.path.join(HERE, "viterbi_ragged_ref.npz"), nbits=np.array(sizes, np.int32), soft=np.concatenate(softs), out=np.concatenate(outs))
+
+
 def crc_vectors():
     rng = np.random.default_rng(7)
     vec = []
@@ -97,6 +119,7 @@ def nco_vectors():
 if __name__ == "__main__":
     viterbi_vectors()
     viterbi_live_vectors()
+    viterbi_ragged_vectors()
     crc_vectors()
     nco_vectors()
     print("golden vectors written to", HERE)

@@ -118,6 +118,12 @@ void sim_psk_soft(int arity, float re, float im, uint8_t *soft)
 	psk_soft(arity, x, soft, PskTable{&tab.psk_pts[0][0]});
 }
 
+// the same for n symbols (xy interleaved): soft receives arity bytes per symbol
+void sim_psk_soft_batch(int arity, const float *xy, int n, uint8_t *soft)
+{
+	for (int i = 0; i < n; i++) sim_psk_soft(arity, xy[2 * i], xy[2 * i + 1], soft + (size_t)i * arity);
+}
+
 int sim_pdu_triage(const uint8_t *buf, uint32_t len, int *kind, uint32_t *hdr_len) { return pdu_triage(buf, len, kind, hdr_len); }
 
 void sim_lpdu_walk(const uint8_t *buf, uint32_t len, uint8_t *counts)
