@@ -228,7 +228,7 @@ __device__ __forceinline__ void symsync_load(SymsyncRegs &r, const ChanScalars &
 // symsync_crcf_reset as the framer left it after input sample k0-1: loop scalars initial, matched-filter window empty
 __device__ __forceinline__ void symsync_restart(SymsyncRegs &r, const DemodShared &sh, int k0)
 {
-	r.rate = 1.5f; r.del = 1.5f; r.tau = 0.f; r.bf = 0.f; r.q = 0.f; r.qhat = 0.f; r.v1 = 0.f;
+	r.rate = HFDL_DM_SS_RATE0; r.del = HFDL_DM_SS_RATE0; r.tau = 0.f; r.bf = 0.f; r.q = 0.f; r.qhat = 0.f; r.v1 = 0.f;
 	r.b = 0; r.decim = 0;
 	r.j = k0 > 0 ? (int)sh.cum[(k0 - 1) & DM_MASK] : 0;
 	r.valid_from = k0;
@@ -247,65 +247,81 @@ __device__ __forceinline__ void symsync_store(const SymsyncRegs &r, ChanScalars 
 
 // Samples [k0, k1) of ONE turn of the ring (the caller cuts a chunk at the wrap).
 // MASKED: some window entries of the chunk's first samples date from before the last timing-loop reset (only in the 18 samples after
-// one); the common chunk runs the variant without the per-sample test and selects (14 instructions of this wave's ~75 per sample).
+// one); the common chunk runs the variant without the per-sample test and selects.
+// This wave bounds every launch and is bound by its instruction count (profiles/r14_experiments.md), so the loop is laid out for the
+// steady state -- an input sample yields one output or none:
+//   - the first output of a sample is straight-line code; only a timing loop far off its rate (another output from the same sample)
+//     enters the general loop behind it;
+//   - the outputs go to the ring as the raw row totals: the division by three (liquid's 1 / k scaling) is the carrier wave's, two per
+//     lane and chunk on what it loads (carrier_chunk) instead of two per output here;
+//   - the filter-bank index is (int)(bf + copysign(largest float below 1/2, bf)): the same integer as (int)roundf(bf) for every float
+//     (tests/hostsim/round_form_check.cpp compares all 2^32), three instructions instead of roundf's ten;
+//   - one lane pointer stepped per sample serves both window reads.
 template <bool MASKED>
 __device__ __forceinline__ void symsync_chunk(SymsyncRegs &r, const DemodConst &T, const BlockIo &io, const DemodShared &sh, int k0, int k1, int lane)
 {
 	const int row = lane >> 4, t = lane & 15;
-	// &mf[k - t].component of this lane's row for k = the first sample of this turn of the ring; tap t + 16 is 16 samples further back
-	const float *base = (const float *)(io.mf - (k0 & ~DM_MASK) - t) + (row & 1);
-	int bi = r.b < 0 ? 0 : (r.b >= D_SS_NPFB ? D_SS_NPFB - 1 : r.b);
-	float2 h = sh.sstab[bi * 64 + lane];
-	float w_lo = base[2 * k0], w_hi = base[2 * (k0 - 16)];
+	// wp = &mf[k - 16 - t].component of this lane's row, k = the sample at hand: tap t + 16 of the window is wp[0], tap t is wp[32]
+	const float *wp = (const float *)(io.mf - (k0 & ~DM_MASK) - t - 16) + (row & 1) + 2 * k0;
+	const float2 *const hp = sh.sstab + lane;
+	float2 h = hp[(r.b < 0 ? 0 : (r.b >= D_SS_NPFB ? D_SS_NPFB - 1 : r.b)) * 64];
+	float w_lo = wp[32], w_hi = wp[0];
 	// An output's two components are the row totals in lanes 15 (re) and 31 (im): those two lanes store them themselves with an ALL-lane
 	// LDS write whose other lanes aim at a scratch word of their own -- no lane reads, no exec masking on the loop's path.  The
 	// per-sample output counts collect in a register, one lane per input sample of the chunk, and go to LDS once per chunk.
 	const bool out_lane = lane == 15 || lane == 31;
-	float *const out_base = out_lane ? (float *)sh.outq + (lane == 31 ? 1 : 0) : sh.sink + lane;
-	const int out_stride = out_lane ? 2 : 0;
+	char *const out_base = out_lane ? (char *)((float *)sh.outq + (lane == 31 ? 1 : 0)) : (char *)(sh.sink + lane);
+	const uint32_t out_stride = out_lane ? (uint32_t)sizeof(cf) : 0u;
 	int cum_v = 0;
-	for (int k = k0; k < k1; k++) {
+	// one output from the window (wl, wh) through the filter bank h, and the loop's step to the next output's bank
+	auto output_step = [&](float wl, float wh) {
+		// four 18-tap dot products at once: row 0/1 = matched filter re/im, row 2/3 = derivative filter re/im
+		const float p = row_scan_sum(h.x * wl + h.y * wh);
+		if (__builtin_expect(r.j < sh.outq_cap, 1)) *(float *)(out_base + out_stride * (uint32_t)(r.j & (OUTQ_RING - 1))) = p;
+		r.j++;
+		const bool filter = r.decim == 2;        // wave-uniform: one scalar compare, one branch around the loop filter
+		r.decim = filter ? 1 : r.decim + 1;
+		if (filter) {
+			const float mx = lane_value(p, 15), my = lane_value(p, 31);
+			const float dx = lane_value(p, 47), dy = lane_value(p, 63);
+			float q = mx * dx + my * dy;
+			q = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);
+			r.q = q;
+			const float v0 = q - T.lf_a1 * r.v1;
+			r.qhat = T.lf_b0 * v0;
+			r.v1 = v0;
+			r.rate += T.ss_rate_adj * r.qhat;
+			r.del = r.rate + r.qhat;
+		}
+		r.tau += r.del;
+		r.bf = r.tau * (float)D_SS_NPFB;
+		r.b = (int)(r.bf + __builtin_copysignf(0x1.fffffep-2f, r.bf));
+	};
+	for (int k = k0; k < k1; k++, wp += 2) {
 		// the next input sample's window entries are fetched now, a whole iteration before they can be needed (sample k1 belongs to
 		// the next chunk and may still be in the making: that value is never used)
-		const float n_lo = base[2 * (k + 1)], n_hi = base[2 * (k + 1 - 16)];
+		const float n_lo = wp[34], n_hi = wp[2];
 		if (r.b < D_SS_NPFB) {
 			float wl = w_lo, wh = w_hi;
 			if (MASKED && k - (D_SS_TAPS - 1) < r.valid_from && row < 2) {          // matched-filter window entries from before the last reset are empty
 				if (k - t < r.valid_from) wl = 0.f;
 				if (k - t - 16 < r.valid_from) wh = 0.f;
 			}
-			int produced = 0;
-			do {
-				// four 18-tap dot products at once: row 0/1 = matched filter re/im, row 2/3 = derivative filter re/im
-				const float p = row_scan_sum(h.x * wl + h.y * wh);
-				if (__builtin_expect(r.j < sh.outq_cap, 1)) out_base[out_stride * (r.j & (OUTQ_RING - 1))] = div3(p);
-				r.j++;
-				if (r.decim == 2) {
-					r.decim = 0;
-					const float mx = lane_value(p, 15), my = lane_value(p, 31);
-					const float dx = lane_value(p, 47), dy = lane_value(p, 63);
-					float q = mx * dx + my * dy;
-					q = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);
-					r.q = q;
-					const float v0 = q - T.lf_a1 * r.v1;
-					r.qhat = T.lf_b0 * v0;
-					r.v1 = v0;
-					r.rate += T.ss_rate_adj * r.qhat;
-					r.del = r.rate + r.qhat;
-				}
-				r.decim++;
-				r.tau += r.del;
-				r.bf = r.tau * (float)D_SS_NPFB;
-				r.b = (int)roundf(r.bf);
-				produced++;
-				if (r.b < D_SS_NPFB) h = sh.sstab[(r.b < 0 ? 0 : r.b) * 64 + lane];      // another output from this input sample
-			} while (r.b < D_SS_NPFB && produced < 4);
+			output_step(wl, wh);
+			if (__builtin_expect(r.b < D_SS_NPFB, 0)) {      // another output from this input sample (four at the most, as liquid's buffer)
+				int produced = 1;
+				do {
+					h = hp[(r.b < 0 ? 0 : r.b) * 64];
+					output_step(wl, wh);
+					produced++;
+				} while (r.b < D_SS_NPFB && produced < 4);
+			}
 		}
 		r.tau -= 1.0f;
 		r.bf -= (float)D_SS_NPFB;
 		r.b -= D_SS_NPFB;
-		bi = r.b < 0 ? 0 : (r.b >= D_SS_NPFB ? D_SS_NPFB - 1 : r.b);
-		h = sh.sstab[bi * 64 + lane];                   // branch of the next input sample: fetched while the stores drain
+		const int lo = r.b > 0 ? r.b : 0;
+		h = hp[(lo < D_SS_NPFB - 1 ? lo : D_SS_NPFB - 1) * 64];      // branch of the next input sample: fetched while the stores drain
 		cum_v = (lane == k - k0) ? (r.j < 65535 ? r.j : 65535) : cum_v;
 		w_lo = n_lo; w_hi = n_hi;
 	}
@@ -318,7 +334,7 @@ struct CarrierRegs {
 	float eu, ev, ex2, ewx, ewy;   // equaliser: lane 1 + t (t < 15) of rows 0 and 1 = tap t (0 oldest); row 0 holds (x, y), row 1 (y, -x)
 	float px, py;                  // lane i < 16: PSK constellation entry i (demod_tables.h psk_pts)
 #ifdef HFDL_DM_PROBE               // experiment builds (profiles/probe_states.py): = 2 carrier-wave cycles per framer state, = 3 outputs per state,
-                                   // reported in the phase-cycle slots of the level tap
+                                   // reported in the phase-cycle slots of the level tap (= 4, = 5: wave 0's / wave 3's busy cycles, = 6: the sum over the steps of the longest wave, demod_block)
 	unsigned long long pa = 0, pb = 0, pc = 0;
 #endif
 };
@@ -402,7 +418,8 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 	const float lv_l = (lane < n) ? io.lvl[(k0 + lane) & DM_MASK] : 0.f;
 	const int cum_l = (lane < n) ? (int)sh.cum[(k0 + lane) & DM_MASK] : 0x7fffffff;
 	const int jbase = k0 > 0 ? (int)sh.cum[(k0 - 1) & DM_MASK] : 0;
-	const cf oq_l = (jbase + lane < sh.outq_cap) ? sh.outq[(jbase + lane) & (OUTQ_RING - 1)] : cf{0.f, 0.f};
+	cf oq_l = (jbase + lane < sh.outq_cap) ? sh.outq[(jbase + lane) & (OUTQ_RING - 1)] : cf{0.f, 0.f};
+	oq_l.x = div3(oq_l.x); oq_l.y = div3(oq_l.y);      // the ring holds the timing recovery's raw row totals (symsync_chunk): out = total / 3
 	{   // the chunk's outputs are taken from the 64 lanes of oq_l: a chunk that produced more (a timing loop far off its rate: up to four
 		// outputs per input sample) is cut where they end, and k1 tells the caller
 #ifndef HFDL_DM_OUT_LANES            // (a smaller value makes every chunk take the cut: how that path was tested, profiles/r03_experiments.md)
@@ -557,6 +574,50 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 			}
 		}
 	};
+	// The searching run, the sibling of the in-frame run.  Called behind a searching symbol that found nothing (the general iteration's
+	// plain searching path, below): the following symbols are all alike as long as the outputs stay paired, the carrier loop holds and
+	// nothing is found, and run here as one tight loop -- the same statements in the same order as the general iteration takes for each of
+	// them (pair step, equaliser, BPSK decision into the 127-bit window, correlation, carrier loop), without its state tests: what selected
+	// that path (searching, sampler on bits, BPSK, no countdown) is not changed by it, the output parity stays even, and the counters move
+	// once, after the run.  The run ends in front of a run-away's single step and at the chunk's last pair, both left to the next general
+	// iteration: `finished`, and (jo, y) is the run's last symbol (the caller's own if the run was empty).  It ends ON a detection or on the no-frame timeout: that symbol has gone
+	// through the pair step and the equaliser, as it has in the general iteration before the correlation is known, and nothing else of it
+	// is committed: `finished` is false and (jo, y) is that symbol, the caller's for on_symbol().  Placed there, not at the start of a
+	// chunk, so that on_symbol() is inlined once and an iteration inside a frame pays nothing for the run.
+	struct SearchRunEnd { bool finished; int jo; cf y; };
+	auto search_run = [&](int &j, int jo, cf y) {
+		bool finished = true;
+		const uint64_t room = (uint64_t)(NO_FRAME_TIMEOUT_FRAMES * SINGLE_SLOT_FRAME_LEN) - 1u - s.symbol_cnt;      // searching symbols that may still go by without the timeout
+		const int n_left = room > 64u ? 64 : (int)room;                  // (a chunk has at most 32 pairs)
+		int n_run = 0;
+		while (j + 1 < jstop && !runaway) {
+			pair_step(j);
+			jo = j + 1; j += 2;
+			y = equalise();
+			if (TAPS && lane == 0) io.tap_symbols[nsym] = y;
+			nsym++;
+			const bool neg = !(y.x > 0);
+			const uint32_t bit = (neg ? 1u : 0u) ^ (s.bitmask & 1u);
+			const uint64_t nhi = ((s.bits_hi << 1) | (s.bits_lo >> 63)) & 0x7FFFFFFFFFFFFFFFull, nlo = (s.bits_lo << 1) | bit;
+			const int m = bits_correlate(nhi, nlo, T.a_hi, T.a_lo);
+			n_run++;
+			if (__builtin_expect(!(m > T.a1_lo && m < T.a1_hi && n_run <= n_left), 0)) { finished = false; break; }
+			const float perr = y.y * (neg ? -1.0f : 1.0f) - y.x * 0.0f;
+			const float e = 0.5f * (fabsf(perr + COSTAS_ERR_LIMIT) - fabsf(perr - COSTAS_ERR_LIMIT));
+			s.err = e;
+			s.phi += COSTAS_ALPHA * e;
+			s.dphi += COSTAS_BETA * e;
+			s.bits_hi = nhi; s.bits_lo = nlo;
+			runaway = fabsf(s.dphi) > COSTAS_RUNAWAY_DPHI;
+		}
+		s.eq_count += 2u * (uint32_t)n_run;
+		s.symsync_out_idx += 2u * (uint32_t)n_run;
+		s.symbol_cnt += (uint64_t)(finished ? n_run : n_run - 1);      // the symbol that ended the run is on_symbol()'s to count
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 3
+		c.pa += (unsigned long long)n_run;
+#endif
+		return SearchRunEnd{finished, jo, y};
+	};
 	int j = jbase;
 	if (s.fr_state != FR_A1) in_frame_run(j);
 	while (j < jstop) {
@@ -611,7 +672,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 			jo = j; j++; s.symsync_out_idx++;
 		}
 		if (on_time) {
-			const cf y = equalise();
+			cf y = equalise();
 			if (s.fr_state == FR_EQ_TRAIN) {
 				bool run = true;
 				if (!s.eq_full) { if (s.eq_count < (uint32_t)D_EQ) run = false; else s.eq_full = 1; }
@@ -642,7 +703,8 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 					s.symbol_cnt++;
 					s.bits_hi = nhi; s.bits_lo = nlo;
 					runaway = fabsf(s.dphi) > COSTAS_RUNAWAY_DPHI;
-					plain = true;
+					const SearchRunEnd end = search_run(j, jo, y);      // the searching symbols that follow, as one tight loop
+					plain = end.finished; jo = end.jo; y = end.y;           // not finished: (jo, y) is on_symbol()'s
 				}
 			}
 			else if (s.symbols_wanted > 1) {
@@ -795,6 +857,9 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	if (wave == 3) {
 		for (int step = 0; pp.s3_done < n_out; step++) {
 			int *mb = sh.mbox + 8 * (step & 1);
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 5
+			const unsigned long long tb = __builtin_amdgcn_s_memtime();
+#endif
 			int to = pp.rs_ready;
 			if (to < n_out) {
 				to = to + DM_CHUNK < n_out ? to + DM_CHUNK : n_out;
@@ -818,6 +883,9 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 				if (hi > in_loaded) in_loaded = hi;
 			}
 			if (lane == 0) mb[4] = to;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 5
+			busy += __builtin_amdgcn_s_memtime() - tb;
+#endif
 			__syncthreads();
 			pp.read(mb);
 		}
@@ -826,11 +894,19 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 		float agc_g = S.agc_g, agc_y2 = S.agc_y2;
 		for (int step = 0; pp.s3_done < n_out; step++) {
 			int *mb = sh.mbox + 8 * (step & 1);
+#if defined(HFDL_DM_PROBE) && (HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 6)
+			const unsigned long long tb = __builtin_amdgcn_s_memtime();
+#endif
 			int to = pp.mf_ready + DM_CHUNK < pp.rs_ready ? pp.mf_ready + DM_CHUNK : pp.rs_ready;
 			// the matched-filter ring keeps what a restart of wave 1 can read (in step, wave 2 is two chunks behind and this never binds)
 			if (to > pp.s3_done + DM_MF_AHEAD) to = pp.s3_done + DM_MF_AHEAD;
 			if (to > pp.mf_ready) agc_mf_chunk<TAPS>(agc_g, agc_y2, T, io, pp.mf_ready, to, lane); else to = pp.mf_ready;
 			if (lane == 0) mb[0] = to;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 4
+			busy += __builtin_amdgcn_s_memtime() - tb;
+#elif defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
+			if (lane == 0) mb[5] = (int)(__builtin_amdgcn_s_memtime() - tb);
+#endif
 			__syncthreads();
 			pp.read(mb);
 		}
@@ -861,6 +937,9 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 			}
 			if (lane == 0) mb[1] = to;
 			if (TAPS) busy += __builtin_amdgcn_s_memtime() - tb;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
+			if (TAPS && lane == 0) mb[6] = (int)(__builtin_amdgcn_s_memtime() - tb);
+#endif
 			__syncthreads();
 			pp.read(mb);
 		}
@@ -879,11 +958,20 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 			if (to > pp.s3_done) reset_at = carrier_chunk<TAPS>(cr, s3, a, T, io, sh, pp.s3_done, to, nsym, lane); else to = pp.s3_done;
 			if (lane == 0) { mb[2] = reset_at >= 0 ? reset_at + 1 : to; mb[3] = reset_at >= 0; }
 			if (TAPS) busy += __builtin_amdgcn_s_memtime() - tb;
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
+			if (TAPS && lane == 0) mb[7] = (int)(__builtin_amdgcn_s_memtime() - tb);
+#endif
 			__syncthreads();
 			pp.read(mb);
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
+			{   // the step lasts as long as its longest wave: what the sum of these leaves of P is the barrier and mailbox step itself
+				const int m01 = mb[5] > mb[6] ? mb[5] : mb[6];
+				cr_probe[0] += (unsigned long long)(m01 > mb[7] ? m01 : mb[7]);
+			}
+#endif
 		}
 		carrier_store(cr, a, lane);
-#ifdef HFDL_DM_PROBE
+#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE != 6
 		cr_probe[0] = cr.pa; cr_probe[1] = cr.pb; cr_probe[2] = cr.pc;
 #endif
 		if (lane == 0) {
@@ -911,7 +999,16 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 		if (wave == 2 && lane == 0) io.tap_level[io.cap - 1] = (float)busy;
 #ifdef HFDL_DM_PROBE
 		__syncthreads();
+#if HFDL_DM_PROBE == 2 || HFDL_DM_PROBE == 3
 		if (wave == 2 && lane == 0) { io.tap_level[io.cap - 4] = (float)cr_probe[0]; io.tap_level[io.cap - 3] = (float)cr_probe[1]; io.tap_level[io.cap - 2] = (float)cr_probe[2]; }
+#elif HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 5
+		// busy cycles of wave 0 (= 4: AGC + matched filter) or wave 3 (= 5: resampler + input fetch), counted like waves 1 and 2 from the
+		// step's start to the mailbox write, in the slot of the cycles ahead of the pipeline (profiles/wave_cycles.py)
+		if (wave == (HFDL_DM_PROBE == 4 ? 0 : 3) && lane == 0) io.tap_level[io.cap - 4] = (float)busy;
+#elif HFDL_DM_PROBE == 6
+		// the sum over the steps of the longest of waves 0, 1, 2 in that step (each wave leaves its step's busy cycles in the mailbox)
+		if (wave == 2 && lane == 0) io.tap_level[io.cap - 4] = (float)cr_probe[0];
+#endif
 #endif
 	}
 	return n_out;

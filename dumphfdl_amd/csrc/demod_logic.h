@@ -129,6 +129,13 @@ struct BlockIo {
 	int channel;
 };
 
+// The timing loop's rate after a reset: k / k_out = 3 / 2 (symsync_crcf_reset).  TEST-ONLY override (dumphfdl_amd/csrc/build_start_rate.sh,
+// tests/test_gpu_demod_search_run.py): with a start rate of about 1 an input sample yields 0, 1 or 2 timing-recovery outputs, which no
+// input can make the loop do from 3 / 2; the product is never built with it.
+#ifndef HFDL_DM_SS_RATE0
+#define HFDL_DM_SS_RATE0 1.5f
+#endif
+
 HFDL_HD void chan_state_init(ChanState &st, const float *eq_h0)
 {
 	ChanScalars &s = st.s;
@@ -137,7 +144,7 @@ HFDL_HD void chan_state_init(ChanState &st, const float *eq_h0)
 	for (unsigned i = 0; i < sizeof(ChanState); i++) p[i] = 0;
 	s.agc_g = 1.0f; s.agc_y2 = 1.0f;          // agc_crcf_create + reset
 	s.noise_floor = 1.0f;                     // src/hfdl.c:490
-	s.ss_rate = 1.5f; s.ss_del = 1.5f;        // k / k_out = 3 / 2
+	s.ss_rate = HFDL_DM_SS_RATE0; s.ss_del = HFDL_DM_SS_RATE0;
 	for (int i = 0; i < D_EQ; i++) { a.eq_w[i].x = eq_h0[i]; a.eq_w[i].y = 0.f; }
 	// framer_reset, src/hfdl.c:974-991
 	s.fr_state = FR_A1; s.symbols_wanted = 1; s.cur_arity = 1; s.s_state = SAMPLER_BITS;
@@ -335,7 +342,7 @@ HFDL_FN void symsync_reset(ChanScalars &s, ChanArrays &a)
 {
 	// symsync_crcf_reset clears the matched-filter window only
 	for (int i = 0; i < D_SS_TAPS; i++) { a.ss_mf[i].x = 0.f; a.ss_mf[i].y = 0.f; }
-	s.ss_rate = 1.5f; s.ss_del = 1.5f;
+	s.ss_rate = HFDL_DM_SS_RATE0; s.ss_del = HFDL_DM_SS_RATE0;
 	s.ss_b = 0; s.ss_bf = 0.f; s.ss_tau = 0.f; s.ss_q = 0.f; s.ss_qhat = 0.f;
 	s.ss_decim = 0; s.ss_v1 = 0.f;
 	s.ev_flags |= EV_SS_RESET;
