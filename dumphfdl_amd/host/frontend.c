@@ -14,52 +14,68 @@
 #include "hfdl_gpu.h"
 #include "host_internal.h"
 
+/* The two optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
+ * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
+struct spectrum_settings { const char *path; int32_t bins, interval_s; int hann; };                         /* path NULL = off */
+struct iq_export_settings { const char *dir; const int32_t *freqs; int32_t nfreqs; int format; float scale; };  /* dir NULL = off */
+
+static struct spectrum_settings spectrum_settings_copy(const struct spectrum_settings *s)
+{
+	struct spectrum_settings c = *s;
+	c.path = s->path ? strdup(s->path) : NULL;
+	return c;
+}
+
+static void spectrum_settings_free(struct spectrum_settings *s) { free((char *)s->path); }
+
+static struct iq_export_settings iq_export_settings_copy(const struct iq_export_settings *s)
+{
+	struct iq_export_settings c = *s;
+	c.dir = s->dir ? strdup(s->dir) : NULL;
+	c.nfreqs = s->dir ? s->nfreqs : 0;
+	int32_t *freqs = s->dir ? hfdl_xcalloc(c.nfreqs > 0 ? (size_t)c.nfreqs : 1, sizeof(int32_t)) : NULL;
+	if (c.nfreqs > 0) memcpy(freqs, s->freqs, (size_t)c.nfreqs * sizeof(int32_t));
+	c.freqs = freqs;
+	return c;
+}
+
+static void iq_export_settings_free(struct iq_export_settings *s)
+{
+	free((char *)s->dir);
+	free((int32_t *)s->freqs);
+}
+
 struct gpu_fft_block {
 	struct block block;
 	int32_t decimation;
 	float transition_bw;
 	int device;
 	hfdl_gpu_geometry geo;
-	char *spec_path;                 /* spectrum monitor as set when fft_create() ran (hfdl_frontend_set_spectrum); NULL = off */
-	int32_t spec_bins, spec_interval_s;
-	int spec_hann;
-	char *iqx_dir;                   /* channel baseband export as set when fft_create() ran (hfdl_frontend_set_iq_export); NULL = off */
-	int32_t *iqx_freqs, iqx_nfreqs;
-	int iqx_format;
-	float iqx_scale;
+	struct spectrum_settings spectrum;       /* as set when fft_create() ran */
+	struct iq_export_settings iqx;
 };
 
 static int g_device = 0;
 void hfdl_frontend_set_device(int device) { g_device = device; }
 
-/* spectrum monitor of the next front end (hfdl_frontend_set_spectrum): path NULL = off */
-static struct { char *path; int32_t bins, interval_s; int hann; } g_spectrum;
+static struct spectrum_settings g_spectrum;
 int hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t interval_s, int hann)
 {
 	if (path != NULL && (bins < 16 || bins > 4096 || (bins & (bins - 1)) != 0 || interval_s < 1)) return -1;
-	free(g_spectrum.path);
-	g_spectrum.path = path ? strdup(path) : NULL;
-	g_spectrum.bins = bins; g_spectrum.interval_s = interval_s; g_spectrum.hann = hann;
+	const struct spectrum_settings given = { path, bins, interval_s, hann };
+	spectrum_settings_free(&g_spectrum);
+	g_spectrum = spectrum_settings_copy(&given);
 	return 0;
 }
 
-/* channel baseband export of the next front end (hfdl_frontend_set_iq_export): dir NULL = off */
-static struct { char *dir; int32_t *freqs, nfreqs; int format; float scale; } g_iqx;
-static int32_t *copy_freqs(const int32_t *freqs, int32_t n)
-{
-	int32_t *c = hfdl_xcalloc(n > 0 ? (size_t)n : 1, sizeof(int32_t));
-	if (n > 0) memcpy(c, freqs, (size_t)n * sizeof(int32_t));
-	return c;
-}
+static struct iq_export_settings g_iqx;
 int hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t nfreqs, int format, float scale)
 {
 	if (dir != NULL && (nfreqs < 0 || (nfreqs > 0 && freqs == NULL) || (format != HFDL_GPU_EXPORT_CF32 && format != HFDL_GPU_EXPORT_CS16)
 			|| (format == HFDL_GPU_EXPORT_CS16 && !(scale > 0.f && isfinite(scale))))) return -1;
-	free(g_iqx.dir);
-	free(g_iqx.freqs);
-	g_iqx.dir = dir ? strdup(dir) : NULL;
-	g_iqx.freqs = dir ? copy_freqs(freqs, nfreqs) : NULL;
-	g_iqx.nfreqs = dir ? nfreqs : 0; g_iqx.format = format; g_iqx.scale = scale;
+	const struct iq_export_settings given = { dir, freqs, nfreqs, format, scale };
+	iq_export_settings_free(&g_iqx);
+	g_iqx = iq_export_settings_copy(&given);
 	return 0;
 }
 
@@ -259,12 +275,110 @@ int32_t hfdl_nf_stats_thread_start(struct block **channel_block_list, int32_t ch
 
 /* ---- the front-end thread ---- */
 
-static uint64_t g_lpdu_tally[4];      /* MPDUs walked, LPDUs processed / good / bad FCS: front-end thread only, copied into the run stats at shutdown */
+#define PDU_BATCH 1024
 
-static void push_pdu(const hfdl_gpu_pdu *p, const struct timeval *t0)
+/* Blocks that can be pushed before a launch has run and the thread has looked again: the blocks of two halves and the uploads ahead
+ * of them, and as many again.  The spectrum history (were every block a row of its own) and the export ring hold that many. */
+#define UNCOLLECTED_BLOCKS_MAX (2 * (2 * HFDL_GPU_FOLD_BATCH_MAX + HFDL_GPU_PREFETCH_MAX + 2))
+
+/* Upload bookkeeping.  The GPU library numbers host blocks in the order their copies were queued, pushed directly or uploaded ahead
+ * of their push.  The ring slots of the newest `leased` of them may still be read by the DMA engine; they lie at the ring's head,
+ * oldest first, so the next block to take lies right behind them.  A block that went through the bounce buffer is a host block
+ * but leases no slot. */
+struct uploads {
+	uint64_t count;                  /* host blocks whose copy has been queued */
+	size_t leased;
+	size_t depth;                    /* uploads that may wait for their push */
+	const void *queued[HFDL_GPU_PREFETCH_MAX + 1];      /* uploads not pushed yet, oldest at q_head */
+	size_t q_head, q_len;
+};
+
+static size_t uploads_next_offset(const struct uploads *u, size_t need) { return u->leased * need; }
+static uint64_t uploads_oldest_leased(const struct uploads *u) { return u->count - u->leased; }
+static void uploads_slot_returned(struct uploads *u) { u->leased--; }
+static void uploads_forget(struct uploads *u) { u->leased = 0; u->q_len = 0; }
+
+static void uploads_pushed_direct(struct uploads *u, bool from_ring)
+{
+	u->count++;
+	if (from_ring) u->leased++;
+}
+
+static void uploads_queued_ahead(struct uploads *u, const void *blk)
+{
+	u->queued[(u->q_head + u->q_len) % (HFDL_GPU_PREFETCH_MAX + 1)] = blk;
+	u->q_len++;
+	u->count++;
+	u->leased++;
+}
+
+/* its slot was leased when the copy was queued */
+static void uploads_pushed_queued(struct uploads *u)
+{
+	u->q_head = (u->q_head + 1) % (HFDL_GPU_PREFETCH_MAX + 1);
+	u->q_len--;
+}
+
+/* spectrum monitor: one CSV line per interval of SIGNAL (blocks pushed x block length / sample rate): a row of the device's history */
+struct spectrum_csv {
+	FILE *file;                      /* NULL = off */
+	int32_t bins;
+	char *line;
+	size_t line_cap;
+	float *mean;
+	uint64_t closed, next;           /* intervals closed so far; the first row not written yet */
+};
+
+/* Channel baseband export: one file per selected channel; finished blocks are collected IQX_CHUNK at a time (wait = 0: never waits for
+ * a kernel stream; wait = 1, at the end of a run: everything queued) and each block's valid samples appended to its channel's file. */
+#define IQX_CHUNK 4
+struct iq_export {
+	int32_t nsel, row;               /* selected channels; samples a row holds (geometry.max_outputs_per_block) */
+	size_t es;                       /* bytes per sample */
+	FILE **files;                    /* NULL = off */
+	char *samples;
+	int32_t *counts;
+	hfdl_gpu_export_block info[IQX_CHUNK];
+	uint64_t next;                   /* the first block not written yet */
+	uint64_t lost;                   /* blocks the ring overwrote before they could be written: named once, counted, the total reported at the end */
+};
+
+struct fe_thread {
+	struct block *block;
+	struct gpu_fft_block *fb;
+	struct circ_buffer *ring;        /* the page-locked input ring in front of this block */
+	hfdl_gpu_frontend *fe;
+	bool ok;                         /* false once the run has failed: what arrives is dropped until the producer shuts down */
+	size_t nch;
+	int32_t *freqs;
+	double fs, centerfreq;           /* of the receiver */
+	size_t need;                     /* samples of a block */
+	int gfmt;                        /* HFDL_GPU_SFMT_* of the ring's samples */
+	struct timeval t0;               /* wall clock at stream start */
+	hfdl_gpu_pdu *pdus;
+	hfdl_gpu_channel_stats *stats;
+	struct uploads up;
+	void *bounce;                    /* only for a ring whose blocks are not contiguous (never one made by this library) */
+	uint64_t undelivered;            /* blocks pushed since the pipeline was last drained */
+	struct timespec last_push;       /* when the newest block was taken from the ring and pushed (CLOCK_REALTIME: pthread_cond_timedwait's clock) */
+	double grace;
+	struct spectrum_csv csv;
+	struct iq_export iqx;
+	double t_first;
+	struct hfdl_run_stats rs;        /* where this thread's time went and what it moved; published once, at shutdown */
+};
+
+static void fail(struct fe_thread *t, const char *text)
+{
+	fprintf(stderr, "GPU front end: %s\n", text);
+	do_exit = 1;
+	t->ok = false;
+}
+
+static void push_pdu(struct fe_thread *t, const hfdl_gpu_pdu *p)
 {
 	if (p->fcs_status == HFDL_GPU_FCS_GOOD && p->pdu_kind != HFDL_GPU_KIND_SPDU) {
-		g_lpdu_tally[0]++; g_lpdu_tally[1] += p->lpdus_processed; g_lpdu_tally[2] += p->lpdus_good; g_lpdu_tally[3] += p->lpdus_bad_fcs;
+		t->rs.mpdus_walked++; t->rs.lpdus_processed += p->lpdus_processed; t->rs.lpdus_good += p->lpdus_good; t->rs.lpdus_bad_fcs += p->lpdus_bad_fcs;
 	}
 	struct metadata *m = hfdl_pdu_metadata_create();
 	struct hfdl_pdu_metadata *hm = container_of(m, struct hfdl_pdu_metadata, metadata);
@@ -276,13 +390,29 @@ static void push_pdu(const hfdl_gpu_pdu *p, const struct timeval *t0)
 	hm->bit_rate = p->bit_rate;
 	hm->slot = p->slot;
 	/* start of frame = A2 detection - (prekey + 2 A) symbols (src/hfdl.c:657-660), on the stream's sample clock */
-	double t = (double)t0->tv_sec + 1e-6 * (double)t0->tv_usec + (double)p->sample_index / (HFDL_SYMBOL_RATE * SPS)
+	double ts = (double)t->t0.tv_sec + 1e-6 * (double)t->t0.tv_usec + (double)p->sample_index / (HFDL_SYMBOL_RATE * SPS)
 		- (448.0 + 2 * 127.0) / HFDL_SYMBOL_RATE;
-	m->rx_timestamp.tv_sec = (time_t)floor(t);
-	m->rx_timestamp.tv_usec = (suseconds_t)((t - floor(t)) * 1e6);
+	m->rx_timestamp.tv_sec = (time_t)floor(ts);
+	m->rx_timestamp.tv_usec = (suseconds_t)((ts - floor(ts)) * 1e6);
 	uint8_t *copy = hfdl_xcalloc((size_t)p->len ? (size_t)p->len : 1, 1);
 	memcpy(copy, p->octets, (size_t)p->len);
 	pdu_decoder_queue_push(m, octet_string_new(copy, (size_t)p->len), 0);
+}
+
+/* The poll -> push_pdu loop.  draining: everything pushed so far is folded, demodulated and delivered (the half being filled is
+ * closed as it is).  Otherwise only what is known to be complete, without draining anything and WITHOUT waiting: what this thread may
+ * queue ahead is bounded by the ring slots it leases to the uploads (it sleeps in release_copied() when the ring has nothing new and
+ * the oldest upload is still running), and slots can only go back to the producer while this thread is not blocked elsewhere.
+ * Ring mutex: not held (calls the device library and the downstream queue). */
+static void deliver_pdus(struct fe_thread *t, bool draining)
+{
+	int32_t n = 0;
+	do {
+		if ((draining ? hfdl_gpu_frontend_poll_pdus(t->fe, t->pdus, PDU_BATCH, &n)
+				: hfdl_gpu_frontend_poll_pdus_ready(t->fe, t->pdus, PDU_BATCH, &n, 2)) != 0) break;
+		for (int32_t i = 0; i < n; i++) push_pdu(t, &t->pdus[i]);
+		t->rs.pdus += (uint64_t)n;
+	} while (n == PDU_BATCH);
 }
 
 static struct hfdl_run_stats g_run;
@@ -309,88 +439,108 @@ static int gpu_format_of(int ring_fmt)
 
 /* give ring slots back to the producer, oldest first, as the DMA engine finishes reading them.  wait_for_one: block until at least
  * the oldest copy is done (the caller is about to sleep and the producer may be waiting for room); otherwise only what is done
- * already.  Returns 0, or -1 if the state of a copy cannot be established (the slot is kept: the producer must never overwrite
- * memory the DMA engine may still read). */
-static int release_copied(hfdl_gpu_frontend *fe, struct circ_buffer *ring, size_t need, uint64_t uploads, size_t *leased, bool wait_for_one)
+ * already.  If the state of a copy cannot be established the run fails and the slot is kept: the producer must never overwrite
+ * memory the DMA engine may still read.
+ * Ring mutex: not held on entry or on return; taken only around the drop. */
+static void release_copied(struct fe_thread *t, bool wait_for_one)
 {
-	while (*leased > 0) {
-		const uint64_t oldest = uploads - *leased;
+	while (t->up.leased > 0) {
+		const uint64_t oldest = uploads_oldest_leased(&t->up);
+		int done;                        /* 1 = the oldest copy has finished, 0 = not yet, negative = unknown */
 		if (wait_for_one) {
-			if (hfdl_gpu_frontend_input_done_upto(fe, oldest) != 0 && hfdl_gpu_frontend_input_done(fe) != 0) return -1;
+			done = hfdl_gpu_frontend_input_done_upto(t->fe, oldest) == 0 || hfdl_gpu_frontend_input_done(t->fe) == 0 ? 1 : -1;
 			wait_for_one = false;
 		} else {
-			const int done = hfdl_gpu_frontend_input_copied(fe, oldest);
-			if (done < 0) return -1;
-			if (done == 0) break;
+			done = hfdl_gpu_frontend_input_copied(t->fe, oldest);
 		}
-		pthread_mutex_lock(ring->mutex);
-		hfdl_ring_drop(ring->buf, need);
-		pthread_mutex_unlock(ring->mutex);
-		pthread_cond_signal(ring->cond);
-		(*leased)--;
+		if (done < 0) { fail(t, hfdl_gpu_last_error()); return; }
+		if (done == 0) break;
+		pthread_mutex_lock(t->ring->mutex);
+		hfdl_ring_drop(t->ring->buf, t->need);
+		pthread_mutex_unlock(t->ring->mutex);
+		pthread_cond_signal(t->ring->cond);
+		uploads_slot_returned(&t->up);
 	}
-	return 0;
 }
 
-/* The front-end thread.  A block never gets copied on the host: the ring in front of this block is page-locked and a whole
- * number of blocks long (block_connect_one2one), so each block is handed to the GPU where it lies -- raw cs16 / cu8 samples
- * included, which the device converts -- and its slot goes back to the producer once the DMA has read it.
- *
- * Uploads run AHEAD of the blocks that compute: whatever whole blocks the ring holds beyond the one being pushed are queued for
- * upload at once (hfdl_gpu_frontend_prefetch_block_raw, up to geometry.prefetch_depth of them), so the copy engine keeps working
- * while this thread waits for the GPU in the collection call -- the fold of a 40 Msps x 256-channel half takes 3 ms, five blocks
- * of PCIe time.
- *
- * Live source or replay?  The pipeline is drained (everything pushed so far folded, demodulated and delivered at once) only when
- * the ring has run EMPTY and the source has stayed silent for a grace period of a quarter of a block's own duration (at most
- * 20 ms), counted from the arrival of the newest block: a live radio delivers a block every block duration and gets its PDUs within that grace; a file reader that hiccups for
- * a millisecond beside a GPU about as fast as itself never drains a filled pipeline (round 4's fixed 0.5 ms grace did, five times
- * in a run, for 19 % of the rate). */
 /* Rows of the spectrum history the device has finished (wait = 0: never waits for a kernel stream; wait = 1, at the end of a run: every
- * closed row), one rtl_power line each, in row order, from row `next` on.  Returns the first row not written yet.  A row the ring has
- * overwritten before it was written is named on stderr. */
-#define SPEC_ROWS (2 * (2 * HFDL_GPU_FOLD_BATCH_MAX + HFDL_GPU_PREFETCH_MAX + 2))
-static uint64_t write_spectrum_rows(hfdl_gpu_frontend *fe, const hfdl_gpu_geometry *geo, double fs, double centerfreq, const struct timeval *t0,
-		FILE *out, float *mean, char *line, int32_t bins, uint64_t next, int wait)
+ * closed row), one rtl_power line each, in row order, from row x->next on.  A row the ring has overwritten before it was written is
+ * named on stderr. */
+static void spectrum_csv_write_rows(struct fe_thread *t, int wait)
 {
-	const double step = (double)(geo->fft_size / bins) * fs / (double)geo->fft_size;
-	const double low = centerfreq - (0.5 * (double)geo->fft_size + 0.5) * fs / (double)geo->fft_size;
+	struct spectrum_csv *x = &t->csv;
+	const hfdl_gpu_geometry *geo = &t->fb->geo;
+	const double step = (double)(geo->fft_size / x->bins) * t->fs / (double)geo->fft_size;
+	const double low = t->centerfreq - (0.5 * (double)geo->fft_size + 0.5) * t->fs / (double)geo->fft_size;
 	for (;;) {
 		hfdl_gpu_spectrum_row info;
 		int32_t n = 0;
-		uint64_t after = next;
-		if (hfdl_gpu_frontend_spectrum_rows(fe, 0, next, 1, mean, NULL, &info, &n, &after, wait) != 0) {
+		uint64_t after = x->next;
+		if (hfdl_gpu_frontend_spectrum_rows(t->fe, 0, x->next, 1, x->mean, NULL, &info, &n, &after, wait) != 0) {
 			fprintf(stderr, "spectrum monitor: %s\n", hfdl_gpu_last_error());
-			return next;
+			return;
 		}
-		if (n == 0) return after;
-		for (uint64_t lost = next; lost < info.row; lost++)
+		if (n == 0) { x->next = after; return; }
+		for (uint64_t lost = x->next; lost < info.row; lost++)
 			fprintf(stderr, "spectrum monitor: interval %llu has no line: its row was overwritten before it could be written\n", (unsigned long long)lost);
+		x->next = after;
 		/* stamped like the PDUs: wall clock at stream start + the signal time of the first block averaged */
-		const double t = (double)t0->tv_sec + 1e-6 * (double)t0->tv_usec + (double)info.first_block * (double)geo->input_size / fs;
-		if (hfdl_spectrum_csv_line(line, 64 + 12 * (size_t)bins, t, low, step, info.blocks, mean, bins) > 0) {
-			fputs(line, out);
-			fflush(out);
+		const double ts = (double)t->t0.tv_sec + 1e-6 * (double)t->t0.tv_usec + (double)info.first_block * (double)geo->input_size / t->fs;
+		if (hfdl_spectrum_csv_line(x->line, x->line_cap, ts, low, step, info.blocks, x->mean, x->bins) > 0) {
+			fputs(x->line, x->file);
+			fflush(x->file);
 		} else {
 			fprintf(stderr, "spectrum monitor: interval %llu has no line: it does not fit the line buffer\n", (unsigned long long)info.row);
 		}
-		next = after;
 	}
 }
 
-/* Channel baseband export: one file per selected channel; finished blocks are collected IQX_CHUNK at a time (wait = 0: never waits for
- * a kernel stream; wait = 1, at the end of a run: everything queued) and each block's valid samples appended to its channel's file. */
-#define IQX_CHUNK 4
-struct iq_export {
-	int32_t nsel, row;               /* selected channels; samples a row holds (geometry.max_outputs_per_block) */
-	size_t es;                       /* bytes per sample */
-	FILE **files;
-	char *samples;
-	int32_t *counts;
-	hfdl_gpu_export_block info[IQX_CHUNK];
-	uint64_t next;                   /* the first block not written yet */
-	uint64_t lost;                   /* blocks the ring overwrote before they could be written: named once, counted, the total reported at the end */
-};
+/* opens the file and turns the monitor and its history on; 0, or -1 with the reason on stderr and nothing left open */
+static int spectrum_csv_open(struct fe_thread *t)
+{
+	struct spectrum_csv *x = &t->csv;
+	const struct spectrum_settings *set = &t->fb->spectrum;
+	x->bins = set->bins;
+	while (x->bins > t->fb->geo.fft_size / 16) x->bins /= 2;
+	x->file = fopen(set->path, "w");       /* a run writes its own file: nothing of an earlier run stays in front of it */
+	if (x->file == NULL || hfdl_gpu_frontend_spectrum_enable(t->fe, x->bins, set->hann ? HFDL_GPU_SPECTRUM_HANN : 0u) != 0
+			|| hfdl_gpu_frontend_spectrum_history(t->fe, UNCOLLECTED_BLOCKS_MAX, 0) != 0) {
+		fprintf(stderr, "spectrum monitor: %s\n", x->file ? hfdl_gpu_last_error() : "cannot open the spectrum file");
+		if (x->file) fclose(x->file);
+		x->file = NULL;
+		return -1;
+	}
+	x->mean = hfdl_xcalloc((size_t)x->bins, sizeof(float));
+	x->line_cap = 64 + 12 * (size_t)x->bins;
+	x->line = hfdl_xcalloc(x->line_cap, 1);
+	return 0;
+}
+
+/* after a push: an interval boundary closes the open row (no device call); finished rows are written as they are found, without waiting */
+static void spectrum_csv_step(struct fe_thread *t)
+{
+	struct spectrum_csv *x = &t->csv;
+	if ((double)t->rs.blocks * (double)t->need / t->fs >= (double)(x->closed + 1) * (double)t->fb->spectrum.interval_s) {
+		uint64_t row = 0;
+		if (hfdl_gpu_frontend_spectrum_row_close(t->fe, &row) != 0)
+			fprintf(stderr, "spectrum monitor: interval %llu has no line: %s\n", (unsigned long long)x->closed, hfdl_gpu_last_error());
+		x->closed++;
+	}
+	spectrum_csv_write_rows(t, 0);
+}
+
+/* at the end of a run, while the front end still exists: every closed row not written yet, then the file is closed */
+static void spectrum_csv_close(struct fe_thread *t)
+{
+	struct spectrum_csv *x = &t->csv;
+	if (x->file != NULL) {
+		spectrum_csv_write_rows(t, 1);
+		fclose(x->file);
+	}
+	free(x->mean);
+	free(x->line);
+	memset(x, 0, sizeof(*x));
+}
 
 static void write_iq_export(hfdl_gpu_frontend *fe, struct iq_export *x, int wait)
 {
@@ -428,304 +578,296 @@ static void iq_export_close(struct iq_export *x)
 	memset(x, 0, sizeof(*x));
 }
 
-/* selects the channels, opens their files and turns the export on; 0, or -1 with the reason on stderr */
+/* selects the channels, opens their files and turns the export on; 0, or -1 with the reason on stderr and nothing left open */
 static int iq_export_open(hfdl_gpu_frontend *fe, const struct gpu_fft_block *fb, struct hfdl_channel_slot **slots, size_t nch, struct iq_export *x)
 {
-	const int32_t nsel = fb->iqx_nfreqs > 0 ? fb->iqx_nfreqs : (int32_t)nch;
+	const struct iq_export_settings *set = &fb->iqx;
+	const int32_t nsel = set->nfreqs > 0 ? set->nfreqs : (int32_t)nch;
 	int32_t *sel = hfdl_xcalloc((size_t)nsel, sizeof(int32_t));
 	int rc = 0;
 	for (int32_t s = 0; s < nsel && rc == 0; s++) {
-		size_t c = fb->iqx_nfreqs > 0 ? 0 : (size_t)s;
-		while (fb->iqx_nfreqs > 0 && c < nch && slots[c]->frequency != fb->iqx_freqs[s]) c++;
-		if (c == nch) { fprintf(stderr, "iq export: %d Hz is not a registered channel\n", fb->iqx_freqs[s]); rc = -1; }
+		size_t c = set->nfreqs > 0 ? 0 : (size_t)s;
+		while (set->nfreqs > 0 && c < nch && slots[c]->frequency != set->freqs[s]) c++;
+		if (c == nch) { fprintf(stderr, "iq export: %d Hz is not a registered channel\n", set->freqs[s]); rc = -1; }
 		sel[s] = (int32_t)c;
 	}
 	x->nsel = nsel;
 	x->row = fb->geo.max_outputs_per_block;
-	x->es = fb->iqx_format == HFDL_GPU_EXPORT_CS16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
+	x->es = set->format == HFDL_GPU_EXPORT_CS16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
 	x->files = hfdl_xcalloc((size_t)nsel, sizeof(FILE *));
 	x->samples = hfdl_xcalloc((size_t)IQX_CHUNK * (size_t)nsel * (size_t)x->row, x->es);
 	x->counts = hfdl_xcalloc((size_t)IQX_CHUNK * (size_t)nsel, sizeof(int32_t));
 	for (int32_t s = 0; s < nsel && rc == 0; s++) {
-		const size_t cap = strlen(fb->iqx_dir) + 32;
+		const size_t cap = strlen(set->dir) + 32;
 		char *path = hfdl_xcalloc(cap, 1);
-		snprintf(path, cap, "%s/%d.%s", fb->iqx_dir, slots[sel[s]]->frequency, fb->iqx_format == HFDL_GPU_EXPORT_CS16 ? "cs16" : "cf32");
+		snprintf(path, cap, "%s/%d.%s", set->dir, slots[sel[s]]->frequency, set->format == HFDL_GPU_EXPORT_CS16 ? "cs16" : "cf32");
 		if ((x->files[s] = fopen(path, "wb")) == NULL) { fprintf(stderr, "iq export: cannot open %s\n", path); rc = -1; }
 		free(path);
 	}
-	/* the ring holds what can be pushed before a block's launch has run and this thread has looked again (SPEC_ROWS), halved until
-	 * it fits the library's cap on a ring */
-	int32_t ring = SPEC_ROWS;
+	/* the ring is halved until it fits the library's cap on a ring */
+	int32_t ring = UNCOLLECTED_BLOCKS_MAX;
 	if (rc == 0) {
-		while ((rc = hfdl_gpu_frontend_export_enable(fe, sel, nsel, fb->iqx_format, fb->iqx_scale, ring)) == HFDL_GPU_ERANGE && ring > 2) ring /= 2;
+		while ((rc = hfdl_gpu_frontend_export_enable(fe, sel, nsel, set->format, set->scale, ring)) == HFDL_GPU_ERANGE && ring > 2) ring /= 2;
 		if (rc != 0) fprintf(stderr, "iq export: %s\n", hfdl_gpu_last_error());
 	}
 	free(sel);
+	if (rc != 0) iq_export_close(x);
 	return rc == 0 ? 0 : -1;
 }
 
-static void *frontend_thread(void *ctx)
+/* Ring mutex: held. */
+static bool next_block_is_there(const struct fe_thread *t)
 {
-	struct block *block = ctx;
-	struct gpu_fft_block *fb = container_of(block, struct gpu_fft_block, block);
-	struct circ_buffer *ring = &block->consumer.in->circ_buffer;
-	struct block_connection *down = block->producer.out;
-	hfdl_gpu_frontend *fe = NULL;
-	void *bounce = NULL;                    /* only for a ring whose blocks are not contiguous (never one made by this library) */
-	hfdl_gpu_pdu *pdus = NULL;
-	hfdl_gpu_channel_stats *stats = NULL;
-	const int32_t max_pdus = 1024;
+	return hfdl_ring_size(t->ring->buf) >= uploads_next_offset(&t->up, t->need) + t->need;
+}
 
-	struct hfdl_channel_slot *slots[MAX_SLOTS];
-	size_t nch = hfdl_channels_on_connection(down, slots, MAX_SLOTS);
-	int32_t *freqs = hfdl_xcalloc(nch ? nch : 1, sizeof(int32_t));
-	for (size_t i = 0; i < nch; i++) freqs[i] = slots[i]->frequency;
-	int ok = nch > 0 && hfdl_gpu_frontend_create(&fe, fb->device, slots[0]->sample_rate, slots[0]->centerfreq, freqs, (int32_t)nch) == 0;
-	if (!ok) {
-		fprintf(stderr, "GPU front end: %s\n", nch ? hfdl_gpu_last_error() : "no channels connected");
-		do_exit = 1;
-	} else {
-		hfdl_gpu_frontend_geometry(fe, &fb->geo);
-		hfdl_gpu_frontend_enable_taps(fe, 0);
-		pdus = hfdl_xcalloc((size_t)max_pdus, sizeof(*pdus));
-		stats = hfdl_xcalloc(nch, sizeof(*stats));
+/* The ring is empty: a live source, or a reader catching its breath?  Wait the grace period, then deliver.  The grace period counts
+ * from the moment the newest block was PUSHED, not from here (the wait for its upload lies in between): a live block's PDUs leave
+ * grace after its arrival, whatever the copy took.
+ * Ring mutex: held on entry and on return; dropped around the draining collection. */
+static void grace_then_drain(struct fe_thread *t)
+{
+	struct block_connection *in = t->block->consumer.in;
+	struct timespec until = t->last_push;
+	until.tv_nsec += (long)(t->grace * 1e9);
+	while (until.tv_nsec >= 1000000000) { until.tv_sec++; until.tv_nsec -= 1000000000; }
+	const double tg = now_s();
+	int rc = 0;
+	while (rc == 0 && !next_block_is_there(t) && !block_connection_is_shutdown_signaled(in))
+		rc = pthread_cond_timedwait(t->ring->cond, t->ring->mutex, &until);
+	t->rs.grace_s += now_s() - tg;
+	if (next_block_is_there(t) || block_connection_is_shutdown_signaled(in)) return;
+	pthread_mutex_unlock(t->ring->mutex);
+	deliver_pdus(t, true);
+	t->rs.drains++;
+	t->undelivered = 0;
+	pthread_mutex_lock(t->ring->mutex);
+}
+
+/* A block that wraps around the end of a ring this library did not size: one copy.  The blocks still leased to the DMA engine sit
+ * in front of it; they go back to the producer first.  Only a cf32 ring can be copied out of.
+ * Ring mutex: held on entry and on return; dropped while the leased slots go back. */
+static const void *bounce_block(struct fe_thread *t)
+{
+	pthread_mutex_unlock(t->ring->mutex);
+	while (t->ok && t->up.leased > 0) release_copied(t, true);
+	pthread_mutex_lock(t->ring->mutex);
+	if (t->ok && t->bounce == NULL) t->bounce = hfdl_xcalloc(t->need, sizeof(float complex));
+	if (t->ok && hfdl_ring_read(t->ring->buf, t->bounce, t->need) != t->need)
+		fail(t, "input ring holds raw samples in blocks that are not contiguous");
+	return t->bounce;
+}
+
+/* The next block to push: one uploaded ahead if there is one, else the next whole block of the ring, waited for.
+ * TOOK_NOTHING: the run has failed; what the ring held was dropped, go round again (until the producer shuts down).
+ * Ring mutex: not held on entry, not held on return. */
+enum took { TOOK_BLOCK, TOOK_SHUTDOWN, TOOK_NOTHING };
+static enum took take_block(struct fe_thread *t, const void **blk, bool *from_bounce)
+{
+	struct circ_buffer *ring = t->ring;
+	*from_bounce = false;
+	if (t->up.q_len > 0) {
+		*blk = t->up.queued[t->up.q_head];            /* uploaded ahead: only its kernels remain to be queued */
+		return TOOK_BLOCK;
 	}
-	pthread_barrier_wait(down->shared_buffer.consumers_ready);
-	struct timeval t0;
-	gettimeofday(&t0, NULL);
-	const size_t need = ok ? (size_t)fb->geo.input_size : 1;
-	/* spectrum monitor: one CSV line per interval of SIGNAL (blocks pushed x block length / sample rate): a row of the device's history */
-	FILE *spec_file = NULL;
-	float *spec_mean = NULL;
-	char *spec_line = NULL;
-	int32_t spec_bins = 0;
-	uint64_t spec_closed = 0, spec_next = 0;     /* intervals closed so far; the first row not written yet */
-	if (ok && fb->spec_path != NULL) {
-		spec_bins = fb->spec_bins;
-		while (spec_bins > fb->geo.fft_size / 16) spec_bins /= 2;
-		spec_file = fopen(fb->spec_path, "w");       /* a run writes its own file: nothing of an earlier run stays in front of it */
-		/* the ring holds what can be pushed before a closed row's launch has run and this thread has looked again: the blocks of two
-		 * halves and the uploads ahead of them, were every one of them a row of its own, and as many again */
-		if (spec_file == NULL || hfdl_gpu_frontend_spectrum_enable(fe, spec_bins, fb->spec_hann ? HFDL_GPU_SPECTRUM_HANN : 0u) != 0
-				|| hfdl_gpu_frontend_spectrum_history(fe, SPEC_ROWS, 0) != 0) {
-			fprintf(stderr, "spectrum monitor: %s\n", spec_file ? hfdl_gpu_last_error() : "cannot open the spectrum file");
-			if (spec_file) fclose(spec_file);
-			spec_file = NULL;
-			do_exit = 1;
-			ok = 0;
+	bool waited_grace = false;
+	pthread_mutex_lock(ring->mutex);
+	/* shutdown is honoured only when there is not a whole block left, so buffered samples are flushed (src/fft.c:39-48) */
+	while (!next_block_is_there(t)) {
+		if (block_connection_is_shutdown_signaled(t->block->consumer.in)) {
+			pthread_mutex_unlock(ring->mutex);
+			return TOOK_SHUTDOWN;
+		}
+		if (t->ok && t->up.leased > 0) {
+			/* the producer may be out of room: slots whose upload is done go back before this thread sleeps */
+			pthread_mutex_unlock(ring->mutex);
+			const double tr = now_s();
+			release_copied(t, true);
+			t->rs.release_s += now_s() - tr;
+			pthread_mutex_lock(ring->mutex);
+		} else if (t->ok && t->undelivered > 0 && !waited_grace) {
+			grace_then_drain(t);
+			waited_grace = true;
 		} else {
-			spec_mean = hfdl_xcalloc((size_t)spec_bins, sizeof(float));
-			spec_line = hfdl_xcalloc(64 + 12 * (size_t)spec_bins, 1);
+			pthread_cond_wait(ring->cond, ring->mutex);
 		}
 	}
-	struct iq_export iqx;
-	memset(&iqx, 0, sizeof(iqx));
-	if (ok && fb->iqx_dir != NULL && iq_export_open(fe, fb, slots, nch, &iqx) != 0) {
-		iq_export_close(&iqx);
-		do_exit = 1;
-		ok = 0;
+	*blk = t->ok ? hfdl_ring_peek(ring->buf, uploads_next_offset(&t->up, t->need), t->need) : NULL;
+	if (t->ok && *blk == NULL) {
+		*blk = bounce_block(t);
+		*from_bounce = true;
 	}
-	const size_t elem = hfdl_ring_elem_size(ring->buf);
-	const int gfmt = gpu_format_of(hfdl_ring_format(ring->buf));
-	/* uploads ahead of the pushes: what the library allows, and what the ring can hold beside the block being pushed and room for
-	 * the producer to write into */
-	size_t depth = 0;
-	if (ok) {
-		const size_t ring_blocks = hfdl_ring_capacity(ring->buf) / need;
-		depth = (size_t)fb->geo.prefetch_depth;
+	if (!t->ok) hfdl_ring_drop(ring->buf, hfdl_ring_size(ring->buf));
+	pthread_mutex_unlock(ring->mutex);
+	if (!t->ok) {
+		pthread_cond_signal(ring->cond);
+		return TOOK_NOTHING;
+	}
+	return TOOK_BLOCK;
+}
+
+/* Push the block take_block() gave.  On failure nothing of ours may stay with the DMA engine: the queued copies are let finish, then
+ * every slot is given up (the ring is emptied by the next take_block()).
+ * Ring mutex: not held. */
+static bool push_block(struct fe_thread *t, const void *blk, bool from_bounce)
+{
+	if (hfdl_gpu_frontend_push_block_raw(t->fe, blk, t->need, from_bounce ? HFDL_GPU_SFMT_CF32 : t->gfmt, 0) != 0) {
+		fail(t, hfdl_gpu_last_error());
+		(void)hfdl_gpu_frontend_prefetch_cancel(t->fe);
+		(void)hfdl_gpu_frontend_input_done(t->fe);
+		uploads_forget(&t->up);
+		return false;
+	}
+	t->rs.blocks++;
+	t->undelivered++;
+	if (t->up.q_len > 0) uploads_pushed_queued(&t->up);
+	else uploads_pushed_direct(&t->up, !from_bounce);
+	return true;
+}
+
+/* queue the uploads of every further whole block the ring holds already: they run beside the blocks still computing.
+ * Ring mutex: not held; taken only to look at the ring. */
+static void upload_ahead(struct fe_thread *t)
+{
+	while (t->up.q_len < t->up.depth) {
+		pthread_mutex_lock(t->ring->mutex);
+		const void *next = next_block_is_there(t) ? hfdl_ring_peek(t->ring->buf, uploads_next_offset(&t->up, t->need), t->need) : NULL;
+		pthread_mutex_unlock(t->ring->mutex);
+		if (next == NULL || hfdl_gpu_frontend_prefetch_block_raw(t->fe, next, t->need, t->gfmt) != 0) break;
+		uploads_queued_ahead(&t->up, next);
+	}
+}
+
+/* creates the front end for the channels registered on the connection, meets the channels at the start barrier (whether or not the
+ * create worked) and opens the optional outputs; on any failure t->ok is false and do_exit is set */
+static void frontend_setup(struct fe_thread *t, struct block *block)
+{
+	memset(t, 0, sizeof(*t));
+	t->block = block;
+	t->fb = container_of(block, struct gpu_fft_block, block);
+	t->ring = &block->consumer.in->circ_buffer;
+	struct gpu_fft_block *fb = t->fb;
+	struct block_connection *down = block->producer.out;
+	struct hfdl_channel_slot *slots[MAX_SLOTS];
+	t->nch = hfdl_channels_on_connection(down, slots, MAX_SLOTS);
+	t->freqs = hfdl_xcalloc(t->nch ? t->nch : 1, sizeof(int32_t));
+	for (size_t i = 0; i < t->nch; i++) t->freqs[i] = slots[i]->frequency;
+	t->ok = true;
+	if (t->nch == 0) {
+		fail(t, "no channels connected");
+	} else if (hfdl_gpu_frontend_create(&t->fe, fb->device, slots[0]->sample_rate, slots[0]->centerfreq, t->freqs, (int32_t)t->nch) != 0) {
+		fail(t, hfdl_gpu_last_error());
+	} else {
+		hfdl_gpu_frontend_geometry(t->fe, &fb->geo);
+		hfdl_gpu_frontend_enable_taps(t->fe, 0);
+		t->pdus = hfdl_xcalloc(PDU_BATCH, sizeof(*t->pdus));
+		t->stats = hfdl_xcalloc(t->nch, sizeof(*t->stats));
+		t->fs = (double)slots[0]->sample_rate;
+		t->centerfreq = (double)slots[0]->centerfreq;
+	}
+	pthread_barrier_wait(down->shared_buffer.consumers_ready);
+	gettimeofday(&t->t0, NULL);
+	t->need = t->ok ? (size_t)fb->geo.input_size : 1;
+	t->gfmt = gpu_format_of(hfdl_ring_format(t->ring->buf));
+	if (t->ok && ((fb->spectrum.path != NULL && spectrum_csv_open(t) != 0)
+			|| (fb->iqx.dir != NULL && iq_export_open(t->fe, fb, slots, t->nch, &t->iqx) != 0))) {
+		do_exit = 1;
+		t->ok = false;
+	}
+	if (t->ok) {
+		/* uploads ahead of the pushes: what the library allows, and what the ring can hold beside the block being pushed and room
+		 * for the producer to write into */
+		const size_t ring_blocks = hfdl_ring_capacity(t->ring->buf) / t->need;
+		size_t depth = (size_t)fb->geo.prefetch_depth;
 		if (depth > HFDL_GPU_PREFETCH_MAX) depth = HFDL_GPU_PREFETCH_MAX;
 		if (ring_blocks < 4) depth = 0; else if (depth > ring_blocks - 3) depth = ring_blocks - 3;
+		t->up.depth = depth;
+		t->grace = 0.25 * (double)t->need / t->fs;
 	}
-	double grace = ok ? 0.25 * (double)need / (double)slots[0]->sample_rate : 0.0;
-	if (grace > 0.020) grace = 0.020;
-	if (grace < 0.0005) grace = 0.0005;
-	uint64_t k = 0, npdus = 0;
-	double t_first = 0, t_last = 0, t_published = 0;
-	double s_wait = 0, s_push = 0, s_poll = 0, s_release = 0, s_grace = 0;      /* where this thread's time went (seconds) */
-	uint64_t drains = 0;
-	size_t leased = 0;                       /* ring slots the DMA engine may still read: the newest `leased` uploads, oldest at the ring's head */
-	uint64_t uploads = 0;                    /* host blocks whose copy has been queued, as the GPU library numbers them */
-	const void *queued[HFDL_GPU_PREFETCH_MAX + 1];      /* uploads not pushed yet, oldest at q_head */
-	size_t q_head = 0, q_len = 0;
-	uint64_t undelivered = 0;                /* blocks pushed since the pipeline was last drained */
-	struct timespec last_push;               /* when the newest block was taken from the ring and pushed (CLOCK_REALTIME: pthread_cond_timedwait's clock) */
-	clock_gettime(CLOCK_REALTIME, &last_push);
+	if (t->grace > 0.020) t->grace = 0.020;
+	if (t->grace < 0.0005) t->grace = 0.0005;
+	clock_gettime(CLOCK_REALTIME, &t->last_push);
+}
+
+/* delivers what is still in the pipeline, finishes the optional outputs, publishes the run statistics (only a run that had a front
+ * end has any), passes the shutdown on to the channels and frees everything */
+static void frontend_teardown(struct fe_thread *t)
+{
+	if (t->fe) {
+		deliver_pdus(t, true);                   /* what the lagging collection left behind */
+		const double t_last = now_s();
+		spectrum_csv_close(t);
+		if (t->iqx.files != NULL) write_iq_export(t->fe, &t->iqx, 1);
+		publish_counters(t->fe, t->stats, (int32_t)t->nch);
+		t->rs.samples = t->rs.blocks * (uint64_t)t->need;
+		t->rs.seconds = t->rs.blocks ? t_last - t->t_first : 0.0;
+		t->rs.bytes_per_sample = (int32_t)hfdl_ring_elem_size(t->ring->buf);
+		t->rs.channels = (int32_t)t->nch;
+		t->rs.block_samples = (int32_t)t->need;
+		t->rs.zero_copy = hfdl_ring_is_pinned(t->ring->buf);
+		pthread_mutex_lock(&g_run_lock);
+		g_run = t->rs;
+		pthread_mutex_unlock(&g_run_lock);
+	}
+	block_connection_one2many_shutdown(t->block->producer.out);
+	if (t->fe) hfdl_gpu_frontend_destroy(t->fe);
+	iq_export_close(&t->iqx);
+	free(t->bounce);
+	free(t->pdus);
+	free(t->stats);
+	free(t->freqs);
+	t->block->running = false;
+}
+
+/* The front-end thread.  A block never gets copied on the host: the ring in front of this block is page-locked and a whole
+ * number of blocks long (block_connect_one2one), so each block is handed to the GPU where it lies -- raw cs16 / cu8 samples
+ * included, which the device converts -- and its slot goes back to the producer once the DMA has read it.
+ *
+ * Uploads run AHEAD of the blocks that compute: whatever whole blocks the ring holds beyond the one being pushed are queued for
+ * upload at once (hfdl_gpu_frontend_prefetch_block_raw, up to geometry.prefetch_depth of them), so the copy engine keeps working
+ * while this thread waits for the GPU in the collection call -- the fold of a 40 Msps x 256-channel half takes 3 ms, five blocks
+ * of PCIe time.
+ *
+ * Live source or replay?  The pipeline is drained (everything pushed so far folded, demodulated and delivered at once) only when
+ * the ring has run EMPTY and the source has stayed silent for a grace period of a quarter of a block's own duration (at most
+ * 20 ms), counted from the arrival of the newest block: a live radio delivers a block every block duration and gets its PDUs
+ * within that grace; a file reader that hiccups for a millisecond beside a GPU about as fast as itself never drains a filled
+ * pipeline (round 4's fixed 0.5 ms grace did, five times in a run, for 19 % of the rate).
+ *
+ * The ring's mutex is never held across a call into the device library or a PDU delivery; every helper below says how it expects
+ * and leaves the mutex. */
+static void *frontend_thread(void *ctx)
+{
+	struct fe_thread t;
+	frontend_setup(&t, ctx);
+	double t_published = 0;
 	for (;;) {
 		const double tw0 = now_s();
 		const void *blk = NULL;
 		bool from_bounce = false;
-		if (q_len > 0) {
-			blk = queued[q_head];            /* uploaded ahead: only its kernels remain to be queued */
-		} else {
-			bool waited_grace = false;
-			pthread_mutex_lock(ring->mutex);
-			/* shutdown is honoured only when there is not a whole block left, so buffered samples are flushed (src/fft.c:39-48) */
-			while (hfdl_ring_size(ring->buf) < (leased + 1) * need) {
-				if (block_connection_is_shutdown_signaled(block->consumer.in)) { pthread_mutex_unlock(ring->mutex); goto shutdown; }
-				if (ok && leased > 0) {
-					/* the producer may be out of room: slots whose upload is done go back before this thread sleeps */
-					pthread_mutex_unlock(ring->mutex);
-					const double tr = now_s();
-					if (release_copied(fe, ring, need, uploads, &leased, true) != 0) {
-						fprintf(stderr, "GPU front end: %s\n", hfdl_gpu_last_error());
-						do_exit = 1;
-						ok = 0;
-					}
-					s_release += now_s() - tr;
-					pthread_mutex_lock(ring->mutex);
-					continue;
-				}
-				if (ok && undelivered > 0 && !waited_grace) {
-					/* the ring is empty: a live source, or a reader catching its breath?  Wait the grace period, then deliver */
-					/* the grace period counts from the moment the newest block was PUSHED, not from here (the wait for its upload
-					 * lies in between): a live block's PDUs leave grace after its arrival, whatever the copy took */
-					struct timespec until = last_push;
-					until.tv_nsec += (long)(grace * 1e9);
-					while (until.tv_nsec >= 1000000000) { until.tv_sec++; until.tv_nsec -= 1000000000; }
-					const double tg = now_s();
-					int rc = 0;
-					while (rc == 0 && hfdl_ring_size(ring->buf) < (leased + 1) * need && !block_connection_is_shutdown_signaled(block->consumer.in))
-						rc = pthread_cond_timedwait(ring->cond, ring->mutex, &until);
-					s_grace += now_s() - tg;
-					waited_grace = true;
-					if (hfdl_ring_size(ring->buf) >= (leased + 1) * need || block_connection_is_shutdown_signaled(block->consumer.in)) continue;
-					pthread_mutex_unlock(ring->mutex);
-					int32_t n = 0;
-					do {                     /* draining collection: the half being filled is closed as it is */
-						if (hfdl_gpu_frontend_poll_pdus(fe, pdus, max_pdus, &n) != 0) break;
-						for (int32_t i = 0; i < n; i++) push_pdu(&pdus[i], &t0);
-						npdus += (uint64_t)n;
-					} while (n == max_pdus);
-					drains++;
-					undelivered = 0;
-					pthread_mutex_lock(ring->mutex);
-					continue;
-				}
-				pthread_cond_wait(ring->cond, ring->mutex);
-			}
-			blk = ok ? hfdl_ring_peek(ring->buf, leased * need, need) : NULL;
-			if (ok && blk == NULL) {
-				/* a block that wraps around the end of a ring this library did not size: one copy.  The blocks still leased
-				 * to the DMA engine sit in front of it; they go back to the producer first. */
-				pthread_mutex_unlock(ring->mutex);
-				while (ok && leased > 0)
-					if (release_copied(fe, ring, need, uploads, &leased, true) != 0) {
-						fprintf(stderr, "GPU front end: %s\n", hfdl_gpu_last_error());
-						do_exit = 1;
-						ok = 0;
-					}
-				pthread_mutex_lock(ring->mutex);
-				if (ok && bounce == NULL) bounce = hfdl_xcalloc(need, sizeof(float complex));
-				if (ok && hfdl_ring_read(ring->buf, bounce, need) != need) {      /* only a cf32 ring can be copied out of */
-					fprintf(stderr, "GPU front end: input ring holds raw samples in blocks that are not contiguous\n");
-					do_exit = 1;
-					ok = 0;
-				}
-				blk = bounce;
-				from_bounce = true;
-			}
-			if (!ok) hfdl_ring_drop(ring->buf, hfdl_ring_size(ring->buf));
-			pthread_mutex_unlock(ring->mutex);
-			if (!ok) { pthread_cond_signal(ring->cond); continue; }
-		}
+		const enum took took = take_block(&t, &blk, &from_bounce);
+		if (took == TOOK_SHUTDOWN) break;
+		if (took == TOOK_NOTHING) continue;
 		const double tw1 = now_s();
-		clock_gettime(CLOCK_REALTIME, &last_push);
-		if (k == 0) t_first = tw1; else s_wait += tw1 - tw0;
-		if (hfdl_gpu_frontend_push_block_raw(fe, blk, need, from_bounce ? HFDL_GPU_SFMT_CF32 : gfmt, 0) != 0) {
-			fprintf(stderr, "GPU front end: %s\n", hfdl_gpu_last_error());
-			do_exit = 1;
-			ok = 0;
-			/* nothing of ours may stay with the DMA engine: let the queued copies finish, then give every slot back */
-			(void)hfdl_gpu_frontend_prefetch_cancel(fe);
-			(void)hfdl_gpu_frontend_input_done(fe);
-			leased = 0;
-			q_len = 0;
-			continue;
-		}
-		k++;
-		undelivered++;
-		if (q_len > 0) { q_head = (q_head + 1) % (HFDL_GPU_PREFETCH_MAX + 1); q_len--; }       /* its slot was leased when the copy was queued */
-		else { uploads++; if (!from_bounce) leased++; }
-		/* queue the uploads of every further whole block the ring holds already: they run beside the blocks still computing */
-		while (!from_bounce && q_len < depth) {
-			pthread_mutex_lock(ring->mutex);
-			const void *next = hfdl_ring_size(ring->buf) >= (leased + 1) * need ? hfdl_ring_peek(ring->buf, leased * need, need) : NULL;
-			pthread_mutex_unlock(ring->mutex);
-			if (next == NULL || hfdl_gpu_frontend_prefetch_block_raw(fe, next, need, gfmt) != 0) break;
-			queued[(q_head + q_len) % (HFDL_GPU_PREFETCH_MAX + 1)] = next;
-			q_len++;
-			uploads++;
-			leased++;
-		}
-		if (spec_file != NULL) {
-			/* an interval boundary closes the open row (no device call); finished rows are written as they are found, without waiting */
-			if ((double)k * (double)need / (double)slots[0]->sample_rate >= (double)(spec_closed + 1) * (double)fb->spec_interval_s) {
-				uint64_t row = 0;
-				if (hfdl_gpu_frontend_spectrum_row_close(fe, &row) != 0)
-					fprintf(stderr, "spectrum monitor: interval %llu has no line: %s\n", (unsigned long long)spec_closed, hfdl_gpu_last_error());
-				spec_closed++;
-			}
-			spec_next = write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 0);
-		}
-		if (iqx.files != NULL) write_iq_export(fe, &iqx, 0);
+		clock_gettime(CLOCK_REALTIME, &t.last_push);
+		if (t.rs.blocks == 0) t.t_first = tw1; else t.rs.wait_input_s += tw1 - tw0;
+		if (!push_block(&t, blk, from_bounce)) continue;
+		if (!from_bounce) upload_ahead(&t);
+		if (t.csv.file != NULL) spectrum_csv_step(&t);
+		if (t.iqx.files != NULL) write_iq_export(t.fe, &t.iqx, 0);
 		const double tw2 = now_s();
-		s_push += tw2 - tw1;
-		/* collect what is known to be complete without draining anything and WITHOUT waiting: what this thread may queue ahead is
-		 * bounded by the ring slots it leases to the uploads (it sleeps in release_copied() when the ring has nothing new and the
-		 * oldest upload is still running), and slots can only go back to the producer while this thread is not blocked elsewhere */
-		int32_t n = 0;
-		do {
-			if (hfdl_gpu_frontend_poll_pdus_ready(fe, pdus, max_pdus, &n, 2) != 0) break;
-			for (int32_t i = 0; i < n; i++) push_pdu(&pdus[i], &t0);
-			npdus += (uint64_t)n;
-		} while (n == max_pdus);
+		t.rs.push_s += tw2 - tw1;
+		deliver_pdus(&t, false);
 		const double tw3 = now_s();
-		s_poll += tw3 - tw2;
-		/* ring slots whose upload has finished go back to the producer; nothing is waited for here */
-		if (release_copied(fe, ring, need, uploads, &leased, false) != 0) {
-			fprintf(stderr, "GPU front end: %s\n", hfdl_gpu_last_error());
-			do_exit = 1;
-			ok = 0;
-		}
-		s_release += now_s() - tw3;
+		t.rs.collect_s += tw3 - tw2;
+		release_copied(&t, false);               /* nothing is waited for here */
+		t.rs.release_s += now_s() - tw3;
 		/* the StatsD counters / gauges are read from the device every 50 ms of wall time at most: one strided device read per
 		 * block would cost more than a block of a small geometry takes (a block is decoded in ~0.3 ms) */
 		const double now = now_s();
-		if (now - t_published >= 0.05) { publish_counters(fe, stats, (int32_t)nch); t_published = now; }
+		if (now - t_published >= 0.05) { publish_counters(t.fe, t.stats, (int32_t)t.nch); t_published = now; }
 	}
-shutdown:
-	if (fe) {
-		int32_t n = 0;
-		do {                                                             /* drain what the lagging collection left behind */
-			if (hfdl_gpu_frontend_poll_pdus(fe, pdus, max_pdus, &n) != 0) break;
-			for (int32_t i = 0; i < n; i++) push_pdu(&pdus[i], &t0);
-			npdus += (uint64_t)n;
-		} while (n == max_pdus);
-		t_last = now_s();
-		if (spec_file != NULL) (void)write_spectrum_rows(fe, &fb->geo, (double)slots[0]->sample_rate, (double)slots[0]->centerfreq, &t0, spec_file, spec_mean, spec_line, spec_bins, spec_next, 1);
-		if (iqx.files != NULL) write_iq_export(fe, &iqx, 1);
-		publish_counters(fe, stats, (int32_t)nch);
-		pthread_mutex_lock(&g_run_lock);
-		g_run.blocks = k; g_run.samples = k * (uint64_t)need; g_run.pdus = npdus;
-		g_run.seconds = k ? t_last - t_first : 0.0;
-		g_run.bytes_per_sample = (int32_t)elem; g_run.channels = (int32_t)nch; g_run.block_samples = (int32_t)need;
-		g_run.zero_copy = hfdl_ring_is_pinned(ring->buf);
-		g_run.wait_input_s = s_wait; g_run.push_s = s_push; g_run.collect_s = s_poll; g_run.release_s = s_release;
-		g_run.drains = drains; g_run.grace_s = s_grace;
-		g_run.mpdus_walked = g_lpdu_tally[0]; g_run.lpdus_processed = g_lpdu_tally[1]; g_run.lpdus_good = g_lpdu_tally[2]; g_run.lpdus_bad_fcs = g_lpdu_tally[3];
-		pthread_mutex_unlock(&g_run_lock);
-	}
-	block_connection_one2many_shutdown(down);
-	if (fe) hfdl_gpu_frontend_destroy(fe);
-	iq_export_close(&iqx);
-	if (spec_file) fclose(spec_file);
-	free(spec_mean);
-	free(spec_line);
-	free(bounce);
-	free(pdus);
-	free(stats);
-	free(freqs);
-	block->running = false;
+	frontend_teardown(&t);
 	return NULL;
 }
 
@@ -746,11 +888,8 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 	fb->decimation = decimation;
 	fb->transition_bw = transition_bw;
 	fb->device = g_device;
-	fb->spec_path = g_spectrum.path ? strdup(g_spectrum.path) : NULL;
-	fb->spec_bins = g_spectrum.bins; fb->spec_interval_s = g_spectrum.interval_s; fb->spec_hann = g_spectrum.hann;
-	fb->iqx_dir = g_iqx.dir ? strdup(g_iqx.dir) : NULL;
-	fb->iqx_freqs = g_iqx.dir ? copy_freqs(g_iqx.freqs, g_iqx.nfreqs) : NULL;
-	fb->iqx_nfreqs = g_iqx.nfreqs; fb->iqx_format = g_iqx.format; fb->iqx_scale = g_iqx.scale;
+	fb->spectrum = spectrum_settings_copy(&g_spectrum);
+	fb->iqx = iq_export_settings_copy(&g_iqx);
 	fb->block.producer.type = PRODUCER_MULTI;
 	fb->block.producer.max_tu = (size_t)fb->geo.fft_size;
 	fb->block.consumer.type = CONSUMER_SINGLE;
@@ -763,8 +902,7 @@ void fft_destroy(struct block *fft_block)
 {
 	if (fft_block == NULL) return;
 	struct gpu_fft_block *fb = container_of(fft_block, struct gpu_fft_block, block);
-	free(fb->spec_path);
-	free(fb->iqx_dir);
-	free(fb->iqx_freqs);
+	spectrum_settings_free(&fb->spectrum);
+	iq_export_settings_free(&fb->iqx);
 	free(fb);
 }

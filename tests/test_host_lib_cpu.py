@@ -1,5 +1,6 @@
 """CPU tests of libhfdl_host.so (plain-C block runtime / inputs keeping the reference's interface), driven from a small C
-program the way dumphfdl's main() drives the reference.  No GPU work: the front-end thread is never started here."""
+program the way dumphfdl's main() drives the reference.  No GPU work: ring, block graph and inputs only.  The front-end thread
+itself runs on the CPU in tests/test_host_frontend_cpu.py, against a host-memory stand-in for libhfdl_gpu.so."""
 import os
 import subprocess
 import numpy as np
