@@ -3,8 +3,8 @@
 # tests/hostsim/serial_demod.h on the fixed-sequence elementary functions of tests/hostsim/shared_math.h (-DHFDL_DM_STRICT), with the
 # shipped pipeline's fast forms switched back on per HFDL_DM_STRICT_FAST (1 sums, 2 AGC, 4 trig, 8 slicer).  Loaded through
 # HFDL_GPU_LIB by profiles/strict_study.py and tests/test_gpu_strict.py (which builds the two it needs when they are missing).
-# Output: build/strict/libhfdl_gpu_strict_<F>.so at the repository root -- outside the package.  Only the demodulator kernels are
-# compiled again (tests/hostsim/strict_demod_kernels.hip wraps demod_kernels.hip); the other objects are the product build's
+# Output: build/strict/libhfdl_gpu_strict_<F>.so at the repository root -- outside the package.  Only the demodulator kernels and
+# their launchers are compiled again (tests/hostsim/strict_demod_kernels.hip wraps demod_kernels.hip); the other objects are the product build's
 # (dumphfdl_amd/build, made by build.sh), the list of them is objects.sh's: a strict build links whatever the product links.
 set -e
 cd "$(dirname "$0")"

@@ -69,17 +69,4 @@ struct Demod {
 	int read_constants(void *tables, size_t tables_bytes, void *constants, size_t constants_bytes);   // laboratory read-back: sizeof(DemodTables), sizeof(HfdlConstants)
 };
 
-#ifdef HFDL_LAB
-int demod_clock_probe_read(unsigned long long *out, int max, int *n);      // laboratory: {tag, shader cycles, 100 MHz ticks, start tick} per probed launch
-int demod_burst_soft_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes, uint8_t *vin, int32_t *vin_lens);   // laboratory: the Viterbi input of every frame, [nframes][HFDL_GPU_LAB_VIN_MAX]
-#endif
-// kernel_ms: time of the kernel launch alone (StageTimer)
-int demod_viterbi_batch(const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out, double *kernel_ms);
-int demod_crc16(const uint8_t *data, uint32_t len, uint16_t crc_init, uint16_t *crc);
-int demod_pdu_triage_batch(const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *fcs_status, uint8_t *kind, uint16_t *hdr_len);
-int demod_psk_slice_batch(int arity, const float *xy, int32_t n, uint32_t *sym, float *phase_error);
-int demod_lpdu_walk_batch(const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *counts);
-int demod_burst_decode_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes,
-		uint8_t *octets, int32_t *lens, double *kernel_ms);
-
 }  // namespace hfdl

@@ -9,12 +9,11 @@
 //     Viterbi mapping: lane = trellis state (64 = one wavefront); the two predecessor metrics arrive by
 //     cross-lane shuffle, the 64 decisions of a trellis step are one __ballot word kept in LDS.
 //
-// Below the kernels: their launchers (demod_launch.h; the owner of a front end's demodulator state is demod_host.cpp), the one-shot stage
-// entry points and the laboratory clock-probe read.
+// Below the kernels: their launchers (demod_launch.h) and nothing else of the host's -- no allocation, no copy, no wait except the
+// constants read-back.  The owner of a front end's demodulator state is demod_host.cpp, the one-shot stage entry points are stages.cpp's,
+// the laboratory's clock-probe reader is lab.cpp's.
 #include <hip/hip_ext.h>
 #include <utility>
-#include <vector>
-#include <cstring>
 #include "demod_core.h"
 #ifdef HFDL_DM_STRICT
 // Hook of the TEST-ONLY strict builds (tests/hostsim/strict_demod_kernels.hip includes this file after defining HFDL_DM_STRICT, the
@@ -23,7 +22,7 @@
 #include HFDL_DM_SERIAL_LOOP
 #endif
 #include "demod_tables.h"
-#include "demod.h"
+#include "hip_handles.h"
 #include "demod_launch.h"
 #ifdef HFDL_LAB
 #include "../../include/hfdl_gpu_lab.h"
@@ -589,12 +588,14 @@ static int set_big_lds(const void *fn, size_t bytes)
 	return 0;
 }
 
+int prepare_burst_decode() { return set_big_lds((const void *)burst_decode_kernel, burst_decode_lds()); }
+
 int prepare_demod_kernels(size_t demod_lds)
 {
 	int rc;
 	if ((rc = set_big_lds((const void *)demod_kernel<true>, demod_lds))) return rc;
 	if ((rc = set_big_lds((const void *)demod_kernel<false>, demod_lds))) return rc;
-	return set_big_lds((const void *)burst_decode_kernel, burst_decode_lds());
+	return prepare_burst_decode();
 }
 
 void launch_demod(bool taps, const DevTables &T, const DemodBuffers &B, const cf *chan_out, const int *n_in, int outs_stride, int nblk, int nch,
@@ -611,26 +612,52 @@ void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes
 			nframes, stale_count, frame_cap, data, scrambler, freqs, pdus, pdu_cap);
 }
 
-#ifdef HFDL_LAB
-// the clock-probe ring of this translation unit's kernels: records made since the last read, oldest first (at most `max`)
-int demod_clock_probe_read(unsigned long long *out, int max, int *n)
+// ---- the stage kernels
+
+int prepare_viterbi_batch(int nbits)
 {
-	unsigned cnt = 0;
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(hfdl_clk_probe_n), sizeof(cnt)));
-	std::vector<unsigned long long> all(4096 * 4);
-	HIP_TRY(hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(hfdl_clk_probe), sizeof(unsigned long long) * all.size()));
-	const unsigned have = cnt < 4096u ? cnt : 4096u;
-	int k = 0;
-	for (unsigned i = 0; i < have && k < max; i++) {
-		const unsigned slot = (cnt - have + i) & 4095u;
-		for (int j = 0; j < 4; j++) out[4 * k + j] = all[4 * slot + j];
-		k++;
-	}
-	*n = k;
-	cnt = 0;
-	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(hfdl_clk_probe_n), &cnt, sizeof(cnt)));
-	return 0;
+	const size_t lds = viterbi_lds_bytes(nbits);
+	if (lds > 160 * 1024) return fail(HFDL_GPU_ERANGE, "a Viterbi run over %d bits needs %zu bytes of LDS", nbits, lds);
+	return set_big_lds((const void *)viterbi_batch_kernel, lds);
+}
+
+void launch_viterbi_batch(const uint8_t *soft, int nbits, int nframes, uint8_t *out, hipStream_t st)
+{
+	hipLaunchKernelGGL(viterbi_batch_kernel, dim3((unsigned)nframes), dim3(64), viterbi_lds_bytes(nbits), st, soft, nbits, out);
+}
+
+void launch_crc16(const uint8_t *data, uint32_t len, uint16_t crc_init, uint32_t *out, hipStream_t st)
+{
+	hipLaunchKernelGGL(crc16_kernel, dim3(1), dim3(64), 0, st, data, len, (uint32_t)crc_init, out);
+}
+
+void launch_pdu_triage(const uint8_t *octets, const int32_t *lens, int npdus, int stride, uint8_t *fcs_status, uint8_t *kind, uint16_t *hdr_len, hipStream_t st)
+{
+	hipLaunchKernelGGL(pdu_triage_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, st, octets, lens, npdus, stride, fcs_status, kind, hdr_len);
+}
+
+void launch_lpdu_walk(const uint8_t *octets, const int32_t *lens, int npdus, int stride, uint8_t *counts, hipStream_t st)
+{
+	hipLaunchKernelGGL(lpdu_walk_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, st, octets, lens, npdus, stride, counts);
+}
+
+void launch_psk_slice(int arity, const cf *x, int n, const float *pts, uint32_t *sym, float *perr, hipStream_t st)
+{
+	const int waves = n < 64 * 256 ? (n + 63) / 64 : 256;
+	hipLaunchKernelGGL(psk_slice_kernel, dim3((unsigned)waves), dim3(64), 0, st, arity, x, n, pts, sym, perr);
+}
+
+#ifdef HFDL_LAB
+void launch_burst_soft(const FrameRec *frames, int nframes, const cf *data, const uint8_t *scrambler, uint8_t *vin, int32_t *vin_lens, hipStream_t st)
+{
+	hipLaunchKernelGGL(burst_soft_kernel, dim3((unsigned)nframes), dim3(64), 2 * K5_TABLE_BYTES + DEC_CONST_BYTES, st, frames, data, scrambler, vin, vin_lens);
+}
+
+hipError_t demod_clock_probe_ring(ClockProbeRing &r)
+{
+	r.len = 4096;
+	const hipError_t e = hipGetSymbolAddress((void **)&r.records, HIP_SYMBOL(hfdl_clk_probe));
+	return e != hipSuccess ? e : hipGetSymbolAddress((void **)&r.count, HIP_SYMBOL(hfdl_clk_probe_n));
 }
 #endif
 
@@ -645,189 +672,5 @@ int read_device_constants(void *constants)
 	HIP_TRY(hipMemcpy(constants, d_k.p, sizeof(HfdlConstants), hipMemcpyDeviceToHost));
 	return 0;
 }
-
-// ---------------------------------------------------------------- one-shot stage entry points (demod.h; stages.cpp calls them)
-
-int demod_viterbi_batch(const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out, double *kernel_ms)
-{
-	const size_t in_bytes = (size_t)nframes * 2 * nbits, out_bytes = (size_t)nframes * ((nbits + 7) / 8);
-	const size_t lds = viterbi_lds_bytes(nbits);
-	if (lds > 160 * 1024) return fail(HFDL_GPU_ERANGE, "a Viterbi run over %d bits needs %zu bytes of LDS", nbits, lds);
-	DevBuf d_in, d_out;
-	HIP_TRY(d_in.alloc(in_bytes));
-	HIP_TRY(d_out.alloc(out_bytes));
-	HIP_TRY(hipMemcpy(d_in.p, soft, in_bytes, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemset(d_out.p, 0, out_bytes));
-	int rc = set_big_lds((const void *)viterbi_batch_kernel, lds);
-	if (rc) return rc;
-	StageTimer tm;
-	hipLaunchKernelGGL(viterbi_batch_kernel, dim3((unsigned)nframes), dim3(64), lds, nullptr, d_in.as<const uint8_t>(), nbits, d_out.as<uint8_t>());
-	*kernel_ms = tm.stop();
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int demod_crc16(const uint8_t *data, uint32_t len, uint16_t crc_init, uint16_t *crc)
-{
-	DevBuf d_in, d_out;
-	HIP_TRY(d_in.alloc(len));
-	HIP_TRY(d_out.alloc(sizeof(uint32_t)));
-	if (len) HIP_TRY(hipMemcpy(d_in.p, data, len, hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(crc16_kernel, dim3(1), dim3(64), 0, nullptr, d_in.as<const uint8_t>(), len, (uint32_t)crc_init, d_out.as<uint32_t>());
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	uint32_t v = 0;
-	HIP_TRY(hipMemcpy(&v, d_out.p, sizeof(v), hipMemcpyDeviceToHost));
-	*crc = (uint16_t)v;
-	return 0;
-}
-
-int demod_pdu_triage_batch(const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *fcs_status, uint8_t *kind, uint16_t *hdr_len)
-{
-	DevBuf d_oct, d_lens, d_fcs, d_kind, d_hl;
-	const size_t n = (size_t)npdus;
-	HIP_TRY(d_oct.alloc(n * (size_t)stride));
-	HIP_TRY(d_lens.alloc(n * sizeof(int32_t)));
-	HIP_TRY(d_fcs.alloc(n)); HIP_TRY(d_kind.alloc(n)); HIP_TRY(d_hl.alloc(n * sizeof(uint16_t)));
-	HIP_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(pdu_triage_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, nullptr, d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(),
-			npdus, stride, d_fcs.as<uint8_t>(), d_kind.as<uint8_t>(), d_hl.as<uint16_t>());
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(fcs_status, d_fcs.p, n, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(kind, d_kind.p, n, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(hdr_len, d_hl.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int demod_psk_slice_batch(int arity, const float *xy, int32_t n, uint32_t *sym, float *phase_error)
-{
-	DemodTables h;
-	build_demod_tables(h, 0.6912f);
-	DevBuf d_x, d_pts, d_sym, d_err;
-	HIP_TRY(d_x.alloc(sizeof(cf) * (size_t)n));
-	HIP_TRY(d_pts.alloc(sizeof(h.psk_pts)));
-	HIP_TRY(d_sym.alloc(sizeof(uint32_t) * (size_t)n));
-	HIP_TRY(d_err.alloc(sizeof(float) * (size_t)n));
-	HIP_TRY(hipMemcpy(d_x.p, xy, sizeof(cf) * (size_t)n, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_pts.p, h.psk_pts, sizeof(h.psk_pts), hipMemcpyHostToDevice));
-	const int waves = n < 64 * 256 ? (n + 63) / 64 : 256;
-	hipLaunchKernelGGL(psk_slice_kernel, dim3((unsigned)waves), dim3(64), 0, nullptr, arity, d_x.as<const cf>(), n, d_pts.as<const float>(), d_sym.as<uint32_t>(), d_err.as<float>());
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(sym, d_sym.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(phase_error, d_err.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int demod_lpdu_walk_batch(const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *counts)
-{
-	DevBuf d_oct, d_lens, d_cnt;
-	const size_t n = (size_t)npdus;
-	HIP_TRY(d_oct.alloc(n * (size_t)stride));
-	HIP_TRY(d_lens.alloc(n * sizeof(int32_t)));
-	HIP_TRY(d_cnt.alloc(n * 5));
-	HIP_TRY(hipMemcpy(d_oct.p, octets, n * (size_t)stride, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_lens.p, lens, n * sizeof(int32_t), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(lpdu_walk_kernel, dim3((unsigned)((npdus + 63) / 64)), dim3(64), 0, nullptr, d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(), npdus, stride, d_cnt.as<uint8_t>());
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(counts, d_cnt.p, n * 5, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int demod_burst_decode_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes,
-		uint8_t *octets, int32_t *lens, double *kernel_ms)
-{
-	DemodTables h;
-	build_demod_tables(h, 0.6912f);
-	std::vector<FrameRec> fr((size_t)nframes);
-	std::vector<cf> data((size_t)nframes * 2 * MAX_DATA_SYMBOLS);
-	std::vector<int32_t> freqs((size_t)nframes, 0);
-	size_t off = 0;
-	for (int i = 0; i < nframes; i++) {
-		const ModeParams mp = mode_params(modes[i]);
-		const size_t nsym = (size_t)mp.segments * 30;
-		std::memcpy(&data[(size_t)i * 2 * MAX_DATA_SYMBOLS], symbols + 2 * off, sizeof(cf) * nsym);
-		off += nsym;
-		FrameRec &f = fr[(size_t)i];
-		std::memset(&f, 0, sizeof(f));
-		f.channel = i; f.slot = 0; f.mode = modes[i]; f.bitmask_lsb = bitmask_lsb[i] & 1;
-		f.signal_level = 1.0f; f.noise_floor = 1.0f;
-		f.sample_index = (uint64_t)i;
-	}
-	DevBuf d_scr, d_fr, d_data, d_counts, d_freqs, d_pdus;
-	int counts[8] = { 0, 0, 0, 0, nframes, 0, 0, 0 };
-	HIP_TRY(d_scr.alloc(DEC_CONST_BYTES));
-	HIP_TRY(hipMemcpy(d_scr.p, h.scrambler, DEC_CONST_BYTES, hipMemcpyHostToDevice));
-	HIP_TRY(d_fr.alloc(sizeof(FrameRec) * fr.size()));
-	HIP_TRY(hipMemcpy(d_fr.p, fr.data(), sizeof(FrameRec) * fr.size(), hipMemcpyHostToDevice));
-	HIP_TRY(d_data.alloc(sizeof(cf) * data.size()));
-	HIP_TRY(hipMemcpy(d_data.p, data.data(), sizeof(cf) * data.size(), hipMemcpyHostToDevice));
-	HIP_TRY(d_counts.alloc(sizeof(counts)));
-	HIP_TRY(hipMemcpy(d_counts.p, counts, sizeof(counts), hipMemcpyHostToDevice));
-	HIP_TRY(d_freqs.alloc(sizeof(int32_t) * freqs.size()));
-	HIP_TRY(hipMemcpy(d_freqs.p, freqs.data(), sizeof(int32_t) * freqs.size(), hipMemcpyHostToDevice));
-	HIP_TRY(d_pdus.alloc(sizeof(hfdl_gpu_pdu) * (size_t)nframes));
-	int rc = set_big_lds((const void *)burst_decode_kernel, burst_decode_lds());
-	if (rc) return rc;
-	StageTimer tm;
-	hipLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)nframes), dim3(64), burst_decode_lds(), nullptr, d_fr.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, (int *)nullptr,
-			nframes, d_data.as<const cf>(), d_scr.as<const uint8_t>(), d_freqs.as<const int32_t>(), d_pdus.as<hfdl_gpu_pdu>(), nframes);
-	*kernel_ms = tm.stop();
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	std::vector<hfdl_gpu_pdu> out((size_t)nframes);
-	HIP_TRY(hipMemcpy(out.data(), d_pdus.p, sizeof(hfdl_gpu_pdu) * out.size(), hipMemcpyDeviceToHost));
-	for (int i = 0; i < nframes; i++) lens[i] = 0;
-	for (auto &p : out) {       // PDU slots are claimed in completion order: route by channel (= frame index)
-		if (p.channel < 0 || p.channel >= nframes) continue;
-		lens[p.channel] = p.len;
-		std::memcpy(octets + (size_t)p.channel * HFDL_GPU_PDU_MAX_OCTETS, p.octets, (size_t)p.len);
-	}
-	return 0;
-}
-
-#ifdef HFDL_LAB
-// hfdl_gpu_lab_burst_soft: frames laid out as demod_burst_decode_batch lays them out, through burst_soft_kernel
-int demod_burst_soft_batch(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes, uint8_t *vin, int32_t *vin_lens)
-{
-	DemodTables h;
-	build_demod_tables(h, 0.6912f);
-	std::vector<FrameRec> fr((size_t)nframes);
-	std::vector<cf> data((size_t)nframes * 2 * MAX_DATA_SYMBOLS);
-	size_t off = 0;
-	for (int i = 0; i < nframes; i++) {
-		const size_t nsym = (size_t)mode_params(modes[i]).segments * 30;
-		std::memcpy(&data[(size_t)i * 2 * MAX_DATA_SYMBOLS], symbols + 2 * off, sizeof(cf) * nsym);
-		off += nsym;
-		FrameRec &f = fr[(size_t)i];
-		std::memset(&f, 0, sizeof(f));
-		f.channel = i; f.slot = 0; f.mode = modes[i]; f.bitmask_lsb = bitmask_lsb[i] & 1;
-	}
-	const size_t out_bytes = (size_t)nframes * HFDL_GPU_LAB_VIN_MAX;
-	DevBuf d_scr, d_fr, d_data, d_vin, d_lens;
-	HIP_TRY(d_scr.alloc(DEC_CONST_BYTES));
-	HIP_TRY(hipMemcpy(d_scr.p, h.scrambler, DEC_CONST_BYTES, hipMemcpyHostToDevice));
-	HIP_TRY(d_fr.alloc(sizeof(FrameRec) * fr.size()));
-	HIP_TRY(hipMemcpy(d_fr.p, fr.data(), sizeof(FrameRec) * fr.size(), hipMemcpyHostToDevice));
-	HIP_TRY(d_data.alloc(sizeof(cf) * data.size()));
-	HIP_TRY(hipMemcpy(d_data.p, data.data(), sizeof(cf) * data.size(), hipMemcpyHostToDevice));
-	HIP_TRY(d_vin.alloc(out_bytes));
-	HIP_TRY(hipMemset(d_vin.p, 0, out_bytes));
-	HIP_TRY(d_lens.alloc(sizeof(int32_t) * (size_t)nframes));
-	HIP_TRY(hipMemset(d_lens.p, 0, sizeof(int32_t) * (size_t)nframes));
-	hipLaunchKernelGGL(burst_soft_kernel, dim3((unsigned)nframes), dim3(64), 2 * K5_TABLE_BYTES + DEC_CONST_BYTES, nullptr, d_fr.as<const FrameRec>(), d_data.as<const cf>(),
-			d_scr.as<const uint8_t>(), d_vin.as<uint8_t>(), d_lens.as<int32_t>());
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(vin, d_vin.p, out_bytes, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(vin_lens, d_lens.p, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToHost));
-	return 0;
-}
-#endif
 
 }  // namespace hfdl

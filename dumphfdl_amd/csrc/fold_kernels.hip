@@ -420,23 +420,11 @@ __global__ __launch_bounds__(FOLD_THREADS) void stream_read_kernel(const float4 
 	if (acc == 1.2345e33f) *sink = acc;
 }
 
-int fold_clock_probe_read(unsigned long long *out, int max, int *n)
+hipError_t fold_clock_probe_ring(ClockProbeRing &r)
 {
-	unsigned cnt = 0;
-	if (hipDeviceSynchronize() != hipSuccess) return -1;
-	if (hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(hfdl_fold_clk_probe_n), sizeof(cnt)) != hipSuccess) return -1;
-	unsigned long long all[1024 * 4];
-	if (hipMemcpyFromSymbol(all, HIP_SYMBOL(hfdl_fold_clk_probe), sizeof(all)) != hipSuccess) return -1;
-	const unsigned have = cnt < 1024u ? cnt : 1024u;
-	int k = 0;
-	for (unsigned i = 0; i < have && k < max; i++) {
-		const unsigned slot = (cnt - have + i) & 1023u;
-		for (int j = 0; j < 4; j++) out[4 * k + j] = all[4 * slot + j];
-		k++;
-	}
-	*n = k;
-	cnt = 0;
-	return hipMemcpyToSymbol(HIP_SYMBOL(hfdl_fold_clk_probe_n), &cnt, sizeof(cnt)) == hipSuccess ? 0 : -1;
+	r.len = 1024;
+	const hipError_t e = hipGetSymbolAddress((void **)&r.records, HIP_SYMBOL(hfdl_fold_clk_probe));
+	return e != hipSuccess ? e : hipGetSymbolAddress((void **)&r.count, HIP_SYMBOL(hfdl_fold_clk_probe_n));
 }
 
 int stream_read_variants() { return 4; }

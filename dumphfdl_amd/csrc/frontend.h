@@ -1,7 +1,7 @@
 // frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h, its launch ledger, and what the
 // translation units of the shim share (namespace hfdl).  hfdl_gpu.cpp is the pipeline, frontend_create.cpp builds a front end,
-// frontend_query.cpp reads one, demod_host.cpp owns its demodulator state, stages.cpp holds the one-shot stage entry points, lab.cpp the
-// laboratory build's switches and probes.
+// frontend_query.cpp reads one, demod_host.cpp owns its demodulator state, stages.cpp holds the one-shot stage entry points (checks, staging
+// and read-back; the kernels' launchers are beside the kernels), lab.cpp the laboratory build's switches, probes and stage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <deque>
@@ -43,6 +43,15 @@ struct HostFftPlan {
 	int build(int n);
 };
 int upload_twiddles(int r, DevBuf &out);
+
+// One-shot stages (stages.cpp).  finish_stage: the stage's launches are queued on the null stream -- wait for them and report what they
+// left.  StageFrames: K5's inputs for `nframes` frames whose data symbols lie back to back in `symbols` -- frame i is channel i, slot 0
+// of `data` ([nframes][2][MAX_DATA_SYMBOLS]), unit levels, sample index i -- and the decoder's constants (scrambler, constellations).
+int finish_stage();
+struct StageFrames {
+	DevBuf frames, data, scrambler;
+	int upload(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes);
+};
 
 // ---------------------------------------------------------------- launch timing
 

@@ -108,7 +108,8 @@ struct FftInputs {
 	int32_t nrx = 1;
 };
 
-// owning device allocation for the one-shot stage entry points (freed on every exit path)
+// owning device allocation (freed on every exit path).  upload / zeroed / fetch are the synchronous copies of the one-shot stage entry
+// points (stages.cpp): an input allocated and filled in one step, an output allocated and cleared, an output read back.
 struct DevBuf {
 	void *p = nullptr;
 	DevBuf() = default;
@@ -116,6 +117,9 @@ struct DevBuf {
 	DevBuf &operator=(const DevBuf &) = delete;
 	~DevBuf() { if (p) (void)hipFree(p); }
 	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+	hipError_t upload(const void *src, size_t bytes) { const hipError_t e = alloc(bytes); return e != hipSuccess || !bytes ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice); }
+	hipError_t zeroed(size_t bytes) { const hipError_t e = alloc(bytes); return e != hipSuccess || !bytes ? e : hipMemset(p, 0, bytes); }
+	hipError_t fetch(void *dst, size_t bytes) const { return hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost); }
 	template <typename T> T *as() const { return (T *)p; }
 };
 
@@ -166,7 +170,10 @@ void launch_ifft_nco(const Geometry &g, const float2 *partial, size_t partial_st
 void launch_nco_decimate(const float2 *in, int input_size, float cosdelta, float sindelta, float rate, int decimation,
 		NcoState *state, float2 *phasor_scratch, float2 *out, hipStream_t st);
 #ifdef HFDL_LAB
-int fold_clock_probe_read(unsigned long long *out, int max, int *n);      // {columns x 100 + blocks, shader cycles, 100 MHz ticks, start tick} per fold launch
+// Where a kernel file's clock-probe ring lives: `len` (a power of two) records of four words and the count of records ever made, asked for
+// in the translation unit that defines the __device__ symbols; lab.cpp has the one reader (hfdl_gpu_lab_clock_probe_read)
+struct ClockProbeRing { const unsigned long long *records; unsigned *count; unsigned len; };
+hipError_t fold_clock_probe_ring(ClockProbeRing &r);      // {columns x 100 + blocks, shader cycles, 100 MHz ticks, start tick} per fold launch
 int stream_read_variants();
 void launch_stream_read(int variant, const float2 *src, size_t bytes, float *sink, hipStream_t st);
 #endif

@@ -1,5 +1,6 @@
-// lab.cpp -- the laboratory build (libhfdl_gpu_lab.so, -DHFDL_LAB; include/hfdl_gpu_lab.h): the A/B switches of the measurement scripts
-// and the probes.  The product build keeps one function of this file: read_lab_config() returning the defaults.
+// lab.cpp -- the laboratory build (libhfdl_gpu_lab.so, -DHFDL_LAB; include/hfdl_gpu_lab.h): the A/B switches of the measurement scripts,
+// the probes (the one reader of the kernels' clock-probe rings among them) and the laboratory's one-shot stage, the burst decoder's
+// Viterbi input.  The product build keeps one function of this file: read_lab_config() returning the defaults.
 #include "frontend.h"
 
 using namespace hfdl;
@@ -10,6 +11,7 @@ LabConfig hfdl::read_lab_config() { return LabConfig(); }
 #include <algorithm>
 #include <cstdio>
 #include "../../include/hfdl_gpu_lab.h"
+#include "demod_launch.h"
 
 LabConfig hfdl::read_lab_config()
 {
@@ -66,13 +68,27 @@ extern "C" int hfdl_gpu_lab_read_constants(hfdl_gpu_frontend *fe, void *tables, 
 	return fe->demod.read_constants(tables, tables_bytes, constants, constants_bytes);
 }
 
+// records made since the last read, oldest first, at most `max`; then the ring's counter starts over.  which = 0: the fold's ring, else
+// the demodulator's
 extern "C" int hfdl_gpu_lab_clock_probe_read(int which, uint64_t *records, int32_t max, int32_t *n)
 {
 	if (!records || !n || max < 1) return fail(HFDL_GPU_EINVAL, "bad arguments");
+	ClockProbeRing r;
+	HIP_TRY(which == 0 ? fold_clock_probe_ring(r) : demod_clock_probe_ring(r));
+	unsigned cnt = 0;
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipMemcpy(&cnt, r.count, sizeof(cnt), hipMemcpyDeviceToHost));
+	std::vector<unsigned long long> all(4 * (size_t)r.len);
+	HIP_TRY(hipMemcpy(all.data(), r.records, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
+	const unsigned have = cnt < r.len ? cnt : r.len;
 	int k = 0;
-	const int rc = which == 0 ? fold_clock_probe_read((unsigned long long *)records, max, &k) : demod_clock_probe_read((unsigned long long *)records, max, &k);
-	if (rc) return fail(HFDL_GPU_EHIP, "clock probe read failed: %s", hipGetErrorString(hipGetLastError()));
+	for (unsigned i = 0; i < have && k < max; i++, k++) {
+		const unsigned slot = (cnt - have + i) & (r.len - 1);
+		for (int j = 0; j < 4; j++) records[4 * k + j] = all[4 * slot + j];
+	}
 	*n = k;
+	cnt = 0;
+	HIP_TRY(hipMemcpy(r.count, &cnt, sizeof(cnt), hipMemcpyHostToDevice));
 	return 0;
 }
 
@@ -81,8 +97,19 @@ extern "C" int hfdl_gpu_lab_burst_soft(int device, const float *symbols, const i
 {
 	if (!symbols || !modes || !bitmask_lsb || !vin || !vin_lens || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	for (int i = 0; i < nframes; i++) if (modes[i] < 0 || modes[i] > 7) return fail(HFDL_GPU_EINVAL, "mode out of range");
-	if (int rc = select_device(device)) return rc;
-	return demod_burst_soft_batch(symbols, modes, bitmask_lsb, nframes, vin, vin_lens);
+	int rc = select_device(device);
+	if (rc) return rc;
+	StageFrames in;                 // the frames as hfdl_gpu_burst_decode lays them out
+	if ((rc = in.upload(symbols, modes, bitmask_lsb, nframes))) return rc;
+	const size_t vin_bytes = (size_t)nframes * HFDL_GPU_LAB_VIN_MAX, lens_bytes = sizeof(int32_t) * (size_t)nframes;
+	DevBuf d_vin, d_lens;
+	HIP_TRY(d_vin.zeroed(vin_bytes));
+	HIP_TRY(d_lens.zeroed(lens_bytes));
+	launch_burst_soft(in.frames.as<const FrameRec>(), nframes, in.data.as<const cf>(), in.scrambler.as<const uint8_t>(), d_vin.as<uint8_t>(), d_lens.as<int32_t>(), nullptr);
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_vin.fetch(vin, vin_bytes));
+	HIP_TRY(d_lens.fetch(vin_lens, lens_bytes));
+	return 0;
 }
 
 extern "C" int hfdl_gpu_lab_fold_variant_count(void) { return fold_variant_count(); }

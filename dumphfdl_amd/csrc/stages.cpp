@@ -1,7 +1,13 @@
-// stages.cpp -- the one-shot stage entry points of include/hfdl_gpu.h: one kernel (or one short chain) on caller-supplied data, no
-// front end.  Stage parity tests and the benches of single stages call them.
+// stages.cpp -- the one-shot stage entry points of include/hfdl_gpu.h, whole: one kernel (or one short chain) on caller-supplied data,
+// no front end.  Each checks its arguments, selects the device, uploads its inputs (DevBuf::upload / zeroed, kernels.h), launches through
+// the kernels' own launchers on the null stream (kernels.h, demod_launch.h), waits (finish_stage) and fetches its outputs.  Stage parity
+// tests and the benches of single stages call them.
 #include <cmath>
+#include <cstring>
+#include <vector>
 #include "frontend.h"
+#include "demod_launch.h"
+#include "demod_tables.h"
 
 using namespace hfdl;
 
@@ -9,11 +15,34 @@ using namespace hfdl;
 static thread_local double g_stage_ms = 0.0;
 extern "C" double hfdl_gpu_last_stage_ms(void) { return g_stage_ms; }
 
-// the arguments have been checked: select the device, run the stage (demod_kernels.hip; a failure leaves its own text)
-template <typename Call> static int run_stage(int device, Call call)
+int hfdl::finish_stage()
 {
-	const int rc = select_device(device);
-	return rc ? rc : call();
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int StageFrames::upload(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes)
+{
+	DemodTables h;
+	build_demod_tables(h, 0.6912f);
+	std::vector<FrameRec> fr((size_t)nframes);
+	std::vector<cf> sym((size_t)nframes * 2 * MAX_DATA_SYMBOLS);
+	size_t off = 0;
+	for (int i = 0; i < nframes; i++) {
+		const size_t nsym = (size_t)mode_params(modes[i]).segments * 30;
+		std::memcpy(&sym[(size_t)i * 2 * MAX_DATA_SYMBOLS], symbols + 2 * off, sizeof(cf) * nsym);
+		off += nsym;
+		FrameRec &f = fr[(size_t)i];
+		std::memset(&f, 0, sizeof(f));
+		f.channel = i; f.slot = 0; f.mode = modes[i]; f.bitmask_lsb = bitmask_lsb[i] & 1;
+		f.signal_level = 1.0f; f.noise_floor = 1.0f;
+		f.sample_index = (uint64_t)i;
+	}
+	HIP_TRY(scrambler.upload(h.scrambler, DEC_CONST_BYTES));
+	HIP_TRY(frames.upload(fr.data(), sizeof(FrameRec) * fr.size()));
+	HIP_TRY(data.upload(sym.data(), sizeof(cf) * sym.size()));
+	return 0;
 }
 
 extern "C" int hfdl_gpu_fft_forward(int device, const float *in, float *out, int32_t n, int shifted)
@@ -25,23 +54,34 @@ extern "C" int hfdl_gpu_fft_forward(int device, const float *in, float *out, int
 	if ((rc = plan.build(n))) return rc;
 	DevBuf d_in, d_work, d_out;
 	const size_t bytes = sizeof(float2) * (size_t)n;
-	HIP_TRY(d_in.alloc(bytes));
+	HIP_TRY(d_in.upload(in, bytes));
 	HIP_TRY(d_work.alloc(bytes));
 	HIP_TRY(d_out.alloc(bytes));
-	HIP_TRY(hipMemcpy(d_in.p, in, bytes, hipMemcpyHostToDevice));
 	StageTimer tm;
 	launch_fft_forward(plan.p, nullptr, d_in.p, SFMT_CF32, 0, nullptr, d_work.as<float2>(), d_out.as<float2>(), shifted != 0, nullptr);
 	g_stage_ms = tm.stop();
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost));
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_out.fetch(out, bytes));
 	return 0;
 }
 
 extern "C" int hfdl_gpu_viterbi27(int device, const uint8_t *soft, int32_t nbits, int32_t nframes, uint8_t *out)
 {
 	if (!soft || !out || nbits <= 0 || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	return run_stage(device, [&] { g_stage_ms = 0.0; return demod_viterbi_batch(soft, nbits, nframes, out, &g_stage_ms); });
+	int rc = select_device(device);
+	if (rc) return rc;
+	g_stage_ms = 0.0;
+	if ((rc = prepare_viterbi_batch(nbits))) return rc;
+	const size_t out_bytes = (size_t)nframes * ((nbits + 7) / 8);
+	DevBuf d_in, d_out;
+	HIP_TRY(d_in.upload(soft, (size_t)nframes * 2 * nbits));
+	HIP_TRY(d_out.zeroed(out_bytes));
+	StageTimer tm;
+	launch_viterbi_batch(d_in.as<const uint8_t>(), nbits, nframes, d_out.as<uint8_t>(), nullptr);
+	g_stage_ms = tm.stop();
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_out.fetch(out, out_bytes));
+	return 0;
 }
 
 extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb,
@@ -49,7 +89,32 @@ extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int
 {
 	if (!symbols || !modes || !bitmask_lsb || !octets || !lens || nframes <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	for (int i = 0; i < nframes; i++) if (modes[i] < 0 || modes[i] > 7) return fail(HFDL_GPU_EINVAL, "mode out of range");
-	return run_stage(device, [&] { g_stage_ms = 0.0; return demod_burst_decode_batch(symbols, modes, bitmask_lsb, nframes, octets, lens, &g_stage_ms); });
+	int rc = select_device(device);
+	if (rc) return rc;
+	g_stage_ms = 0.0;
+	StageFrames in;
+	if ((rc = in.upload(symbols, modes, bitmask_lsb, nframes))) return rc;
+	// K5 as the pipeline launches it: a frame queue of `nframes` entries, all of them filled (counts[4]), a PDU ring with a slot for each
+	const int counts[8] = { 0, 0, 0, 0, nframes, 0, 0, 0 };
+	DevBuf d_counts, d_freqs, d_pdus;
+	HIP_TRY(d_counts.upload(counts, sizeof(counts)));
+	HIP_TRY(d_freqs.zeroed(sizeof(int32_t) * (size_t)nframes));
+	HIP_TRY(d_pdus.alloc(sizeof(hfdl_gpu_pdu) * (size_t)nframes));
+	if ((rc = prepare_burst_decode())) return rc;
+	StageTimer tm;
+	launch_burst_decode(in.frames.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, nullptr, nframes, in.data.as<const cf>(),
+			in.scrambler.as<const uint8_t>(), d_freqs.as<const int32_t>(), d_pdus.as<hfdl_gpu_pdu>(), nframes, nullptr, nullptr, nullptr);
+	g_stage_ms = tm.stop();
+	if ((rc = finish_stage())) return rc;
+	std::vector<hfdl_gpu_pdu> pdus((size_t)nframes);
+	HIP_TRY(d_pdus.fetch(pdus.data(), sizeof(hfdl_gpu_pdu) * pdus.size()));
+	for (int i = 0; i < nframes; i++) lens[i] = 0;
+	for (auto &p : pdus) {      // PDU slots are claimed in completion order: route by channel (= frame index)
+		if (p.channel < 0 || p.channel >= nframes) continue;
+		lens[p.channel] = p.len;
+		std::memcpy(octets + (size_t)p.channel * HFDL_GPU_PDU_MAX_OCTETS, p.octets, (size_t)p.len);
+	}
+	return 0;
 }
 
 // decimating_shift_addition_init + decimating_shift_addition_cc (src/libcsdr_gpl.c:26-74) on the device: the NCO / decimator
@@ -68,17 +133,14 @@ extern "C" int hfdl_gpu_nco_decimate(int device, const float *in, int32_t input_
 	st.decimation_remain = *decimation_remain; st.starting_phase = *starting_phase;
 	const size_t max_out = ((size_t)input_size + (size_t)decimation - 1) / (size_t)decimation;
 	DevBuf d_in, d_out, d_ph, d_st;
-	HIP_TRY(d_in.alloc(sizeof(float2) * (size_t)input_size));
+	HIP_TRY(d_in.upload(in, sizeof(float2) * (size_t)input_size));
 	HIP_TRY(d_out.alloc(sizeof(float2) * max_out));
 	HIP_TRY(d_ph.alloc(sizeof(float2) * max_out));
-	HIP_TRY(d_st.alloc(sizeof(NcoState)));
-	HIP_TRY(hipMemcpy(d_in.p, in, sizeof(float2) * (size_t)input_size, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_st.p, &st, sizeof(st), hipMemcpyHostToDevice));
+	HIP_TRY(d_st.upload(&st, sizeof(st)));
 	launch_nco_decimate(d_in.as<const float2>(), input_size, cd, sd, r, decimation, d_st.as<NcoState>(), d_ph.as<float2>(), d_out.as<float2>(), nullptr);
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpy(&st, d_st.p, sizeof(st), hipMemcpyDeviceToHost));
-	if (st.output_size > 0) HIP_TRY(hipMemcpy(out, d_out.p, sizeof(float2) * (size_t)st.output_size, hipMemcpyDeviceToHost));
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_st.fetch(&st, sizeof(st)));
+	if (st.output_size > 0) HIP_TRY(d_out.fetch(out, sizeof(float2) * (size_t)st.output_size));
 	*decimation_remain = st.decimation_remain; *starting_phase = st.starting_phase; *output_size = st.output_size;
 	return 0;
 }
@@ -86,7 +148,17 @@ extern "C" int hfdl_gpu_nco_decimate(int device, const float *in, int32_t input_
 extern "C" int hfdl_gpu_crc16_ccitt(int device, const uint8_t *data, uint32_t len, uint16_t crc_init, uint16_t *crc)
 {
 	if (!crc || (!data && len)) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	return run_stage(device, [&] { return demod_crc16(data, len, crc_init, crc); });
+	int rc = select_device(device);
+	if (rc) return rc;
+	DevBuf d_in, d_out;
+	HIP_TRY(d_in.upload(data, len));         // len = 0: one byte nobody reads (DevBuf::alloc)
+	HIP_TRY(d_out.alloc(sizeof(uint32_t)));
+	launch_crc16(d_in.as<const uint8_t>(), len, crc_init, d_out.as<uint32_t>(), nullptr);
+	if ((rc = finish_stage())) return rc;
+	uint32_t v = 0;
+	HIP_TRY(d_out.fetch(&v, sizeof(v)));
+	*crc = (uint16_t)v;
+	return 0;
 }
 
 // PDUs of a batch: at least one, each 1 .. stride octets long
@@ -100,20 +172,55 @@ extern "C" int hfdl_gpu_pdu_triage(int device, const uint8_t *octets, const int3
 		uint8_t *fcs_status, uint8_t *pdu_kind, uint16_t *hdr_len)
 {
 	if (!octets || !lens || !fcs_status || !pdu_kind || !hdr_len || npdus <= 0 || stride <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	if (int rc = check_pdu_lens(lens, npdus, stride)) return rc;
-	return run_stage(device, [&] { return demod_pdu_triage_batch(octets, lens, npdus, stride, fcs_status, pdu_kind, hdr_len); });
+	int rc = check_pdu_lens(lens, npdus, stride);
+	if (rc || (rc = select_device(device))) return rc;
+	const size_t n = (size_t)npdus;
+	DevBuf d_oct, d_lens, d_fcs, d_kind, d_hl;
+	HIP_TRY(d_oct.upload(octets, n * (size_t)stride));
+	HIP_TRY(d_lens.upload(lens, n * sizeof(int32_t)));
+	HIP_TRY(d_fcs.alloc(n));
+	HIP_TRY(d_kind.alloc(n));
+	HIP_TRY(d_hl.alloc(n * sizeof(uint16_t)));
+	launch_pdu_triage(d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(), npdus, stride, d_fcs.as<uint8_t>(), d_kind.as<uint8_t>(), d_hl.as<uint16_t>(), nullptr);
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_fcs.fetch(fcs_status, n));
+	HIP_TRY(d_kind.fetch(pdu_kind, n));
+	HIP_TRY(d_hl.fetch(hdr_len, n * sizeof(uint16_t)));
+	return 0;
 }
 
 extern "C" int hfdl_gpu_lpdu_walk(int device, const uint8_t *octets, const int32_t *lens, int32_t npdus, int32_t stride, uint8_t *counts)
 {
 	if (!octets || !lens || !counts || npdus <= 0 || stride <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
-	if (int rc = check_pdu_lens(lens, npdus, stride)) return rc;
-	return run_stage(device, [&] { return demod_lpdu_walk_batch(octets, lens, npdus, stride, counts); });
+	int rc = check_pdu_lens(lens, npdus, stride);
+	if (rc || (rc = select_device(device))) return rc;
+	const size_t n = (size_t)npdus;
+	DevBuf d_oct, d_lens, d_cnt;
+	HIP_TRY(d_oct.upload(octets, n * (size_t)stride));
+	HIP_TRY(d_lens.upload(lens, n * sizeof(int32_t)));
+	HIP_TRY(d_cnt.alloc(n * 5));
+	launch_lpdu_walk(d_oct.as<const uint8_t>(), d_lens.as<const int32_t>(), npdus, stride, d_cnt.as<uint8_t>(), nullptr);
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_cnt.fetch(counts, n * 5));
+	return 0;
 }
 
 extern "C" int hfdl_gpu_psk_slice(int device, int32_t arity, const float *xy, int32_t n, uint32_t *sym, float *phase_error)
 {
 	if (!xy || !sym || !phase_error || n <= 0) return fail(HFDL_GPU_EINVAL, "bad arguments");
 	if (arity < 1 || arity > 3) return fail(HFDL_GPU_EINVAL, "arity %d: HFDL uses BPSK, QPSK and 8-PSK (1..3 bits per symbol)", arity);
-	return run_stage(device, [&] { return demod_psk_slice_batch(arity, xy, n, sym, phase_error); });
+	int rc = select_device(device);
+	if (rc) return rc;
+	DemodTables h;
+	build_demod_tables(h, 0.6912f);
+	DevBuf d_x, d_pts, d_sym, d_err;
+	HIP_TRY(d_x.upload(xy, sizeof(cf) * (size_t)n));
+	HIP_TRY(d_pts.upload(h.psk_pts, sizeof(h.psk_pts)));
+	HIP_TRY(d_sym.alloc(sizeof(uint32_t) * (size_t)n));
+	HIP_TRY(d_err.alloc(sizeof(float) * (size_t)n));
+	launch_psk_slice(arity, d_x.as<const cf>(), n, d_pts.as<const float>(), d_sym.as<uint32_t>(), d_err.as<float>(), nullptr);
+	if ((rc = finish_stage())) return rc;
+	HIP_TRY(d_sym.fetch(sym, sizeof(uint32_t) * (size_t)n));
+	HIP_TRY(d_err.fetch(phase_error, sizeof(float) * (size_t)n));
+	return 0;
 }
