@@ -30,7 +30,7 @@ struct LabConfig {
 	int fold_slices = 0;           // HFDL_GPU_FOLD_SLICES (BatchOverrides::fold_slices)
 	int cu_split = 0;              // HFDL_GPU_CU_SPLIT = k (2 .. 8): the demodulator's stream on every k-th CU, the channelizer's on the others
 	bool cu_partition = false;     // HFDL_GPU_CU_PARTITION=1: the planner's CU partition of the fold-bound geometries (planner.h plan_cu_partition)
-	int fft_stream = -1;           // HFDL_GPU_FFT_STREAM 0 / 1: forward FFTs on a stream of their own, instead of "where the CU partition applies"
+	int fft_stream = -1;           // HFDL_GPU_FFT_STREAM 0 / 1: every forward FFT on stream A / on a stream of their own, instead of "by where the block lies" (their own stream where the CU partition applies)
 	bool decode_stream = true;     // HFDL_GPU_DECODE_STREAM: the burst decoders on a stream of their own
 	int fold_bound = -1;           // HFDL_GPU_FOLD_BOUND 0 / 1: instead of "128 channels and more"
 	bool fold_ramp = true;         // HFDL_GPU_FOLD_RAMP=0: every half the full size from the start
@@ -166,14 +166,17 @@ struct ChannelExport {
 // them).  So: streams, then memory, then events.
 struct hfdl_gpu_frontend {
 	int device = 0;
-	hfdl::Stream stream;                // A: forward FFTs of the half being filled, then ONE fold and ONE inverse FFT / NCO launch per half
+	hfdl::Stream stream;                // A: forward FFTs of the uploaded blocks of the half being filled, then ONE fold and ONE inverse FFT / NCO launch per half
 	hfdl::Stream stream_b;              // B: demodulator launches of half k-1, beside the forward FFTs and the fold of half k
 	hfdl::Stream stream_d;              // D: burst decoders + PDU snapshots, off the demodulators' critical path (an alias of B only in a laboratory A/B run)
-	hfdl::Stream stream_c;              // C: host -> device copies into the staging ring, up to n_stage - 1 blocks ahead of the blocks that compute
-	hfdl::Stream stream_f;              // F: forward FFTs of the half being filled, beside the fold of the half before (its own stream under the CU partition or with HFDL_GPU_FFT_STREAM=1, else an alias of A)
+	hfdl::Stream stream_c;              // C, the input stream: whatever brings a block's samples to the transform -- the host -> device copy of a host block into the staging ring (up to n_stage - 1 blocks ahead of the blocks that compute), the forward FFT itself of a device-resident block, beside the fold of the half before
+	hfdl::Stream stream_f;              // F: laboratory only (the CU partition, HFDL_GPU_FFT_STREAM=1): every forward FFT on a stream of its own; not created otherwise
 	bool cu_partitioned = false;        // streams A, F and B are bound to disjoint sets of CUs (planner.h plan_cu_partition)
 	bool own_decode_stream() const { return stream_d.owned; }
-	bool fft_own_stream() const { return stream_f.owned; }
+	hfdl::FftRule fft_rule = hfdl::FFT_RULE_INPUT;      // which side a block's forward FFT runs on (planner.h)
+	hfdl::FftOrder order;               // ... and what orders it against its neighbours
+	int side_of(bool on_device) const { return hfdl::fft_side(fft_rule, on_device); }
+	hipStream_t fft_stream(int side) const { return side == hfdl::FFT_SERIAL ? stream.s : stream_f.owned ? stream_f.s : stream_c.s; }
 	static constexpr int MAX_HALF = hfdl::FOLD_MAX_BLOCKS;      // blocks per half at most: what one fold launch can take (32)
 	static constexpr int MAX_STAGE = HFDL_GPU_PREFETCH_MAX + 1;      // staging buffers for host input at most: uploads run at most 17 blocks ahead
 	static_assert(MAX_HALF == hfdl::PLAN_MAX_HALF && MAX_STAGE == hfdl::PLAN_MAX_STAGE && HFDL_GPU_FOLD_BATCH_MAX == MAX_HALF, "include/hfdl_gpu.h, kernels.h and planner.h name the same limits");
@@ -222,7 +225,8 @@ struct hfdl_gpu_frontend {
 	hfdl::DoneEvent dm[2][MAX_HALF];
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)
 	hfdl::DoneEvent fft_done;           // the last forward FFT of a half on stream A: what the held-back demodulators wait for
-	hfdl::DoneEvent spec[2];            // newest forward FFT of the half in spectrum set 0 / 1 done (rides on its last pass; stream F only, never timed)
+	hfdl::DoneEvent spec[2];            // newest forward FFT BESIDE the fold (stream C / F) of the half in spectrum set 0 / 1 done (rides on its last pass): what the half's fold waits for
+	hfdl::Event ev_switch;              // recorded on the stream of the forward FFT before, where a block's FFT runs on the other one
 	hfdl::Event ev_demod[2];            // recorded behind the last burst decoder of the half
 	hfdl::Event ev_stage_ready[MAX_STAGE];      // copy of the host block in this buffer done: what its forward FFT and input_done_upto() wait for
 	hfdl::Event ev_stage_free[MAX_STAGE];       // pass 1 of the forward FFT that read this buffer done (rides on that dispatch): the copy stream may refill it

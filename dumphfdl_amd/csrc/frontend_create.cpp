@@ -190,7 +190,7 @@ extern "C" int hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int
 // where the fold bounds the block (planner.h plan_cu_partition); the forward FFTs then get a stream of their own.  Measured slower than
 // the plain streams on cfg3 (profiles/r09_experiments.md section 2): not the product's path.
 // Order of creation: the runtime hands its hardware queues (four by default) to streams in turn, and two streams on one queue run in
-// turn -- the four that carry kernels (A, B, D, F) come first, the copy stream after them.
+// turn -- A, B, D (and the laboratory's F) come first, the input stream C after them: the fourth stream of the product, as it has been.
 static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
 {
 	CuPartition part = plan_cu_partition((int)fe->freqs.size(), Demod::workgroup_lds(), fe->fold_bound);
@@ -227,15 +227,17 @@ static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
 	if (lab.decode_stream) CREATE_TRY(fe->stream_d.create());
 	else fe->stream_d.alias(fe->stream_b);
 	fe->demod.separate_decode = fe->own_decode_stream();
-	// Forward FFTs of the half being filled on a stream of their own, beside the fold of the half before (two sets of spectra / phasor
-	// tables / state snapshots): a laboratory switch, and what goes with the CU partition, where stream A alone would be serial.  Round 4
-	// measured it slower on cfg3 (beside demodulator workgroups of 117 KiB of LDS); with the 37 KiB demodulator it gains 2 - 4 % on cfg3
-	// and 8 % on cfg4 from device-resident input and loses 16 % with host input (profiles/r09_experiments.md section 2), so the product
-	// keeps the FFTs in front of the fold on stream A.
+	// Forward FFTs of the half being filled beside the fold of the half before (two sets of spectra / phasor tables / state snapshots).
+	// The product decides per push by where the block lies (planner.h FftRule): a device-resident block's FFT runs on the input stream C,
+	// which carries no copy for such a block; an uploaded block's stays in front of the fold on stream A (a stream of their own for ALL
+	// forward FFTs gained 2 - 4 % on cfg3 and 8 % on cfg4 from device-resident input and lost 16 % with host input,
+	// profiles/r09_experiments.md section 2).  The laboratory's switch puts every FFT on stream A or on a stream F of their own, and the
+	// CU partition, where stream A alone would be serial, goes with the latter.
 	if (lab.fft_stream < 0 ? part.on : lab.fft_stream != 0) {
 		if (part.on) CREATE_TRY(fe->stream_f.create_on_cus(part.mask_fold));
 		else CREATE_TRY(fe->stream_f.create());
-	} else fe->stream_f.alias(fe->stream);
+		fe->fft_rule = FFT_RULE_OWN;
+	} else if (lab.fft_stream == 0) fe->fft_rule = FFT_RULE_SERIAL;
 	CREATE_TRY(fe->stream_c.create());
 	return 0;
 }
@@ -292,6 +294,7 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 		for (DoneEvent &d : fe->dm[i]) CREATE_TRY(d.own.create(EV_NO_TIMING));
 	}
 	CREATE_TRY(fe->fft_done.own.create(EV_NO_TIMING));
+	CREATE_TRY(fe->ev_switch.create(EV_NO_TIMING));
 	if (int rc = fe->fft.build(pl.n)) return rc;
 	const size_t n = (size_t)pl.n;
 	const size_t K = (size_t)nrx;

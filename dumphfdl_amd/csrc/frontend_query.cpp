@@ -115,7 +115,8 @@ extern "C" int hfdl_gpu_frontend_input_done(hfdl_gpu_frontend *fe)
 {
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	HIP_TRY(hipSetDevice(fe->device));
-	HIP_TRY(hipStreamSynchronize(fe->stream_c));
+	// the newest copy's event, not the stream: the input stream also carries the forward FFTs of device-resident blocks
+	if (fe->host_blocks) HIP_TRY(hipEventSynchronize(fe->input_event(fe->host_blocks - 1)));
 	return 0;
 }
 

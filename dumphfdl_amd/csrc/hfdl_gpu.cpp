@@ -82,7 +82,7 @@ int hfdl_gpu_frontend::settle_events()
 
 // ---------------------------------------------------------------- input staging
 
-extern "C" void *hfdl_gpu_frontend_stream(hfdl_gpu_frontend *fe) { return fe ? (void *)fe->stream_f.s : nullptr; }      // the stream that reads the input
+extern "C" void *hfdl_gpu_frontend_stream(hfdl_gpu_frontend *fe) { return fe ? (void *)fe->fft_stream(fe->side_of(true)) : nullptr; }      // the stream that reads device input
 
 // a block of input: a known sample format, exactly input_size samples
 static int check_block(const hfdl_gpu_frontend *fe, size_t nsamples, int fmt)
@@ -105,7 +105,7 @@ static int queue_input_copy(hfdl_gpu_frontend *fe, const void *const *iq, size_t
 	const size_t need = nsamples * (size_t)fe->nrx;
 	if (fe->stage_cap[sb] < need) {
 		HIP_TRY(hipStreamSynchronize(fe->stream_c));
-		HIP_TRY(hipStreamSynchronize(fe->stream_f));
+		HIP_TRY(hipStreamSynchronize(fe->fft_stream(fe->side_of(false))));
 		fe->stage_cap[sb] = 0;
 		fe->d_stage[sb] = std::make_unique<DevBuf>();
 		HIP_TRY(fe->d_stage[sb]->alloc(sizeof(float2) * need));
@@ -123,12 +123,13 @@ static int queue_input_copy(hfdl_gpu_frontend *fe, const void *const *iq, size_t
 	fe->host_blocks = j + 1;
 	// a buffer this library did not allocate may be reused by the caller as soon as we return (include/hfdl_gpu.h): do not
 	// rely on the runtime staging pageable memory synchronously -- wait for the copy (the kernels of the previous block keep running)
-	if (!pinned) HIP_TRY(hipStreamSynchronize(fe->stream_c));
+	if (!pinned) HIP_TRY(hipEventSynchronize(fe->ev_stage_ready[sb]));
 	*sb_out = sb;
 	return 0;
 }
 
-// Host input is staged in HBM: the copies (stream C) run up to n_stage - 1 blocks ahead of the blocks that compute (stream A).
+// Host input is staged in HBM: the copies (stream C) run up to n_stage - 1 blocks ahead of the blocks that compute (stream A).  Device
+// input is read where it lies, by a forward FFT on stream C itself (enqueue_fft).
 // iq[0 .. nrx - 1]: one block of every receiver; in.fresh[] receives where the forward FFT reads them.
 // *stage_idx = staging buffer used (-1 for device input): the forward FFT's first pass signals ev_stage_free when it has read it.
 static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int fmt, int on_device, FftInputs &in, int *stage_idx)
@@ -155,7 +156,7 @@ static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsam
 		if (rc) return rc;
 	}
 	fe->host_pushed++;
-	HIP_TRY(hipStreamWaitEvent(fe->stream_f, fe->ev_stage_ready[sb], 0));
+	HIP_TRY(hipStreamWaitEvent(fe->fft_stream(fe->side_of(false)), fe->ev_stage_ready[sb], 0));
 	for (int r = 0; r < fe->nrx; r++) in.fresh[r] = fe->d_stage[sb]->as<const char>() + (size_t)r * sample_bytes(fmt) * nsamples;
 	*stage_idx = sb;
 	return 0;
@@ -192,10 +193,10 @@ extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 	if (int rc = single_receiver_only(fe, "hfdl_gpu_frontend_prefetch_cancel")) return rc;
 	if (fe->host_pushed == fe->host_blocks) return 0;
 	HIP_TRY(hipSetDevice(fe->device));
-	// the copies are in flight on stream C: let them finish (the caller gets its buffers back), then forget the blocks.  They keep
+	// the copies are in flight on stream C: let the newest finish (the caller gets its buffers back), then forget the blocks.  They keep
 	// their host block numbers -- input_done_upto() of those numbers returns at once.  Their staging buffers are refilled by later
 	// copies, which wait for ev_stage_free as last recorded by the blocks that used the buffers BEFORE the cancelled ones: long done.
-	HIP_TRY(hipStreamSynchronize(fe->stream_c));
+	HIP_TRY(hipEventSynchronize(fe->input_event(fe->host_blocks - 1)));
 	fe->host_pushed = fe->host_blocks;
 	return 0;
 }
@@ -206,7 +207,7 @@ extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 // Launched the moment the channelizer of a half is done, they race the next blocks' forward-FFT workgroups for LDS and
 // the outcome depends on details as small as the FFT's LDS footprint: measured on MI355X, the same fold kernel took
 // 2.56 ms or 2.87 ms per launch (profiles/r01_experiments.md).  So the demodulator launches of a half are held back until the
-// forward FFTs of the NEXT half have been queued: the workgroups then arrive while only the LDS-free fold kernel is resident, spread
+// forward FFTs of the NEXT half have been queued on stream A: the workgroups then arrive while only the LDS-free fold kernel is resident, spread
 // evenly, and the fold time is the good one every time.  A sync / poll launches held-back demodulators at once.
 // A half of `nblk` blocks is demodulated `batch` blocks per launch, each launch followed by its burst decoder.
 static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, bool after_fft)
@@ -243,31 +244,46 @@ static int flush_pending_demod(hfdl_gpu_frontend *fe, bool after_fft)
 	return launch_demod(fe, buf, nblk, after_fft);
 }
 
-// Stream A, when a block is pushed: its forward FFT into the next spectrum slot of the half being filled (the block's NCO phasor
-// table and carried state ride on the three pass launches).  Nothing else happens until the half is closed.
-static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_idx)
+// When a block is pushed: its forward FFT into the next spectrum slot of the half being filled (the block's NCO phasor table and carried
+// state ride on the three pass launches) -- on stream A for an uploaded block, on the input stream, beside the fold of the half before,
+// for a device-resident one (planner.h FftOrder has the rules).  Nothing else happens until the half is closed.
+static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_idx, int on_device)
 {
 	const Geometry &g = fe->geo;
 	const int i = fe->batch_fill, set = fe->cur_half;
+	const FftPushPlan plan = fe->order.push(fe->side_of(on_device != 0), i, fe->half_target, fe->pending_demod_buf >= 0);
+	const hipStream_t st = fe->fft_stream(plan.side);
+	// a forward FFT beside the fold carries nothing the held-back demodulators of the half before could wait for: launched now, as a sync would
+	if (plan.flush_before)
+		if (int rc = flush_pending_demod(fe, false)) return rc;
+	if (plan.wait_switch) {
+		// the forward FFT before this one ran on the other stream (mixed input: rare): behind everything queued there so far
+		HIP_TRY(hipEventRecord(fe->ev_switch, fe->fft_stream(plan.side ^ 1)));
+		HIP_TRY(hipStreamWaitEvent(st, fe->ev_switch, 0));
+	}
+	// beside the fold: this set of spectra / phasor tables / snapshots was last read by the fold and inverse FFT two halves ago
+	if (plan.wait_set_free && fe->chan[set].pending()) HIP_TRY(hipStreamWaitEvent(st, fe->chan[set].event(), 0));
+	// ... and the first fold after a drain is left alone: behind the inverse FFT of the half just closed, as on stream A
+	if (plan.wait_first_fold) HIP_TRY(hipStreamWaitEvent(st, fe->chan[set ^ 1].event(), 0));
 	// The events other streams (and the bench's fold timer) wait for ride on the kernel dispatches themselves
 	// (hipExtLaunchKernelGGL start / stop events): a separate hipEventRecord is one more barrier packet in the queue, ~5 us
 	// of idle machine each (profiles/r01_experiments.md).
-	// FFT on stream A: the held-back demodulators of the half before follow the LAST forward FFT of this half (launch_demod)
-	const bool pend = !fe->fft_own_stream() && fe->pending_demod_buf >= 0 && i + 1 == fe->half_target;
-	// FFT on its own stream: this set of spectra / phasor tables / snapshots was last read by the fold and inverse FFT two halves ago
-	if (fe->fft_own_stream() && i == 0) HIP_TRY(hipStreamWaitEvent(fe->stream_f, fe->chan[set].event(), 0));
 	NcoJob job;
 	job.cc = fe->d_cc; job.chain = fe->d_nco; job.snap = fe->snap_slot(set, i);
 	job.ph = fe->ph_slot(set, i); job.cont = fe->d_ph_cont;
 	job.nch = g.nch; job.outs = g.outs; job.post_input_size = g.post_input_size; job.post = g.post;
-	// timed (stream A only): the first pass' start and the last pass' stop ride on their dispatches; the stop event doubles as "this forward FFT is done"
+	// timed: the first pass' start and the last pass' stop ride on their dispatches; the stop event doubles as "this forward FFT is done":
+	// what the half's fold waits for (beside the fold), what the held-back demodulators of the half before follow (the LAST forward
+	// FFT of a half on stream A, launch_demod)
 	hipEvent_t fft_start = nullptr, fft_done = nullptr;
-	if (fe->fft_own_stream()) fft_done = fe->spec[set].signal();
-	else if (int rc = pend ? fe->timers.arm(ST_FFT, 1, fe->fft_done, fft_start) : fe->timers.arm(ST_FFT, 1, fft_start, fft_done)) return rc;
-	if (pend) fft_done = fe->fft_done.event();
+	if (plan.side == FFT_BESIDE || plan.hold_after) {
+		DoneEvent &done = plan.side == FFT_BESIDE ? fe->spec[set] : fe->fft_done;
+		if (int rc = fe->timers.arm(ST_FFT, 1, done, fft_start)) return rc;
+		fft_done = done.event();
+	} else if (int rc = fe->timers.arm(ST_FFT, 1, fft_start, fft_done)) return rc;
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
-	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, fe->stream_f,
+	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, st,
 			FftOutLayout(), fft_done, job,
 			stage_idx >= 0 ? fe->ev_stage_free[stage_idx].e : nullptr,      // input consumed once pass 1 is done: the copy stream may refill the buffer
 			fft_start);
@@ -289,7 +305,7 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 			m.row_fresh = h->open_blocks == 0;
 			done = h->ev[slot];
 		}
-		launch_spectrum_monitor(m, fe->stream_f, done);
+		launch_spectrum_monitor(m, st, done);
 		mon->last = done;
 		for (int r = 0; r < fe->nrx; r++) {
 			if ((mon->fresh >> r) & 1) { mon->blocks[(size_t)r] = 0; mon->first[(size_t)r] = fe->blocks; }
@@ -301,7 +317,7 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		}
 		mon->fresh = 0;
 	}
-	if (pend) {
+	if (plan.hold_after) {
 		int rc = flush_pending_demod(fe, true);
 		if (rc) return rc;
 	}
@@ -321,7 +337,8 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	if (nblk == 0) return 0;
 	const Geometry &g = fe->geo;
 	const int half = fe->cur_half;
-	if (fe->fft_own_stream()) HIP_TRY(hipStreamWaitEvent(fe->stream, fe->spec[half].event(), 0));      // the newest forward FFT of this half (stream F)
+	const HalfClosePlan plan = fe->order.close(launch_now);
+	if (plan.wait_input) HIP_TRY(hipStreamWaitEvent(fe->stream, fe->spec[half].event(), 0));      // the newest forward FFT of this half beside the fold (stream C / F)
 	// launches of up to `fold_nb` blocks (fold_launch_blocks), each timed and counted as the launch it is: the shape the bench prices is a
 	// launch that happened
 	for (int done = 0, take = 0; done < nblk; done += take) {
@@ -371,8 +388,8 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	if (!with_demod) return 0;                   // channelize-only: the half is simply left behind
 	fe->prev_demod_buf = fe->demod_buf;          // what poll_pdus_ready(.., 1) waits for: the half before the newest one
 	fe->demod_buf = half;
-	// (forward FFTs on their own stream run beside everything anyway: there is no quiet moment to hold the demodulators back for)
-	if (launch_now || fe->fft_own_stream()) return launch_demod(fe, half, nblk, false);
+	// (forward FFTs beside the fold run beside everything anyway: there is no quiet moment to hold the demodulators back for)
+	if (!plan.hold_back) return launch_demod(fe, half, nblk, false);
 	fe->pending_demod_buf = half;
 	fe->pending_demod_nblk = nblk;
 	return 0;
@@ -388,7 +405,7 @@ extern "C" int hfdl_gpu_frontend_channelize_block(hfdl_gpu_frontend *fe, const f
 	if ((rc = stage_input(fe, one, nsamples, SFMT_CF32, on_device, in, &sidx))) return rc;
 	if ((rc = flush_pending_demod(fe, false))) return rc;
 	if ((rc = close_half(fe, true))) return rc;             // blocks pushed for the demodulator and not yet handed to it
-	if ((rc = enqueue_fft(fe, in, SFMT_CF32, sidx))) return rc;
+	if ((rc = enqueue_fft(fe, in, SFMT_CF32, sidx, on_device))) return rc;
 	return close_half(fe, false, false);                    // this block is never demodulated
 }
 
@@ -422,7 +439,7 @@ static int push_any(hfdl_gpu_frontend *fe, const void *const *raw, size_t nsampl
 	int sidx = -1;
 	int rc = stage_input(fe, raw, nsamples, fmt, on_device, in, &sidx);
 	if (rc) return rc;
-	if ((rc = enqueue_fft(fe, in, fmt, sidx))) return rc;
+	if ((rc = enqueue_fft(fe, in, fmt, sidx, on_device))) return rc;
 	if (fe->batch_fill < fe->half_target) return 0;         // the half is still filling
 	// demodulator-bound geometry (few channels): the fold is short, there is nothing to place the demodulator under, and
 	// holding it back until the NEXT half's forward FFTs would put those blocks' host -> device copies on the demodulator's
@@ -462,6 +479,7 @@ extern "C" int hfdl_gpu_frontend_sync(hfdl_gpu_frontend *fe)
 	{ int rc = close_half(fe, true); if (rc) return rc; }           // blocks waiting for their half to fill: folded and demodulated now
 	fe->half_target = fe->half_first;                               // a drain: the pipeline starts over with a short first half
 	for (const Stream *s : { &fe->stream_c, &fe->stream_f, &fe->stream, &fe->stream_b, &fe->stream_d }) HIP_TRY(s->sync());      // (an alias is its owner's to synchronise)
+	fe->order.drained();
 	HIP_TRY(hipGetLastError());
 	return fe->settle_events();
 }

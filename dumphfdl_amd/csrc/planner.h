@@ -254,6 +254,62 @@ inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sampl
 	return b;
 }
 
+// ---------------------------------------------------------------- which stream a block's forward FFT runs on
+
+// A block's forward FFT runs either SERIAL -- on stream A, in front of the fold of its own half and behind the fold of the half before --
+// or BESIDE: on the input stream (stream C; the laboratory's stream F), while stream A folds the half before.  The forward FFT is
+// HBM-bound and the fold bound on the matrix pipe, so a block that is already in HBM goes beside; a block that was uploaded keeps its FFT
+// on stream A, where the staging ring and the demodulator hold-back are tuned for it (a copy stream busy with kernels would put the
+// uploads behind them).  Chosen per push.  The laboratory build can put every FFT on one side (HFDL_GPU_FFT_STREAM).
+enum FftSide { FFT_SERIAL = 0, FFT_BESIDE = 1 };
+enum FftRule { FFT_RULE_INPUT, FFT_RULE_SERIAL, FFT_RULE_OWN };     // by where the block lies / all on stream A / all on stream F
+inline int fft_side(FftRule rule, bool on_device) { return rule == FFT_RULE_INPUT ? (on_device ? FFT_BESIDE : FFT_SERIAL) : rule == FFT_RULE_OWN ? FFT_BESIDE : FFT_SERIAL; }
+
+// What the launch of one forward FFT has to do besides the launch, and what the closing of a half has to.  The forward FFTs form a chain
+// (overlap history, work buffer, NCO state) and share two sets of spectra / phasor tables / snapshots with the fold and inverse FFT:
+//   - consecutive FFTs on one stream are ordered by it; an FFT on the other stream than the one before first waits for everything queued
+//     on that stream so far (wait_switch)
+//   - the first FFT of a half, BESIDE: its set was last read by the fold and inverse FFT two halves ago, on stream A (wait_set_free);
+//     SERIAL, stream A orders it
+//   - the first fold after a drain runs alone, with everything behind it waiting for it: forward FFTs beside it would only slow it down
+//     (20 blocks into an idle pipeline: 16 + 4, and the four blocks' FFTs took 0.2 ms out of the fold of the sixteen).  The first FFT of the
+//     SECOND half since a drain, BESIDE, therefore waits for the inverse FFT of the first (wait_first_fold) -- where it would be on stream A
+//   - the fold of a half waits for the newest BESIDE FFT of that half, if there is one (HalfClosePlan::wait_input)
+//   - held-back demodulators (fold-bound geometries, launch_demod): a half's launches are held back only if its newest FFT ran SERIAL --
+//     the next half is then expected in front of the fold as well -- and go behind the LAST serial FFT of the next half, which carries the
+//     event they wait for (hold_after).  A BESIDE FFT carries no such event: it launches what is held back at once, in front of
+//     itself (flush_before), so that nothing ever waits for an event no launch will signal
+struct FftPushPlan { int side; bool wait_switch, wait_set_free, wait_first_fold, flush_before, hold_after; };
+struct HalfClosePlan { bool wait_input, hold_back; };
+struct FftOrder {
+	int prev_side = -1;             // side of the newest forward FFT; -1: none since everything queued was waited for
+	bool half_beside = false;       // an FFT of the half being filled ran BESIDE
+	int halves = 0;                 // halves closed since everything queued was waited for
+	// fill: blocks already in the half being filled, target: blocks that close it, held_back: the half before waits for its demodulators
+	FftPushPlan push(int side, int fill, int target, bool held_back)
+	{
+		FftPushPlan p{};
+		p.side = side;
+		p.wait_switch = prev_side >= 0 && prev_side != side;
+		p.wait_set_free = side == FFT_BESIDE && fill == 0;
+		p.wait_first_fold = side == FFT_BESIDE && fill == 0 && halves == 1;
+		p.flush_before = side == FFT_BESIDE && held_back;
+		p.hold_after = side == FFT_SERIAL && held_back && fill + 1 == target;
+		prev_side = side;
+		half_beside = half_beside || side == FFT_BESIDE;
+		return p;
+	}
+	// a half of at least one block is closed; launch_now: the caller wants its demodulators at once (a sync / poll, a demodulator-bound geometry)
+	HalfClosePlan close(bool launch_now)
+	{
+		const HalfClosePlan c{ half_beside, !launch_now && prev_side == FFT_SERIAL };
+		half_beside = false;
+		halves++;
+		return c;
+	}
+	void drained() { prev_side = -1; halves = 0; }      // every stream has been synchronised
+};
+
 // ---------------------------------------------------------------- the CU partition of the fold-bound geometries
 
 // Where the fold bounds the block, the demodulator's latency-bound waves and the fold's matrix waves are kept off each other's SIMDs:

@@ -186,13 +186,15 @@ int  hfdl_gpu_frontend_geometry(const hfdl_gpu_frontend *fe, hfdl_gpu_geometry *
 /* Enqueue one block: exactly geometry.input_size new complex samples (interleaved I,Q float32).  Asynchronous: the block's forward
  * FFT is queued at once; fold, inverse FFT, demodulator and burst decoder follow when geometry.fold_batch blocks are waiting or the
  * caller syncs / polls, whichever comes first (the results do not depend on which).
- * on_device != 0: `iq` is a device pointer that stays valid until the next sync.
+ * on_device != 0: `iq` is a device pointer that stays valid until the next sync; its forward FFT runs on the input stream
+ *   (hfdl_gpu_frontend_stream()), beside the fold of the blocks before.  Host and device blocks may be mixed freely.
  * on_device == 0: the host -> device copy runs on its own stream into a ring of geometry.prefetch_depth + 1 staging buffers, so the copies
  *   run up to a whole half (fold_batch blocks, or more where demod_batch is larger) ahead of the kernels.  A buffer from hfdl_gpu_host_alloc() (page-locked) is read by DMA after the call
  *   returns: reuse it only after hfdl_gpu_frontend_input_done() / _sync() / _poll_pdus().  Any other host buffer (pageable,
  *   or registered by the caller) is waited for inside the call and may be reused as soon as it returns. */
 int  hfdl_gpu_frontend_push_block(hfdl_gpu_frontend *fe, const float *iq, size_t nsamples, int on_device);
-/* wait until every host -> device input copy enqueued so far has finished (the kernels keep running) */
+/* wait until every host -> device input copy enqueued so far has finished (the kernels keep running, the forward FFTs of device
+ * blocks on the same stream included) */
 int  hfdl_gpu_frontend_input_done(hfdl_gpu_frontend *fe);
 /* wait until the copy of host block number `host_block` (0 = the first block pushed with on_device == 0) has finished, WITHOUT
  * waiting for the blocks pushed after it: a caller that leases two page-locked buffers pushes block k+1, then waits for block k and
@@ -249,8 +251,11 @@ typedef struct {
 	uint32_t pdu_ring_capacity;
 } hfdl_gpu_frontend_counters_t;
 int  hfdl_gpu_frontend_counters(hfdl_gpu_frontend *fe, hfdl_gpu_frontend_counters_t *out);
-/* the HIP stream the channelizer kernels (forward FFT, fold, inverse FFT) are launched on (hipStream_t as void*); device
- * input handed to push_block must be complete on, or synchronised with, this stream */
+/* the HIP stream that reads device-resident input (hipStream_t as void*): the front end's input stream, on which the forward FFT of a
+ * block pushed with on_device != 0 is launched -- beside the fold of the blocks before, which runs on a stream of its own -- and which
+ * carries the host -> device copies of the other blocks.  Device input handed to push_block must be complete on, or synchronised with,
+ * this stream: a block produced ON it (a kernel or a device-side copy queued there before the push) needs no synchronisation at all.
+ * The push contract is unchanged: the pointer stays valid until the next sync, the forward FFT is queued at once */
 void *hfdl_gpu_frontend_stream(hfdl_gpu_frontend *fe);
 
 /* per-channel observability: the hot-path StatsD counters and the noise-floor gauge of the reference

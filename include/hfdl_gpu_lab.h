@@ -5,8 +5,9 @@
  * include/hfdl_gpu.h, plus the fold tiling sweep, the probes below and the A/B environment switches the scripts under profiles/
  * use.  Nothing here is part of the drop-in boundary; the product library exports none of it (tests/test_host_lib_cpu.py checks).
  *
- *   HFDL_GPU_FFT_STREAM=0|1   forward FFTs of the half being filled on the fold's stream / on a stream of their own (default: their own
- *                             stream where the CU partition applies)
+ *   HFDL_GPU_FFT_STREAM=0|1   EVERY forward FFT on the fold's stream / on a stream of their own, whatever the input (default: the
+ *                             product's rule -- a device-resident block's on the input stream, an uploaded block's on the fold's; their
+ *                             own stream where the CU partition applies)
  *   HFDL_GPU_CU_PARTITION=1   the CU partition of the fold-bound geometries (planner.h plan_cu_partition): demodulators and channelizer
  *                             on disjoint CUs; nothing below 128 channels
  *   HFDL_GPU_DECODE_STREAM=0  burst decoders back on the demodulators' stream
