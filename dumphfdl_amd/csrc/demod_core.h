@@ -4,11 +4,11 @@
 // msresamp -> AGC -> matched filter -> symsync -> Costas -> LMS equaliser -> M-PSK slicer -> preamble
 // correlator / framer.
 //
-// Mapping: ONE WORKGROUP OF THREE WAVEFRONTS PER CHANNEL, the waves forming a software pipeline over chunks of DM_CHUNK
+// Mapping: ONE WORKGROUP OF FOUR WAVEFRONTS PER CHANNEL, the waves forming a software pipeline over chunks of DM_CHUNK
 // 5400-sps samples.  The reference runs these stages as one serial loop; three of them are genuine recurrences (the AGC gain,
 // the symbol-timing loop, the carrier loop + equaliser + framer FSM) and each costs a lone wavefront a few hundred cycles per
-// sample in dependent-instruction latency.  They only feed FORWARD -- AGC -> timing recovery -> carrier/equaliser/framer --
-// with one rare exception, so they run concurrently on three SIMDs of the CU:
+// sample in dependent-instruction latency.  They only feed FORWARD -- resampler -> AGC -> timing recovery -> carrier/equaliser/framer --
+// with one rare exception, so they run concurrently on the four SIMDs of the CU (WAVE_RESAMPLER, WAVE_AGC, WAVE_TIMING, WAVE_CARRIER):
 //
 //   wave 3   arbitrary resampler (msresamp_crcf_execute; no recurrence: a lane per output) of chunk s+1, and the channelizer samples
 //            of chunk s+3 fetched from HBM into an LDS ring
@@ -25,7 +25,9 @@
 // sample k it publishes k, and wave 1 restarts at k+1 from the reset state, which is fully determined (empty matched-filter
 // window, the last 18 matched-filter samples in the derivative window, initial loop scalars).  Results are those of the
 // serial order, sample for sample; resets are rare (once per frame), so the re-run costs nothing measurable.
-// The waves meet at one workgroup barrier per chunk and exchange progress through a double-buffered LDS mailbox.
+// The waves meet at one workgroup barrier per chunk and exchange progress through a double-buffered LDS mailbox (demod_lds.h PipeMail):
+// in a step every wave works on what the mailbox of the step before allowed it, lane 0 publishes how far it got, and after the barrier
+// all four read the same PipeProgress.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "demod_logic.h"
@@ -34,6 +36,7 @@
 namespace hfdl {
 
 constexpr int DM_WAVES = 4, DM_THREADS = 64 * DM_WAVES;      // (chunk and ring sizes: demod_lds.h)
+constexpr int WAVE_AGC = 0, WAVE_TIMING = 1, WAVE_CARRIER = 2, WAVE_RESAMPLER = 3;      // the pipeline's stages by wave: the order of PipeMail::busy[]
 
 // ---- DPP helpers (GFX9 encodings): all row-local, a row = 16 lanes ----
 __device__ __forceinline__ float dpp_row_shr1(float old, float src)      // lane i <- src[i-1]; lane 0 of every row <- old
@@ -88,31 +91,99 @@ __device__ __forceinline__ float lane_value(float v, int lane)           // wave
 	return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
-// what the three waves share through LDS besides the sample buffers
+// what the four waves share through LDS besides the sample rings
 struct DemodShared {
 	cf *outq;                      // symsync outputs of the launch, in order: output j at outq[j & (OUTQ_RING - 1)]
 	int outq_cap;                  // outputs a launch may produce at most (the 16-bit counts of cum[]); beyond it they are dropped
 	uint16_t *cum;                 // cum[k & DM_MASK] = outputs produced up to and including input sample k
 	const float2 *sstab;           // [16 banks][64 lanes] {tap t, tap t+16} of the lane's row: rows 0,1 matched filter, rows 2,3 derivative
 	ChanScalars *S;                // the channel's scalars; every wave owns a disjoint set of fields
-	int *mbox;                     // [2][8] progress mailbox: {mf_ready, ss_to, s3_done, s3_reset, rs_ready}
+	PipeMail *mbox;                // [2] progress mailbox, written in turn: step s uses mbox[s & 1]
 	float *sink;                   // [64] write-only scratch, one word per lane
 	cf *stage;                     // [64] the carrier wave's data symbols of one chunk (a chunk has at most 64 outputs)
 };
 
-// progress of the three stages as every wave sees it after a step's barrier
-struct PipeProgress {
-	int rs_ready = 0, mf_ready = 0, ss_ready = 0, s3_done = 0;
-	bool restart = false;
-	__device__ __forceinline__ void read(const int *mb)
+// The mailbox of a step: mbox[step & 1], its offset worked out in ints.
+__device__ __forceinline__ PipeMail &step_mail(PipeMail *mbox, int step)
+{
+	return *(PipeMail *)((int *)mbox + (int)(sizeof(PipeMail) / sizeof(int)) * (step & 1));
+}
+
+// ---------------- experiment builds: -DHFDL_DM_PROBE=2 .. 6 (profiles/probe_states.py, profiles/wave_cycles.py) ----------------
+// Counters reported in the phase-cycle slots of the level tap, from PHASE_AHEAD on, over what the product puts there:
+//   = 2  the carrier wave's cycles per framer state -- searching, equaliser training, data -- in three slots;  = 3  its outputs, likewise
+//   = 4  wave 0's busy cycles (AGC + matched filter), = 5  wave 3's (resampler + input fetch), counted like the product's counters of
+//        waves 1 and 2 from the step's start to the mailbox write
+//   = 6  the sum over the steps of the longest of waves 0, 1, 2 in that step: what it leaves of the pipelined phase is the barrier and
+//        mailbox step itself
+// The product defines none of it: both types are empty then, and what demod_block() and carrier_chunk() call compiles to nothing.
+#ifdef HFDL_DM_PROBE
+struct StateProbe {                // = 2, = 3: per framer state
+	unsigned long long search = 0, train = 0, data = 0;
+	__device__ __forceinline__ unsigned long long now() const { return __builtin_amdgcn_s_memtime(); }
+	__device__ __forceinline__ void iteration(unsigned long long t0, int fr_state)      // a general iteration begun at t0 in fr_state: one output
 	{
-		rs_ready = mb[4];
-		mf_ready = mb[0];
-		s3_done = mb[2];
-		restart = mb[3] != 0;
-		ss_ready = restart ? s3_done : mb[1];          // a reset discards what wave 1 computed beyond the reset sample
+		const unsigned long long dt = HFDL_DM_PROBE == 2 ? __builtin_amdgcn_s_memtime() - t0 : 1ull;
+		if (fr_state == FR_A1) search += dt; else if (fr_state == FR_EQ_TRAIN) train += dt; else if (fr_state == FR_DATA_1 || fr_state == FR_DATA_2) data += dt;
+	}
+	__device__ __forceinline__ void frame_run(unsigned long long t0, bool training, int n_run)
+	{
+		const unsigned long long dt = HFDL_DM_PROBE == 2 ? __builtin_amdgcn_s_memtime() - t0 : (unsigned long long)n_run;
+		if (training) train += dt; else data += dt;
+	}
+	__device__ __forceinline__ void search_run(int n_run) { if (HFDL_DM_PROBE == 3) search += (unsigned long long)n_run; }
+};
+struct StepClock {                 // = 4, 5, 6: per step of the pipeline
+	unsigned long long t0 = 0, longest = 0;
+	template <int WAVE> static constexpr bool clocks() { return (WAVE == WAVE_AGC && (HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 6)) || (WAVE == WAVE_RESAMPLER && HFDL_DM_PROBE == 5); }
+	template <int WAVE> __device__ __forceinline__ void begin() { if (clocks<WAVE>()) t0 = __builtin_amdgcn_s_memtime(); }
+	// behind the wave's mailbox write: into the wave's busy cycles, or (= 6) this step's into the mailbox
+	template <int WAVE> __device__ __forceinline__ void end(unsigned long long &busy, PipeMail &mail, int lane) const
+	{
+		if (!clocks<WAVE>()) return;
+		if (HFDL_DM_PROBE != 6) busy += __builtin_amdgcn_s_memtime() - t0;
+		else if (lane == 0) mail.busy[WAVE] = (int)(__builtin_amdgcn_s_memtime() - t0);
+	}
+	// = 6, waves 1 and 2: they clock their steps for the product's counters already, from `since`
+	template <int WAVE> __device__ __forceinline__ void end_since(unsigned long long since, PipeMail &mail, int lane) const
+	{
+		if (HFDL_DM_PROBE == 6 && lane == 0) mail.busy[WAVE] = (int)(__builtin_amdgcn_s_memtime() - since);
+	}
+	__device__ __forceinline__ void after_barrier(const PipeMail &mail)      // = 6: the step lasted as long as its longest wave
+	{
+		if (HFDL_DM_PROBE != 6) return;
+		const int m01 = mail.busy[WAVE_AGC] > mail.busy[WAVE_TIMING] ? mail.busy[WAVE_AGC] : mail.busy[WAVE_TIMING];
+		longest += (unsigned long long)(m01 > mail.busy[WAVE_CARRIER] ? m01 : mail.busy[WAVE_CARRIER]);
+	}
+	// all threads, behind the product's own phase cycles
+	__device__ __forceinline__ void report(float *tap_level, int cap, int wave, int lane, unsigned long long busy, const StateProbe &sp) const
+	{
+		__syncthreads();
+		float *slots = tap_level + phase_slot(cap, PHASE_AHEAD);
+		if (HFDL_DM_PROBE == 2 || HFDL_DM_PROBE == 3) {
+			if (wave == WAVE_CARRIER && lane == 0) { slots[0] = (float)sp.search; slots[1] = (float)sp.train; slots[2] = (float)sp.data; }
+		} else if (HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 5) {
+			if (wave == (HFDL_DM_PROBE == 4 ? WAVE_AGC : WAVE_RESAMPLER) && lane == 0) slots[0] = (float)busy;
+		} else if (HFDL_DM_PROBE == 6) {
+			if (wave == WAVE_CARRIER && lane == 0) slots[0] = (float)longest;
+		}
 	}
 };
+#else
+struct StateProbe {
+	__device__ __forceinline__ unsigned long long now() const { return 0ull; }
+	__device__ __forceinline__ void iteration(unsigned long long, int) {}
+	__device__ __forceinline__ void frame_run(unsigned long long, bool, int) {}
+	__device__ __forceinline__ void search_run(int) {}
+};
+struct StepClock {
+	template <int WAVE> __device__ __forceinline__ void begin() {}
+	template <int WAVE> __device__ __forceinline__ void end(unsigned long long &, PipeMail &, int) const {}
+	template <int WAVE> __device__ __forceinline__ void end_since(unsigned long long, PipeMail &, int) const {}
+	__device__ __forceinline__ void after_barrier(const PipeMail &) {}
+	__device__ __forceinline__ void report(float *, int, int, int, unsigned long long, const StateProbe &) const {}
+};
+#endif
 
 // ---------------- wave 0: AGC + matched filter of samples [a0, a1) ----------------
 
@@ -333,10 +404,6 @@ __device__ __forceinline__ void symsync_chunk(SymsyncRegs &r, const DemodConst &
 struct CarrierRegs {
 	float eu, ev, ex2, ewx, ewy;   // equaliser: lane 1 + t (t < 15) of rows 0 and 1 = tap t (0 oldest); row 0 holds (x, y), row 1 (y, -x)
 	float px, py;                  // lane i < 16: PSK constellation entry i (demod_tables.h psk_pts)
-#ifdef HFDL_DM_PROBE               // experiment builds (profiles/probe_states.py): = 2 carrier-wave cycles per framer state, = 3 outputs per state,
-                                   // reported in the phase-cycle slots of the level tap (= 4, = 5: wave 0's / wave 3's busy cycles, = 6: the sum over the steps of the longest wave, demod_block)
-	unsigned long long pa = 0, pb = 0, pc = 0;
-#endif
 };
 
 // The carrier wave's slicer.  modem_demodulate_psk takes arg(x), subtracts pi (1 - 1/M) and walks a binary reference ladder:
@@ -397,6 +464,21 @@ __device__ __forceinline__ void carrier_store(const CarrierRegs &c, ChanArrays &
 	}
 }
 
+// sine and cosine of the carrier NCO's phase.  |phase| <= pi: the hardware sin/cos (argument in revolutions) needs no range reduction
+__device__ __forceinline__ void nco_sincos(float phase, float &sp, float &cp)
+{
+#ifdef HFDL_DM_LIBM_TRIG              // experiment (profiles/r03_experiments.md): the library's accurate sincosf instead of v_sin / v_cos
+	sincosf(phase, &sp, &cp);
+#else
+	const float rev = phase * 0.15915494309189535f;
+	sp = __builtin_amdgcn_sinf(rev); cp = __builtin_amdgcn_cosf(rev);
+#endif
+}
+
+#ifndef HFDL_DM_OUT_LANES            // timing-recovery outputs a chunk of the carrier wave takes at most (a smaller value makes every chunk take
+#define HFDL_DM_OUT_LANES 64         // the cut: how that path was tested, profiles/r03_experiments.md)
+#endif
+
 // processes samples [k0, k1); returns the index of the sample during which the framer reset the timing loop (the wave stops
 // after that sample), or -1.
 // The loop runs over the timing-recovery OUTPUTS of the chunk, not over its input samples: two of three input samples yield an
@@ -408,7 +490,7 @@ __device__ __forceinline__ void carrier_store(const CarrierRegs &c, ChanArrays &
 // and at the end of the chunk -- the state is the same for all the samples in between, it only changes on such symbols.
 template <bool TAPS>
 __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, ChanArrays &a, const DemodConst &T, const BlockIo &io, const DemodShared &sh,
-		int k0, int &k1, int &nsym, int lane)
+		int k0, int &k1, int &nsym, int lane, StateProbe &probe)
 {
 	const int t = (lane & 15) - 1;
 	const bool row1 = (lane >> 4) & 1, act = t >= 0 && lane < 32;
@@ -422,9 +504,6 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 	oq_l.x = div3(oq_l.x); oq_l.y = div3(oq_l.y);      // the ring holds the timing recovery's raw row totals (symsync_chunk): out = total / 3
 	{   // the chunk's outputs are taken from the 64 lanes of oq_l: a chunk that produced more (a timing loop far off its rate: up to four
 		// outputs per input sample) is cut where they end, and k1 tells the caller
-#ifndef HFDL_DM_OUT_LANES            // (a smaller value makes every chunk take the cut: how that path was tested, profiles/r03_experiments.md)
-#define HFDL_DM_OUT_LANES 64
-#endif
 		const unsigned long long over = __ballot(lane < n && cum_l - jbase > HFDL_DM_OUT_LANES);
 		if (__builtin_expect(over != 0, 0)) { n = (int)__builtin_ctzll(over); k1 = k0 + n; }      // n >= 1: one sample yields at most 4 outputs
 	}
@@ -482,13 +561,8 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 			ph2 = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
 		}
 		s.phi = ph2;
-#ifdef HFDL_DM_LIBM_TRIG
 		float sp, cp;
-		sincosf((lane & 1) ? ph2 : ph1, &sp, &cp);
-#else
-		const float rev = ((lane & 1) ? ph2 : ph1) * 0.15915494309189535f;
-		const float sp = __builtin_amdgcn_sinf(rev), cp = __builtin_amdgcn_cosf(rev);
-#endif
+		nco_sincos((lane & 1) ? ph2 : ph1, sp, cp);
 		cf r;
 		r.x = oi.x * cp + oi.y * sp;
 		r.y = oi.y * cp - oi.x * sp;
@@ -533,9 +607,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 			if (n_run > s.symbols_wanted - 1) n_run = s.symbols_wanted - 1;
 			if ((!train || s.eq_full) && (!s.use_data || s.data_n + n_run <= MAX_DATA_SYMBOLS)) {
 				if (s.use_data && staged == 0) stage_at = s.data_slot * MAX_DATA_SYMBOLS + s.data_n;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE >= 2
-				const unsigned long long tR0 = __builtin_amdgcn_s_memtime();
-#endif
+				const unsigned long long t_run = probe.now();
 				int ki = 0;
 				for (int i = 0; i < n_run; i++, j += 2) {
 					pair_step(j);
@@ -565,12 +637,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 				s.symbol_cnt += (uint64_t)n_run;
 				s.symbols_wanted -= n_run;
 				if (s.use_data) s.data_n += n_run;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE >= 2
-				{
-					const unsigned long long dt = HFDL_DM_PROBE == 2 ? __builtin_amdgcn_s_memtime() - tR0 : (unsigned long long)n_run;
-					if (train) c.pb += dt; else c.pc += dt;
-				}
-#endif
+				probe.frame_run(t_run, train, n_run);
 			}
 		}
 	};
@@ -613,18 +680,14 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 		s.eq_count += 2u * (uint32_t)n_run;
 		s.symsync_out_idx += 2u * (uint32_t)n_run;
 		s.symbol_cnt += (uint64_t)(finished ? n_run : n_run - 1);      // the symbol that ended the run is on_symbol()'s to count
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 3
-		c.pa += (unsigned long long)n_run;
-#endif
+		probe.search_run(n_run);
 		return SearchRunEnd{finished, jo, y};
 	};
 	int j = jbase;
 	if (s.fr_state != FR_A1) in_frame_run(j);
 	while (j < jstop) {
-#ifdef HFDL_DM_PROBE
-		const unsigned long long tA0 = __builtin_amdgcn_s_memtime();
-		const int st0 = s.fr_state;
-#endif
+		const unsigned long long t_iter = probe.now();
+		const int state_iter = s.fr_state;
 		int jo;                                   // the output the rest of the iteration is about
 		bool on_time;
 		if (!(s.symsync_out_idx & 1u) && j + 1 < jstop && !runaway) {
@@ -641,14 +704,8 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 				const float dn = ph - (float)(2.0 * M_PI), up = ph + (float)(2.0 * M_PI);
 				s.phi = ph > (float)M_PI ? dn : (ph < -(float)M_PI ? up : ph);
 			}
-			// |phi| <= pi: the hardware sin/cos (argument in revolutions) needs no range reduction
-#ifdef HFDL_DM_LIBM_TRIG              // experiment (profiles/r03_experiments.md): the library's accurate sincosf instead of v_sin / v_cos
 			float sp, cp;
-			sincosf(s.phi, &sp, &cp);
-#else
-			const float rev = s.phi * 0.15915494309189535f;
-			const float sp = __builtin_amdgcn_sinf(rev), cp = __builtin_amdgcn_cosf(rev);
-#endif
+			nco_sincos(s.phi, sp, cp);
 			cf r;
 			r.x = oi.x * cp + oi.y * sp;
 			r.y = oi.y * cp - oi.x * sp;
@@ -757,12 +814,7 @@ __device__ __forceinline__ int carrier_chunk(CarrierRegs &c, ChanScalars &s, Cha
 				runaway = fabsf(s.dphi) > COSTAS_RUNAWAY_DPHI && s.fr_state == FR_A1;
 			}
 		}
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE >= 2
-		{
-			const unsigned long long dt = HFDL_DM_PROBE == 2 ? __builtin_amdgcn_s_memtime() - tA0 : 1ull;
-			if (st0 == FR_A1) c.pa += dt; else if (st0 == FR_EQ_TRAIN) c.pb += dt; else if (st0 == FR_DATA_1 || st0 == FR_DATA_2) c.pc += dt;
-		}
-#endif
+		probe.iteration(t_iter, state_iter);
 		if (__builtin_expect(s.ev_flags != 0, 0)) {
 			if (s.ev_flags & EV_EQ_RESET) {      // eqlms_cccf_reset ran (framer reset): mirror it in the register window
 				c.eu = 0.f; c.ev = 0.f; c.ex2 = 0.f;
@@ -811,11 +863,8 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	const uint64_t total = (uint64_t)n_in << 24;
 	int n_out = 0;
 	if ((uint64_t)rs_phase < total) n_out = (int)((total - rs_phase + T.rs_step - 1) / T.rs_step);
-	if (n_out > io.cap - 4) n_out = io.cap - 4;      // cannot happen: cap is sized from the geometry (+8); the last 4 level slots carry phase cycles
-	// channelizer samples the outputs [0, k_end) need; the whole input once the last output is covered (the hand-over below reads its end)
-	auto need = [&](int k_end) {
-		return k_end >= n_out ? n_in : (int)(((uint64_t)rs_phase + (uint64_t)(k_end - 1) * T.rs_step) >> 24) + 1;
-	};
+	if (n_out > io.cap - DM_PHASE_SLOTS) n_out = io.cap - DM_PHASE_SLOTS;      // cannot happen: cap is sized from the geometry (+8); the last level slots carry phase cycles
+	auto need = [&](int k_end) { return resampler_inputs(rs_phase, T.rs_step, k_end, n_out, n_in); };
 	// what the resampler leaves for the next launch, by wave 3 when it is done with the ring
 	auto resampler_store = [&]() {
 		cf nh;
@@ -831,16 +880,16 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	// ---- ahead of the pipeline: the histories in front of sample 0 of the input and AGC rings, the channelizer samples of the first
 	// three chunks, and the resampler's first chunk -- wave 0 starts on it at once
 	if (tid < D_RS_TAPS - 1) in.ring[(-1 - tid) & DM_IN_MASK] = a.rs_hist[tid];
-	if (wave == 1 && lane < D_MF - 1) io.agc[(-1 - lane) & DM_AGC_MASK] = a.mf_hist[lane];
+	if (wave == WAVE_TIMING && lane < D_MF - 1) io.agc[(-1 - lane) & DM_AGC_MASK] = a.mf_hist[lane];
 	const int rs0 = n_out < DM_CHUNK ? n_out : DM_CHUNK;
 	int in_loaded = need(rs0 + 2 * DM_CHUNK);
 	for (int g = tid; g < in_loaded; g += DM_THREADS) in.ring[g & DM_IN_MASK] = input_sample(in, g);
 	if (TAPS && tid == 0) io.tap_counts[1] = 0;
 	__syncthreads();
-	if (wave == 3) resample_outputs<TAPS>(rs_phase, T, io, in.ring, 0, rs0, lane);
+	if (wave == WAVE_RESAMPLER) resample_outputs<TAPS>(rs_phase, T, io, in.ring, 0, rs0, lane);
 	__syncthreads();
 	if (n_out < 1) {
-		if (wave == 3) resampler_store();
+		if (wave == WAVE_RESAMPLER) resampler_store();
 		return 0;
 	}
 
@@ -849,24 +898,19 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	// of barriers, same mailbox reads), so that only its own stage's state is live in its registers.
 	unsigned long long busy = 0;
 	int nsym = 0;
-#ifdef HFDL_DM_PROBE
-	unsigned long long cr_probe[3] = { 0, 0, 0 };
-#endif
+	StepClock clk;
+	StateProbe states;
 	PipeProgress pp;
 	pp.rs_ready = rs0;
-	if (wave == 3) {
+	if (wave == WAVE_RESAMPLER) {
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 8 * (step & 1);
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 5
-			const unsigned long long tb = __builtin_amdgcn_s_memtime();
-#endif
+			PipeMail &mail = step_mail(sh.mbox, step);
+			clk.begin<WAVE_RESAMPLER>();
 			int to = pp.rs_ready;
 			if (to < n_out) {
-				to = to + DM_CHUNK < n_out ? to + DM_CHUNK : n_out;
-				if (to > pp.s3_done + DM_RS_AHEAD) to = pp.s3_done + DM_RS_AHEAD;      // the ring holds that much (never binds while the waves run in step)
-				// the samples two chunks further on are asked for first and put into the ring last: a round trip to HBM beside the fold
-				// takes as long as a chunk
-				const int hi = need(to + 2 * DM_CHUNK < n_out ? to + 2 * DM_CHUNK : n_out);
+				to = resampler_advance(pp, n_out);
+				// the samples two chunks further on are asked for first and put into the ring last
+				const int hi = need(resampler_fetch_ahead(to, n_out));
 				cf nx[2];
 #pragma unroll
 				for (int u = 0; u < 2; u++) {
@@ -882,66 +926,49 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 				for (int g = in_loaded + 128 + lane; g < hi; g += 64) in.ring[g & DM_IN_MASK] = input_sample(in, g);      // (a chunk spans fewer than 65 samples)
 				if (hi > in_loaded) in_loaded = hi;
 			}
-			if (lane == 0) mb[4] = to;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 5
-			busy += __builtin_amdgcn_s_memtime() - tb;
-#endif
+			if (lane == 0) mail.rs_ready = to;
+			clk.end<WAVE_RESAMPLER>(busy, mail, lane);
 			__syncthreads();
-			pp.read(mb);
+			pp.read(&mail);
 		}
 		resampler_store();
-	} else if (wave == 0) {
+	} else if (wave == WAVE_AGC) {
 		float agc_g = S.agc_g, agc_y2 = S.agc_y2;
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 8 * (step & 1);
-#if defined(HFDL_DM_PROBE) && (HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 6)
-			const unsigned long long tb = __builtin_amdgcn_s_memtime();
-#endif
-			int to = pp.mf_ready + DM_CHUNK < pp.rs_ready ? pp.mf_ready + DM_CHUNK : pp.rs_ready;
-			// the matched-filter ring keeps what a restart of wave 1 can read (in step, wave 2 is two chunks behind and this never binds)
-			if (to > pp.s3_done + DM_MF_AHEAD) to = pp.s3_done + DM_MF_AHEAD;
+			PipeMail &mail = step_mail(sh.mbox, step);
+			clk.begin<WAVE_AGC>();
+			int to = agc_advance(pp);
 			if (to > pp.mf_ready) agc_mf_chunk<TAPS>(agc_g, agc_y2, T, io, pp.mf_ready, to, lane); else to = pp.mf_ready;
-			if (lane == 0) mb[0] = to;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 4
-			busy += __builtin_amdgcn_s_memtime() - tb;
-#elif defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
-			if (lane == 0) mb[5] = (int)(__builtin_amdgcn_s_memtime() - tb);
-#endif
+			if (lane == 0) mail.mf_ready = to;
+			clk.end<WAVE_AGC>(busy, mail, lane);
 			__syncthreads();
-			pp.read(mb);
+			pp.read(&mail);
 		}
 		cf nh;
 		if (lane < D_MF - 1) nh = io.agc[(n_out - 1 - lane) & DM_AGC_MASK];       // reaches into the entries in front of sample 0 when n_out < 18
 		__builtin_amdgcn_wave_barrier();
 		if (lane < D_MF - 1) a.mf_hist[lane] = nh;
 		if (lane == 0) { S.agc_g = agc_g; S.agc_y2 = agc_y2; }
-	} else if (wave == 1) {
+	} else if (wave == WAVE_TIMING) {
 		SymsyncRegs ss;
 		symsync_load(ss, S, a, io, lane);
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 		__builtin_amdgcn_wave_barrier();
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 8 * (step & 1);
+			PipeMail &mail = step_mail(sh.mbox, step);
 			const unsigned long long tb = TAPS ? __builtin_amdgcn_s_memtime() : 0ull;
 			if (pp.restart) symsync_restart(ss, sh, pp.ss_ready);
-			int to = pp.ss_ready + DM_CHUNK < pp.mf_ready ? pp.ss_ready + DM_CHUNK : pp.mf_ready;
-			// never more than two chunks ahead of what wave 2 has finished: the output ring holds that much (in step, wave 2 is exactly one
-			// chunk behind and this never binds; it does when a timing loop far off its rate makes wave 2 cut its chunks short)
-			if (to > pp.s3_done + 2 * DM_CHUNK) to = pp.s3_done + 2 * DM_CHUNK;
-			if (to < pp.ss_ready) to = pp.ss_ready;
+			const int to = timing_advance(pp);
 			for (int k0 = pp.ss_ready; k0 < to;) {
 				const int k1 = (k0 | DM_MASK) + 1 < to ? (k0 | DM_MASK) + 1 : to;      // a chunk that crosses the ring's wrap: two pieces
 				if (__builtin_expect(k0 - (D_SS_TAPS - 1) < ss.valid_from, 0)) symsync_chunk<true>(ss, T, io, sh, k0, k1, lane);
 				else symsync_chunk<false>(ss, T, io, sh, k0, k1, lane);
 				k0 = k1;
 			}
-			if (lane == 0) mb[1] = to;
-			if (TAPS) busy += __builtin_amdgcn_s_memtime() - tb;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
-			if (TAPS && lane == 0) mb[6] = (int)(__builtin_amdgcn_s_memtime() - tb);
-#endif
+			if (lane == 0) mail.ss_ready = to;
+			if (TAPS) { busy += __builtin_amdgcn_s_memtime() - tb; clk.end_since<WAVE_TIMING>(tb, mail, lane); }
 			__syncthreads();
-			pp.read(mb);
+			pp.read(&mail);
 		}
 		if (pp.restart) symsync_restart(ss, sh, n_out);      // a reset during the launch's last sample
 		symsync_store(ss, S, a, io, n_out, lane);
@@ -951,29 +978,18 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 		s3.ev_flags = 0;
 		carrier_load(cr, s3, a, T, lane);
 		for (int step = 0; pp.s3_done < n_out; step++) {
-			int *mb = sh.mbox + 8 * (step & 1);
+			PipeMail &mail = step_mail(sh.mbox, step);
 			const unsigned long long tb = TAPS ? __builtin_amdgcn_s_memtime() : 0ull;
-			int to = pp.s3_done + DM_CHUNK < pp.ss_ready ? pp.s3_done + DM_CHUNK : pp.ss_ready;
+			int to = carrier_advance(pp);         // (carrier_chunk cuts it where more than 64 timing-recovery outputs end)
 			int reset_at = -1;
-			if (to > pp.s3_done) reset_at = carrier_chunk<TAPS>(cr, s3, a, T, io, sh, pp.s3_done, to, nsym, lane); else to = pp.s3_done;
-			if (lane == 0) { mb[2] = reset_at >= 0 ? reset_at + 1 : to; mb[3] = reset_at >= 0; }
-			if (TAPS) busy += __builtin_amdgcn_s_memtime() - tb;
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
-			if (TAPS && lane == 0) mb[7] = (int)(__builtin_amdgcn_s_memtime() - tb);
-#endif
+			if (to > pp.s3_done) reset_at = carrier_chunk<TAPS>(cr, s3, a, T, io, sh, pp.s3_done, to, nsym, lane, states); else to = pp.s3_done;
+			if (lane == 0) { mail.s3_done = reset_at >= 0 ? reset_at + 1 : to; mail.s3_reset = reset_at >= 0; }
+			if (TAPS) { busy += __builtin_amdgcn_s_memtime() - tb; clk.end_since<WAVE_CARRIER>(tb, mail, lane); }
 			__syncthreads();
-			pp.read(mb);
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE == 6
-			{   // the step lasts as long as its longest wave: what the sum of these leaves of P is the barrier and mailbox step itself
-				const int m01 = mb[5] > mb[6] ? mb[5] : mb[6];
-				cr_probe[0] += (unsigned long long)(m01 > mb[7] ? m01 : mb[7]);
-			}
-#endif
+			pp.read(&mail);
+			clk.after_barrier(mail);
 		}
 		carrier_store(cr, a, lane);
-#if defined(HFDL_DM_PROBE) && HFDL_DM_PROBE != 6
-		cr_probe[0] = cr.pa; cr_probe[1] = cr.pb; cr_probe[2] = cr.pc;
-#endif
 		if (lane == 0) {
 			// every field wave 2 owns (the timing-loop scalars it touched through symsync_reset() are wave 1's)
 			S.phi = s3.phi; S.dphi = s3.dphi; S.err = s3.err;
@@ -994,22 +1010,10 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	unsigned long long tP1 = __builtin_amdgcn_s_memtime();
 	if (TAPS) {
 		// phase cycles: what runs ahead of the pipeline, the whole pipelined phase (wall), wave 1 busy, wave 2 busy
-		if (tid == 0) { io.tap_level[io.cap - 4] = (float)(tP0 - tR0); io.tap_level[io.cap - 3] = (float)(tP1 - tP0); }
-		if (wave == 1 && lane == 0) io.tap_level[io.cap - 2] = (float)busy;
-		if (wave == 2 && lane == 0) io.tap_level[io.cap - 1] = (float)busy;
-#ifdef HFDL_DM_PROBE
-		__syncthreads();
-#if HFDL_DM_PROBE == 2 || HFDL_DM_PROBE == 3
-		if (wave == 2 && lane == 0) { io.tap_level[io.cap - 4] = (float)cr_probe[0]; io.tap_level[io.cap - 3] = (float)cr_probe[1]; io.tap_level[io.cap - 2] = (float)cr_probe[2]; }
-#elif HFDL_DM_PROBE == 4 || HFDL_DM_PROBE == 5
-		// busy cycles of wave 0 (= 4: AGC + matched filter) or wave 3 (= 5: resampler + input fetch), counted like waves 1 and 2 from the
-		// step's start to the mailbox write, in the slot of the cycles ahead of the pipeline (profiles/wave_cycles.py)
-		if (wave == (HFDL_DM_PROBE == 4 ? 0 : 3) && lane == 0) io.tap_level[io.cap - 4] = (float)busy;
-#elif HFDL_DM_PROBE == 6
-		// the sum over the steps of the longest of waves 0, 1, 2 in that step (each wave leaves its step's busy cycles in the mailbox)
-		if (wave == 2 && lane == 0) io.tap_level[io.cap - 4] = (float)cr_probe[0];
-#endif
-#endif
+		if (tid == 0) { io.tap_level[phase_slot(io.cap, PHASE_AHEAD)] = (float)(tP0 - tR0); io.tap_level[phase_slot(io.cap, PHASE_PIPELINE)] = (float)(tP1 - tP0); }
+		if (wave == WAVE_TIMING && lane == 0) io.tap_level[phase_slot(io.cap, PHASE_TIMING_BUSY)] = (float)busy;
+		if (wave == WAVE_CARRIER && lane == 0) io.tap_level[phase_slot(io.cap, PHASE_CARRIER_BUSY)] = (float)busy;
+		clk.report(io.tap_level, io.cap, wave, lane, busy, states);
 	}
 	return n_out;
 }

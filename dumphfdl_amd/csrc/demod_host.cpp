@@ -51,8 +51,8 @@ int Demod::fit_batch(int outs, float resamp_rate, int want)
 		const int cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
 		if (batch > 1 && demod_workgroup_lds(cap) > 160 * 1024) continue;
 		// ... and less than one second of signal per launch WHATEVER asked for the batch (cap samples at 5400 sps): a channel then finishes
-		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (hfdl_gpu.cpp
-		// pick_demod_batch states the same bound; an override must not get past it)
+		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (planner.h
+		// plan_batches asks for no more; an override, which it takes as it is, must not get past this)
 		if (batch == 1 || (2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
 	}
 	return batch;

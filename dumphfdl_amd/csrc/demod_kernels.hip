@@ -18,7 +18,7 @@
 #ifdef HFDL_DM_STRICT
 // Hook of the TEST-ONLY strict builds (tests/hostsim/strict_demod_kernels.hip includes this file after defining HFDL_DM_STRICT, the
 // fixed-sequence elementary functions and HFDL_DM_SERIAL_LOOP = the header with the one-lane serial loop it wants run instead of the
-// three-wave pipeline).  The product build defines none of it and this file names nothing under tests/.
+// four-wave pipeline).  The product build defines none of it and this file names nothing under tests/.
 #include HFDL_DM_SERIAL_LOOP
 #endif
 #include "demod_tables.h"
@@ -63,9 +63,9 @@ __device__ unsigned hfdl_clk_probe_n;
 #define HFDL_CLK_PROBE_END(tag)
 #endif
 
-// __launch_bounds__(256, 5): at most 96 VGPRs per wave.  The demodulator workgroups (four
-// waves each, one per SIMD of a CU; 37 KiB of LDS whatever the launch's length: demod_lds.h) are co-resident with the fold kernel's workgroups (stream A), and the two are budgeted against each
-// other: the fold's tiling leaves a SIMD at least these registers of its 512 (one 372 / 420-register wave per SIMD since round 5; four waves
+// __launch_bounds__(256, 5): at most 96 VGPRs per wave.  The demodulator workgroups (four waves each -- resampler, AGC + matched
+// filter, timing recovery, carrier -- one per SIMD of a CU; 37 KiB of LDS whatever the launch's length: the per-sample arrays are rings,
+// demod_lds.h) are co-resident with the fold kernel's workgroups (stream A), and the two are budgeted against each other: the fold's tiling leaves a SIMD at least these registers of its 512 (one 372 / 420-register wave per SIMD since round 5; four waves
 // of 104 in round 1) -- a fold tiling that does not (two waves of 256) makes the two kernels take turns and costs the pipeline 10 %
 // (fold_kernels.hip, profiles/r05/k4_tilings_in_pipeline.txt).  Staying inside the budget also keeps the loops free of scratch spills:
 // scratch is memory, and beside a kernel that reads HBM at 4.6 TB/s every spill reload is a multi-microsecond stall.
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	if (tid < D_EQ) l_eq[tid] = T.c.eq_h0[tid];
 	if (tid < 8) { l_m1[tid] = T.c.m1_hi[tid]; l_m1[8 + tid] = T.c.m1_lo[tid]; }
 	if (tid < 128) l_corr[tid] = T.c.corr_tab[tid];
-	if (tid < 16) ((int *)(lds + L.mbox))[tid] = 0;
+	if (tid < (int)(2 * sizeof(PipeMail) / sizeof(int))) ((int *)(lds + L.mbox))[tid] = 0;
 	__syncthreads();
 	if (tid < DM_MAX_BLOCKS) {           // samples up to and including block tid
 		int sum = 0;
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	sh.cum = (uint16_t *)(lds + L.cum);
 	sh.sstab = l_sstab;
 	sh.S = S;
-	sh.mbox = (int *)(lds + L.mbox);
+	sh.mbox = (PipeMail *)(lds + L.mbox);
 	sh.sink = (float *)(lds + L.sink);
 	sh.stage = (cf *)(lds + L.stage);
 #ifdef HFDL_DM_STRICT
@@ -286,9 +286,6 @@ __device__ __forceinline__ void viterbi27_wave(const uint8_t *vin, int nbits, ui
 		c.odd[r] = (lane >> (5 - r)) & 1;
 	}
 	uint32_t metric = lane == 0 ? 0u : 63u;           // init_viterbi27(vp, 0)
-#ifdef HFDL_VIT_DEBUG
-	const unsigned long long dbg0 = __builtin_amdgcn_s_memtime();
-#endif
 	// 60 trellis steps per trip: every lane fetches the soft pair of one step, the serial loop takes them with v_readlane
 	for (int base = 0; base < nbits; base += 60) {
 		const int tt = base + lane;
@@ -305,9 +302,6 @@ __device__ __forceinline__ void viterbi27_wave(const uint8_t *vin, int nbits, ui
 		}
 		if (lane < lim) decw[base + lane] = ((uint64_t)whi << 32) | wlo;
 	}
-#ifdef HFDL_VIT_DEBUG
-	const unsigned long long dbg1 = __builtin_amdgcn_s_memtime();
-#endif
 	__syncthreads();
 	// chainback with the "d += 6" offset: bit idx comes from the word of step idx+6 (words past the end read as 0).  The
 	// decision of state s at step t sits in bit rotr6(s, (t+1) mod 6); that rotated state register `pos` changes in ONE bit per
@@ -343,12 +337,48 @@ __device__ __forceinline__ void viterbi27_wave(const uint8_t *vin, int nbits, ui
 			if (o < noct) out[o] = (uint8_t)v;
 		}
 	}
-#ifdef HFDL_VIT_DEBUG
-	if (lane == 0 && blockIdx.x == 0) printf("viterbi nbits %d forward %llu chainback %llu cycles\n", nbits, dbg1 - dbg0, (unsigned long long)__builtin_amdgcn_s_memtime() - dbg1);
-#endif
 }
 
 constexpr int K5_TABLE_BYTES = 15360;      // >= 168*30*3 coded bits, 256-aligned
+constexpr int K5_MAX_BITS = 7560;          // Viterbi steps of the longest frame: 168 * 30 * 3 coded bits at rate 1/2
+
+// LDS of a burst decoder's workgroup (one wave, one frame): de-interleaver table, Viterbi input, the decoder's decision words -- the
+// laboratory's soft half alone has none -- and the staged scrambler and constellation constants.  Read by the kernels and their launchers.
+struct BurstLds {
+	size_t table, vin, decw, consts, total;
+	__host__ __device__ constexpr explicit BurstLds(bool viterbi)
+		: table(0), vin(K5_TABLE_BYTES), decw(2 * (size_t)K5_TABLE_BYTES), consts(decw + (viterbi ? viterbi_lds_bytes(K5_MAX_BITS) : 0)), total(consts + DEC_CONST_BYTES) {}
+};
+
+// A frame of the queue as the burst decoder's kernels take it up
+struct BurstFrame {
+	FrameRec fr;
+	ModeParams mp;
+	int nsym, ncoded, cols;        // symbols, coded bits and de-interleaver columns of the mode
+	const cf *sym;                 // the frame's data symbols
+	float mask_flip;
+	uint8_t *l_scr;                // LDS: 128 bytes of scrambler, then the constellation table
+	float *l_psk;
+};
+
+// frame f's parameters, and the scrambler and constellation constants staged at `consts` (DEC_CONST_BYTES of LDS); ends in a barrier
+__device__ __forceinline__ BurstFrame burst_frame(const FrameRec *__restrict__ frames, int f, const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler,
+		unsigned char *consts, int lane)
+{
+	BurstFrame b;
+	b.l_scr = consts;
+	b.l_psk = (float *)(consts + DEC_PSK_OFFSET);
+	b.fr = frames[f];
+	b.mp = mode_params(b.fr.mode);
+	b.nsym = b.mp.segments * 30; b.ncoded = b.nsym * b.mp.arity; b.cols = b.ncoded / 40;
+	b.sym = data_all + ((size_t)b.fr.channel * 2 + b.fr.slot) * MAX_DATA_SYMBOLS;
+	b.mask_flip = b.fr.bitmask_lsb ? -1.0f : 1.0f;
+	b.l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
+	if (lane + 64 < 120) b.l_scr[lane + 64] = scrambler[lane + 64];
+	if (lane < 32) b.l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
+	__syncthreads();
+	return b;
+}
 
 // The soft half of the burst decoder -- descrambler, soft de-map, de-interleaver push and pop, rate-1/4 combine -- for one frame and
 // one wave: fills vin (LDS) with what the Viterbi decoder is fed and returns its length.  l_scr / l_psk: the staged constants;
@@ -409,22 +439,13 @@ __global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__rest
 	if (f == 0 && lane == 0 && stale_count) *stale_count = 0;      // the counter of the launch after next: its last users finished before this launch began
 	if (nframes > frame_cap) nframes = frame_cap;
 	if (f >= nframes) return;
-	uint8_t *table = lds;
-	uint8_t *vin = lds + K5_TABLE_BYTES;
-	uint64_t *decw = (uint64_t *)(lds + 2 * K5_TABLE_BYTES);
-	uint8_t *l_scr = lds + 2 * K5_TABLE_BYTES + viterbi_lds_bytes(7560);             // 128 bytes, then the constellation table
-	float *l_psk = (float *)(l_scr + DEC_PSK_OFFSET);
-
-	const FrameRec fr = frames[f];
-	const ModeParams mp = mode_params(fr.mode);
-	const int nsym = mp.segments * 30, ncoded = nsym * mp.arity, cols = ncoded / 40;
-	const cf *sym = data_all + ((size_t)fr.channel * 2 + fr.slot) * MAX_DATA_SYMBOLS;
-	const float mask_flip = fr.bitmask_lsb ? -1.0f : 1.0f;
-	l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
-	if (lane + 64 < 120) l_scr[lane + 64] = scrambler[lane + 64];
-	if (lane < 32) l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
-	__syncthreads();
-	const int vin_len = burst_soft_wave(fr.mode, nsym, ncoded, cols, sym, mask_flip, l_scr, l_psk, table, vin);
+	constexpr BurstLds L(true);
+	uint8_t *table = lds + L.table, *vin = lds + L.vin;
+	uint64_t *decw = (uint64_t *)(lds + L.decw);
+	const BurstFrame b = burst_frame(frames, f, data_all, scrambler, lds + L.consts, lane);
+	const FrameRec &fr = b.fr;
+	const ModeParams &mp = b.mp;
+	const int vin_len = burst_soft_wave(fr.mode, b.nsym, b.ncoded, b.cols, b.sym, b.mask_flip, b.l_scr, b.l_psk, table, vin);
 	// claim a slot of the PDU ring: counts[1] = PDUs ever produced, counts[3] = PDUs the host has taken (both mod 2^32);
 	// a full ring drops the PDU (counts[2]) without leaving a hole
 	int slot = -1;
@@ -484,20 +505,10 @@ __global__ __launch_bounds__(64) void burst_soft_kernel(const FrameRec *__restri
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 	const int f = blockIdx.x, lane = threadIdx.x;
-	uint8_t *table = lds;
-	uint8_t *vin = lds + K5_TABLE_BYTES;
-	uint8_t *l_scr = lds + 2 * K5_TABLE_BYTES;
-	float *l_psk = (float *)(l_scr + DEC_PSK_OFFSET);
-	const FrameRec fr = frames[f];
-	const ModeParams mp = mode_params(fr.mode);
-	const int nsym = mp.segments * 30, ncoded = nsym * mp.arity, cols = ncoded / 40;
-	const cf *sym = data_all + ((size_t)fr.channel * 2 + fr.slot) * MAX_DATA_SYMBOLS;
-	const float mask_flip = fr.bitmask_lsb ? -1.0f : 1.0f;
-	l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
-	if (lane + 64 < 120) l_scr[lane + 64] = scrambler[lane + 64];
-	if (lane < 32) l_psk[lane] = ((const float *)(scrambler + DEC_PSK_OFFSET))[lane];
-	__syncthreads();
-	const int vin_len = burst_soft_wave(fr.mode, nsym, ncoded, cols, sym, mask_flip, l_scr, l_psk, table, vin);
+	constexpr BurstLds L(false);
+	uint8_t *table = lds + L.table, *vin = lds + L.vin;
+	const BurstFrame b = burst_frame(frames, f, data_all, scrambler, lds + L.consts, lane);
+	const int vin_len = burst_soft_wave(b.fr.mode, b.nsym, b.ncoded, b.cols, b.sym, b.mask_flip, b.l_scr, b.l_psk, table, vin);
 	__syncthreads();
 	uint8_t *dst = vin_out + (size_t)f * HFDL_GPU_LAB_VIN_MAX;
 	for (int j = lane; j < vin_len && j < HFDL_GPU_LAB_VIN_MAX; j += 64) dst[j] = vin[j];
@@ -580,7 +591,7 @@ __global__ void constants_kernel(HfdlConstants *out)
 
 size_t demod_workgroup_lds(int cap) { return DemodLds(cap).total; }
 
-size_t burst_decode_lds() { return 2 * (size_t)K5_TABLE_BYTES + viterbi_lds_bytes(7560) + DEC_CONST_BYTES; }
+size_t burst_decode_lds() { return BurstLds(true).total; }
 
 static int set_big_lds(const void *fn, size_t bytes)
 {
@@ -650,7 +661,7 @@ void launch_psk_slice(int arity, const cf *x, int n, const float *pts, uint32_t 
 #ifdef HFDL_LAB
 void launch_burst_soft(const FrameRec *frames, int nframes, const cf *data, const uint8_t *scrambler, uint8_t *vin, int32_t *vin_lens, hipStream_t st)
 {
-	hipLaunchKernelGGL(burst_soft_kernel, dim3((unsigned)nframes), dim3(64), 2 * K5_TABLE_BYTES + DEC_CONST_BYTES, st, frames, data, scrambler, vin, vin_lens);
+	hipLaunchKernelGGL(burst_soft_kernel, dim3((unsigned)nframes), dim3(64), BurstLds(false).total, st, frames, data, scrambler, vin, vin_lens);
 }
 
 hipError_t demod_clock_probe_ring(ClockProbeRing &r)

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <mutex>
 #include "frontend.h"
+#include "demod_lds.h"
 
 using namespace hfdl;
 
@@ -287,7 +288,7 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 		if (cnt) HIP_TRY(hipMemcpy2D(dst, sizeof(float2), fe->ph_slot(fe->last_set, index) + channel, sizeof(float2) * (size_t)g.nch, sizeof(float2), (size_t)cnt, hipMemcpyDeviceToHost));
 		*n_floats = 2 * (size_t)cnt;
 		return 0; }
-	case HFDL_GPU_TAP_PHASE_CYCLES: src = fe->demod.d_tap_lvl + (size_t)channel * fe->demod.cap + fe->demod.cap - 4; nf = 4; break;
+	case HFDL_GPU_TAP_PHASE_CYCLES: src = fe->demod.d_tap_lvl + (size_t)channel * fe->demod.cap + phase_slot(fe->demod.cap, PHASE_AHEAD); nf = DM_PHASE_SLOTS; break;
 	default:
 		if (int rc = fe->demod.tap(what, channel, &src, &nf)) return rc;
 	}

@@ -215,15 +215,17 @@ inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sampl
 	// cfg2 block.  When blocks arrive faster than they are demodulated (file replay, catching up) consecutive blocks are therefore handed
 	// to ONE launch, which treats them as one longer stretch of samples -- the per-channel state is carried sample by sample, so the
 	// result is that of block-by-block processing.  A caller that waits for its PDUs after every block (live input: poll / sync) still
-	// gets a launch per block: a partial batch is launched by any call that needs the results.  Bounds: the LDS (Demod::init keeps what
-	// fits: 30 B per sample, three cfg3 blocks), and one second of signal -- less than half the shortest frame (2.34 s), so that a channel
-	// finishes at most one frame per launch (frame queue: one entry per channel; two data slots).
+	// gets a launch per block: a partial batch is launched by any call that needs the results.  Bounds (Demod::fit_batch): the kernel's
+	// block table, output counts that fit 16 bits, and one second of signal -- less than half the shortest frame (2.34 s), so that a channel
+	// finishes at most one frame per launch (frame queue: one entry per channel; two data slots).  The LDS is no bound: a workgroup's
+	// per-sample arrays are rings (demod_lds.h).
 	int want = (int)std::floor(1.0 / ((double)input_size / (double)sample_rate));
 	want = std::max(1, std::min(8, want));
-	// Where the fold bounds the block the demodulator workgroups (one per channel, ~one per CU) must stay CO-RESIDENT with the fold's
-	// (34 KiB of LDS per workgroup in the thirty-two-column form) and a forward-FFT tile: three cfg3 blocks per launch take 117 KiB of a
-	// CU's 160 KiB since the timing-recovery outputs go through a ring (round 6; round 5: two blocks, 118 KiB).  One block more and the
-	// kernels take turns (measured in round 5 at 159 KiB: a demodulator launch beside a 4.8 ms fold took 5.5 ms, profiles/r05_experiments.md).
+	// Where the fold bounds the block: three.  The measurement behind it predates the rings -- the demodulator workgroups (one per channel)
+	// must stay CO-RESIDENT with the fold's (34 KiB of LDS per workgroup in the thirty-two-column form) and a forward-FFT tile, and with
+	// whole-launch arrays three cfg3 blocks took 117 KiB of a CU's 160 KiB; one block more and the kernels took turns (round 5, at 159 KiB:
+	// a demodulator launch beside a 4.8 ms fold took 5.5 ms, profiles/r05_experiments.md).  A workgroup takes 37 KiB today whatever the
+	// launch's length (demod_lds.h), so the LDS no longer argues for three; more has not been measured since.
 	if (fold_bound) want = std::min(want, 3);
 	if (ov.demod_batch) want = ov.demod_batch;                              // 1 = a launch per block
 	want = demod_fit(want);

@@ -404,7 +404,7 @@ enum {
 	HFDL_GPU_TAP_AGC_LEVEL = 7,      /* f32[n], agc signal level per 5400-sps sample */
 	HFDL_GPU_TAP_NCO_PHASORS = 9,    /* cf32[n]: the NCO phasors (cos phi_k, sin phi_k) that multiplied the last block's outputs of `channel`
 	                                    (decimating_shift_addition_cc's recurrence, src/libcsdr_gpl.c:48-66; bit-exact vs the reference) */
-	HFDL_GPU_TAP_PHASE_CYCLES = 8    /* f32[4]: shader cycles of the last demod launch: resampler phase, the whole three-wave pipelined phase (wall),
+	HFDL_GPU_TAP_PHASE_CYCLES = 8    /* f32[4]: shader cycles of the last demod launch: resampler phase, the whole four-wave pipelined phase (wall),
 	                                    busy cycles of the timing-recovery wave, busy cycles of the carrier / equaliser / framer wave */
 };
 /* Stage taps 4..8 make the demodulator write its intermediate samples to HBM every launch; on by default (tests), a

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Viterbi cycle probe (debug build with -DHFDL_VIT_DEBUG prints forward / chainback cycles of workgroup 0)."""
+"""The Viterbi stage alone: batches of 8, 2048 and 2048 frames of 7560 bits (time it with the laboratory build's clock-probe ring or a profiler)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
