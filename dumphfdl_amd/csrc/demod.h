@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <memory>
+#include <vector>
 #include "../../include/hfdl_gpu.h"
 #include "hip_handles.h"
 #include "kernels.h"
@@ -41,6 +42,9 @@ struct Demod {
 	DevArray<int> d_counts;                 // [1] pdus produced, [2] pdus dropped, [3] pdus taken by the host, [4..7] frames queued, one counter per block mod 4
 	DevArray<hfdl_gpu_pdu> d_pdus;
 	DevArray<int32_t> d_freqs;
+	DevArray<ChanState> d_state_image;      // one ChanState as chan_state_init() makes it: allocated by the first retune, never otherwise
+	PinnedBuf<ChanState> h_state_image;     // ... and where it is uploaded from (no pageable copy, no wait)
+	std::vector<int> retuned;               // channels whose state reset is queued and not known to have run: stats_all() reports them fresh
 	DevArray<float2> d_tap_rs, d_tap_mf, d_tap_sym;      // stage taps
 	DevArray<float> d_tap_lvl;
 	DevArray<int> d_tap_counts;             // [nch][2]
@@ -48,6 +52,7 @@ struct Demod {
 	PinnedBuf<hfdl_gpu_pdu> h_pdu_bounce;   // [bounce_cap]
 	PinnedBuf<ChanScalars> h_stats_bounce;  // [nch]
 	Event ev_dec[2];                        // decoder of an even / odd launch done: its frame queue and counter may be reused (made by the first such decoder)
+	Event ev_retuned;                       // rides on the newest retune_demod_kernel (made by the first retune)
 
 	Demod();
 	~Demod();
@@ -63,6 +68,13 @@ struct Demod {
 	int collect(hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);                    // stream idle: everything produced
 	int collect_snapshot(int buf, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);  // up to the end of that buffer's block
 	int take(unsigned produced, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);
+	// Retune of channel c (hfdl_gpu_frontend_retune_channel): prepare_retune() makes the state image (the first call allocates it and
+	// queues its upload on `st_b`; nothing else changes if it fails); enqueue_retune() queues the state reset behind the demodulators
+	// on `st_b` and the new PDU frequency behind the burst decoders on `st_d`.  From then on the channel's statistics are a fresh
+	// channel's: until the reset is known to have run, stats_all() -- which waits for nothing -- reports the image's counters for it,
+	// never the old ones, so a reader never sees a counter rise and then run backwards.
+	int prepare_retune(hipStream_t st_b);
+	void enqueue_retune(int c, int32_t freq, hipStream_t st_b, hipStream_t st_d);
 	int stats_all(hfdl_gpu_channel_stats *out, int n);
 	int tap(int what, int channel, const void **src, size_t *nfloats);
 	int stats(int channel, hfdl_gpu_channel_stats *out);

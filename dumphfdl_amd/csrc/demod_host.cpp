@@ -148,6 +148,30 @@ int Demod::enqueue_decode(int buf, hipStream_t st, hipEvent_t start, hipEvent_t 
 	return 0;
 }
 
+int Demod::prepare_retune(hipStream_t st_b)
+{
+	if (d_state_image.p) return 0;
+	DevArray<ChanState> d;
+	PinnedBuf<ChanState> h;
+	Event ev;
+	CREATE_TRY(d.alloc(1));
+	CREATE_TRY(h.alloc(1));
+	CREATE_TRY(ev.create(EV_NO_TIMING));
+	chan_state_init(*h.p, img->h.eq_h0);
+	HIP_TRY(hipMemcpyAsync(d.p, h.p, sizeof(ChanState), hipMemcpyHostToDevice, st_b));
+	std::swap(d_state_image.p, d.p);
+	std::swap(h_state_image.p, h.p);
+	ev_retuned = std::move(ev);
+	return 0;
+}
+
+void Demod::enqueue_retune(int c, int32_t freq, hipStream_t st_b, hipStream_t st_d)
+{
+	launch_retune_demod(d_states, d_state_image, c, st_b, ev_retuned);
+	launch_retune_freq(d_freqs, c, freq, st_d);
+	retuned.push_back(c);
+}
+
 // copy ring entries [taken, produced) to the host, at most `max`; every entry below `produced` is complete.
 // `produced` may be an OLDER snapshot than `taken` (a draining poll followed by a snapshot poll with no push in between):
 // the difference is taken as signed, so a stale snapshot yields nothing instead of wrapping.
@@ -237,8 +261,14 @@ int Demod::stats_all(hfdl_gpu_channel_stats *out, int n)
 {
 	if (n > nch) return fail(HFDL_GPU_EINVAL, "statistics of %d channels asked for, %d exist", n, nch);
 	ChanScalars *sc = h_stats_bounce.p;
+	// asked BEFORE the copy: if the newest state reset has run, the copy sees every reset
+	if (!retuned.empty() && hipEventQuery(ev_retuned) == hipSuccess) retuned.clear();
+	(void)hipGetLastError();              // "not ready" is an answer
 	HIP_TRY(hipMemcpy2DAsync(sc, sizeof(ChanScalars), &d_states[0].s, sizeof(ChanState), sizeof(ChanScalars), (size_t)n, hipMemcpyDeviceToHost, st_collect));
 	HIP_TRY(hipStreamSynchronize(st_collect));
+	// a channel whose reset is still queued is a fresh channel already: the image's scalars, the stream position it has reached
+	for (int c : retuned)
+		if (c < n) { const uint64_t at = sc[c].sample_cnt; sc[c] = h_state_image.p->s; sc[c].sample_cnt = at; }
 	for (int i = 0; i < n; i++) fill_stats(sc[i], out + i);
 	return 0;
 }

@@ -587,6 +587,26 @@ __global__ void constants_kernel(HfdlConstants *out)
 	}
 }
 
+// Retune (hfdl_gpu_frontend_retune_channel), the demodulator's side: the state of channel c becomes the image chan_state_init() made at
+// create, word by word over the lanes, except two fields that are carried on: sample_cnt (a PDU's sample index stays the stream's
+// position) and data_slot (the burst decoder of the last frame before the boundary may still be reading the other slot).
+__global__ __launch_bounds__(256) void retune_demod_kernel(ChanState *__restrict__ states, const ChanState *__restrict__ image, int c)
+{
+	static_assert(sizeof(ChanState) % 4 == 0 && offsetof(ChanState, s.sample_cnt) % 4 == 0 && offsetof(ChanState, s.data_slot) % 4 == 0, "copied as 32-bit words");
+	static_assert(sizeof(ChanScalars::sample_cnt) == 8 && sizeof(ChanScalars::data_slot) == 4, "the carried fields are two words and one word");
+	constexpr unsigned words = sizeof(ChanState) / 4, cnt0 = offsetof(ChanState, s.sample_cnt) / 4, slot = offsetof(ChanState, s.data_slot) / 4;
+	uint32_t *dst = (uint32_t *)(states + c);
+	const uint32_t *src = (const uint32_t *)image;
+	for (unsigned w = threadIdx.x; w < words; w += blockDim.x)
+		if (w != cnt0 && w != cnt0 + 1 && w != slot) dst[w] = src[w];
+}
+
+// ... and the burst decoder's: the frequency its PDUs of channel c are labelled with
+__global__ void retune_freq_kernel(int32_t *freqs, int c, int32_t freq)
+{
+	if (blockIdx.x == 0 && threadIdx.x == 0) freqs[c] = freq;
+}
+
 // ---------------------------------------------------------------- launchers (demod_launch.h)
 
 size_t demod_workgroup_lds(int cap) { return DemodLds(cap).total; }
@@ -621,6 +641,16 @@ void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes
 {
 	hipExtLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)frame_cap), dim3(64), (unsigned)burst_decode_lds(), st, start, stop, 0, frames, counts,
 			nframes, stale_count, frame_cap, data, scrambler, freqs, pdus, pdu_cap);
+}
+
+void launch_retune_demod(ChanState *states, const ChanState *image, int c, hipStream_t st, hipEvent_t done)
+{
+	hipExtLaunchKernelGGL(retune_demod_kernel, dim3(1), dim3(256), 0, st, nullptr, done, 0, states, image, c);
+}
+
+void launch_retune_freq(int32_t *freqs, int c, int32_t freq, hipStream_t st)
+{
+	hipLaunchKernelGGL(retune_freq_kernel, dim3(1), dim3(64), 0, st, freqs, c, freq);
 }
 
 // ---- the stage kernels

@@ -40,6 +40,10 @@ void launch_demod(bool taps, const DevTables &T, const DemodBuffers &B, const cf
 // K5: one wavefront per entry of the frame queue (`frame_cap` of them)
 void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data,
 		const uint8_t *scrambler, const int32_t *freqs, hfdl_gpu_pdu *pdus, int pdu_cap, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+// retune: states[c] = *image except sample_cnt and data_slot (the demodulators' stream; `done`, optional, rides on the dispatch);
+// freqs[c] = freq (the burst decoders' stream)
+void launch_retune_demod(ChanState *states, const ChanState *image, int c, hipStream_t st, hipEvent_t done);
+void launch_retune_freq(int32_t *freqs, int c, int32_t freq, hipStream_t st);
 int read_device_constants(void *constants);  // sizeof(HfdlConstants): hfdl_constants() as the device evaluates it
 
 // The stage kernels: one wavefront per frame (Viterbi), one lane per PDU (triage, LPDU walk), up to 256 wavefronts sharing the symbols

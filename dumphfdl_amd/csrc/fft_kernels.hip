@@ -9,6 +9,7 @@
 // the overlap history and the fftshift are index remaps on the first load / last store, never a pass.
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "retune_launch.h"
 #include "fft_core.h"
 #include "fft_regs.h"
 
@@ -348,6 +349,22 @@ static void launch_rpass1(int fmt, dim3 grid, hipStream_t st, hipEvent_t start, 
 	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CS16, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
 	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CU8, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
 	else hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CF32, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
+}
+
+// Retune (hfdl_gpu_frontend_retune_channel): channel c becomes a freshly created channel as far as the riders' arrays go -- its
+// channelizer constants are the new frequency's, its carried NCO state and segment hand-over what create left there (zero).  One lane,
+// three plain stores; stream order places it behind every rider and inverse FFT that read the old values.
+__global__ void retune_channelizer_kernel(ChanConst *cc, NcoState *chain, float2 *cont, int c, ChanConst k)
+{
+	if (blockIdx.x != 0 || threadIdx.x != 0) return;
+	cc[c] = k;
+	chain[c] = NcoState{ 0, 0.f, 0, 0 };
+	cont[c] = make_float2(0.f, 0.f);
+}
+
+void launch_retune_channelizer(ChanConst *cc, NcoState *chain, float2 *cont, int c, const ChanConst &k, hipStream_t st, hipEvent_t done)
+{
+	hipExtLaunchKernelGGL(retune_channelizer_kernel, dim3(1), dim3(64), 0, st, nullptr, done, 0, cc, chain, cont, c, k);
 }
 
 // the register-resident passes take radices 64 / 128 / 256 (N = 2^18 .. 2^24); smaller transforms keep the LDS radix-4 passes

@@ -4,6 +4,7 @@
 // and read-back; the kernels' launchers are beside the kernels), lab.cpp the laboratory build's switches, probes and stage.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <complex>
 #include <deque>
 #include <memory>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "hip_handles.h"
 #include "kernels.h"
 #include "planner.h"
+#include "retune_launch.h"
 #include "demod.h"
 #include "spectrum.h"
 #include "export_ring.h"
@@ -18,6 +20,7 @@
 namespace hfdl {
 
 int select_device(int device);        // checks the index and the architecture, hipSetDevice
+int check_channel_span(int32_t sample_rate, int32_t nrx, int c, int32_t freq, int r, int32_t centre);     // channel c on `freq` inside +-fs/2 of the centre of its receiver r
 long env_long(const char *name, long lo, long hi, long otherwise);
 inline int ilog2(int x) { int l = 0; while ((1 << l) < x) l++; return l; }
 inline size_t sample_bytes(int fmt) { return fmt == SFMT_CS16 ? 4 : fmt == SFMT_CU8 ? 2 : 8; }
@@ -160,7 +163,27 @@ struct ChannelExport {
 	hipEvent_t newest = nullptr;        // what the newest launch carried (null: no launch yet)
 };
 
+// Retune (hfdl_gpu_frontend_retune_channel): what the first call allocates and later ones keep.  The new time-domain taps go through one
+// of two page-locked buffers into `pad` (N points, zeroed once: only the first taps_length are ever written), and the tap FFT has a work
+// buffer of its own -- d_work belongs to the chain of forward FFTs, which may be running on another stream.  staged[i] rides on the first
+// pass of the tap FFT behind the copy out of stage[i]: the call's only host wait.  `done` rides on retune_channelizer_kernel.
+struct Retune {
+	DevBuf pad, work;
+	PinnedBuf<float2> stage[2];
+	Event staged[2];
+	DoneEvent done;
+	uint64_t calls = 0;
+	std::vector<float> lp;              // the low-pass prototype every channel's band-pass is made from (planner.h design_bandpass), kept between calls
+	float lp_cut = -1.f;
+};
+
 }  // namespace hfdl
+
+// One channel as create designs it (frontend_create.cpp): the channelizer constants and the taps_length time-domain taps of a channel of
+// receiver `rx` on `freq`.  build_taps() and a retune call the same function, so a retuned channel's are a fresh create's bit for bit.
+// lp / lp_cut: the caller's cache of the low-pass prototype (planner.h design_bandpass); taps == nullptr: the constants alone.  False: the
+// planner refuses the shift.
+bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, hfdl::ChanConst &k, std::complex<float> *taps, std::vector<float> &lp, float &lp_cut);
 
 // Members are destroyed in reverse order of declaration: events first, then memory, then the streams (the destructor has synchronised
 // them).  So: streams, then memory, then events.
@@ -219,6 +242,7 @@ struct hfdl_gpu_frontend {
 	float2 *d_ph = nullptr, *d_ph_cont = nullptr;      // [half_blocks] NCO phasor tables [outs][nch] and the riders' segment hand-over [nch]
 	std::unique_ptr<hfdl::SpectrumMonitor> mon;        // null: off
 	std::unique_ptr<hfdl::ChannelExport> exp;          // null: off
+	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
 
 	// ---- events
 	// demodulator launch j of the half in buffer 0 / 1 done (the decoder may start), the LAST launch of the half at [0]: chan_out is free

@@ -99,6 +99,22 @@ static int build_fold_windows(hfdl_gpu_frontend *fe)
 	return 0;
 }
 
+bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, ChanConst &k, std::complex<float> *taps, std::vector<float> &lp, float &lp_cut)
+{
+	// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency -- from the centre of ITS receiver
+	float shift = (float)(fe->rx_center[(size_t)rx] - (freq + 1440)) / (float)fe->sample_rate;
+	Plan cp;
+	if (!plan_block(cp, fe->tbw, fe->decimation, shift)) return false;
+	k = ChanConst{};
+	k.offsetbin = cp.offsetbin;
+	k.nco_sindelta = cp.sindelta; k.nco_cosdelta = cp.cosdelta; k.nco_rate = cp.rate;
+	k.frequency = freq;
+	if (taps == nullptr) return true;          // the constants alone
+	float half_bw = 0.5f / fe->decimation;
+	design_bandpass(taps, fe->plan.taps_length, (-shift) - half_bw, (-shift) + half_bw, lp, lp_cut);
+	return true;
+}
+
 static int build_taps(hfdl_gpu_frontend *fe)
 {
 	const Plan &pl = fe->plan;
@@ -118,17 +134,7 @@ static int build_taps(hfdl_gpu_frontend *fe)
 		for (;;) {
 			int c = next.fetch_add(1);
 			if (c >= nch) break;
-			// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency -- from the centre of ITS receiver
-			float shift = (float)(fe->rx_center[(size_t)fe->rx_of[(size_t)c]] - (fe->freqs[c] + 1440)) / (float)fe->sample_rate;
-			Plan cp;
-			if (!plan_block(cp, fe->tbw, fe->decimation, shift)) { bad++; continue; }
-			ChanConst k{};
-			k.offsetbin = cp.offsetbin;
-			k.nco_sindelta = cp.sindelta; k.nco_cosdelta = cp.cosdelta; k.nco_rate = cp.rate;
-			k.frequency = fe->freqs[c];
-			fe->cc[c] = k;
-			float half_bw = 0.5f / fe->decimation;
-			design_bandpass(host.data() + (size_t)c * pl.taps_length, pl.taps_length, (-shift) - half_bw, (-shift) + half_bw, lp, lp_cut);
+			if (!design_channel(fe, fe->rx_of[(size_t)c], fe->freqs[c], fe->cc[c], host.data() + (size_t)c * pl.taps_length, lp, lp_cut)) bad++;
 		}
 	};
 	std::vector<std::thread> pool;
@@ -159,6 +165,14 @@ static int build_taps(hfdl_gpu_frontend *fe)
 	return 0;
 }
 
+// span check of src/main.c:214-226, against the channel's own receiver
+int hfdl::check_channel_span(int32_t sample_rate, int32_t nrx, int c, int32_t freq, int r, int32_t centre)
+{
+	if (std::abs((int64_t)centre - freq) < sample_rate / 2) return 0;
+	return nrx == 1 ? fail(HFDL_GPU_EINVAL, "channel %d Hz outside +-fs/2 of centre %d", freq, centre)
+	                : fail(HFDL_GPU_EINVAL, "channel %d (%d Hz) outside +-fs/2 of the centre %d of its receiver %d", c, freq, centre, r);
+}
+
 // Every argument is checked here, before a device is selected (the checks need no GPU)
 static int check_create_args(hfdl_gpu_frontend **out, int32_t sample_rate, int32_t nrx, const int32_t *centerfreqs, const int32_t *freqs,
 		const int32_t *nch_per_rx)
@@ -171,10 +185,7 @@ static int check_create_args(hfdl_gpu_frontend **out, int32_t sample_rate, int32
 	if (sample_rate < 5400) return fail(HFDL_GPU_EINVAL, "sample rate must be >= 5400 (src/main.c:638-641)");
 	for (int r = 0, c = 0; r < nrx; r++)
 		for (int i = 0; i < nch_per_rx[r]; i++, c++)
-			// span check of src/main.c:214-226, against the channel's own receiver
-			if (std::abs((int64_t)centerfreqs[r] - freqs[c]) >= sample_rate / 2)
-				return nrx == 1 ? fail(HFDL_GPU_EINVAL, "channel %d Hz outside +-fs/2 of centre %d", freqs[c], centerfreqs[r])
-				                : fail(HFDL_GPU_EINVAL, "channel %d (%d Hz) outside +-fs/2 of the centre %d of its receiver %d", c, freqs[c], centerfreqs[r], r);
+			if (int rc = check_channel_span(sample_rate, nrx, c, freqs[c], r, centerfreqs[r])) return rc;
 	return 0;
 }
 
@@ -317,6 +328,7 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	CREATE_TRY(fe->alloc(fe->d_nco, (size_t)nch));
 	CREATE_TRY(hipMemsetAsync(fe->d_nco, 0, sizeof(NcoState) * (size_t)nch, fe->stream));
 	CREATE_TRY(fe->alloc(fe->d_ph_cont, (size_t)nch));
+	CREATE_TRY(hipMemsetAsync(fe->d_ph_cont, 0, sizeof(float2) * (size_t)nch, fe->stream));      // (written before it is read; zero so that a retune can put it back)
 	CREATE_TRY(fe->alloc(fe->d_cc, (size_t)nch));
 	fe->mem.emplace_back();
 	if (int rc = upload_twiddles(pl.m, fe->mem.back())) return rc;

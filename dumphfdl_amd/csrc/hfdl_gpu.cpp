@@ -265,6 +265,8 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 	if (plan.wait_set_free && fe->chan[set].pending()) HIP_TRY(hipStreamWaitEvent(st, fe->chan[set].event(), 0));
 	// ... and the first fold after a drain is left alone: behind the inverse FFT of the half just closed, as on stream A
 	if (plan.wait_first_fold) HIP_TRY(hipStreamWaitEvent(st, fe->chan[set ^ 1].event(), 0));
+	// ... and behind the retune that rewrote a channel's constants and carried NCO state on stream A since the forward FFT before
+	if (plan.wait_retune) HIP_TRY(hipStreamWaitEvent(st, fe->retune->done.event(), 0));
 	// The events other streams (and the bench's fold timer) wait for ride on the kernel dispatches themselves
 	// (hipExtLaunchKernelGGL start / stop events): a separate hipEventRecord is one more barrier packet in the queue, ~5 us
 	// of idle machine each (profiles/r01_experiments.md).
@@ -467,6 +469,73 @@ extern "C" int hfdl_gpu_frontend_push_blocks_raw(hfdl_gpu_frontend *fe, const vo
 {
 	if (!fe || !raw) return fail(HFDL_GPU_EINVAL, "null argument");
 	return push_any(fe, raw, nsamples, sample_format, on_device);
+}
+
+// ---------------------------------------------------------------- retune
+
+// From this call on channel `channel` is a freshly created channel on new_freq_hz; blocks pushed before it run on the old frequency.  The
+// half being filled is closed as a sync closes it, without the sync's waits, and each piece of the change is queued behind the last
+// kernel that uses the old value and in front of the first that must see the new one:
+//   A: new time-domain taps -> pad -> forward FFT into the channel's tap slot -> retune_channelizer_kernel (d_cc, d_nco, d_ph_cont).
+//      The closed half's fold is behind every forward FFT queued so far wherever it ran, so stream A is too; the next forward FFT is
+//      behind the kernel by stream order (A) or by the event the kernel carries (beside the fold: planner.h FftOrder::retune)
+//   B: retune_demod_kernel behind the closed half's demodulators;  D: retune_freq_kernel behind its burst decoders
+// Everything is checked, designed and allocated before the first launch: a refusal leaves the front end as it was.
+extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t channel, int32_t new_freq_hz)
+{
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	const int nch = fe->geo.nch;
+	if (channel < 0 || channel >= nch) return fail(HFDL_GPU_EINVAL, "channel %d out of range (%d channels)", channel, nch);
+	if (fe->prune_tol > 0) return fail(HFDL_GPU_EINVAL, "retune refused: HFDL_GPU_FOLD_PRUNE is set, and the pruned fold's row windows depend on the pass bands");
+	const int rx = fe->rx_of[(size_t)channel];
+	if (int rc = check_channel_span(fe->sample_rate, fe->nrx, channel, new_freq_hz, rx, fe->rx_center[(size_t)rx])) return rc;
+	for (int c = 0; c < nch; c++)
+		if (c != channel && fe->rx_of[(size_t)c] == rx && fe->freqs[(size_t)c] == new_freq_hz)
+			return fail(HFDL_GPU_EINVAL, "channel %d of receiver %d already listens on %d Hz", c, rx, new_freq_hz);
+	const size_t ntaps = (size_t)fe->plan.taps_length, n = (size_t)fe->plan.n;
+	ChanConst k;
+	{
+		std::vector<float> none;
+		float cut = -1.f;
+		if (!design_channel(fe, rx, new_freq_hz, k, nullptr, none, cut)) return fail(HFDL_GPU_EINVAL, "fastddc planning failed for %d channel(s)", 1);
+	}
+	HIP_TRY(hipSetDevice(fe->device));
+	if (!fe->retune) {
+		auto r = std::make_unique<Retune>();
+		CREATE_TRY(r->pad.alloc(sizeof(float2) * n));
+		CREATE_TRY(r->work.alloc(sizeof(float2) * n));
+		for (int i = 0; i < 2; i++) {
+			CREATE_TRY(r->stage[i].alloc(ntaps));
+			CREATE_TRY(r->staged[i].create(EV_NO_TIMING));
+		}
+		CREATE_TRY(r->done.own.create(EV_NO_TIMING));
+		if (int rc = fe->demod.prepare_retune(fe->stream_b)) return rc;
+		HIP_TRY(hipMemsetAsync(r->pad.p, 0, sizeof(float2) * n, fe->stream));
+		fe->retune = std::move(r);
+	}
+	Retune &r = *fe->retune;
+	const int sb = (int)(r.calls & 1);
+	if (r.calls >= 2) HIP_TRY(hipEventSynchronize(r.staged[sb]));       // the tap FFT of two calls ago has read what was copied out of this buffer
+	// the time-domain taps, designed on the host (exact reference arithmetic) straight into the page-locked buffer the copy reads
+	static_assert(sizeof(std::complex<float>) == sizeof(float2), "taps are copied as cf32");
+	design_channel(fe, rx, new_freq_hz, k, (std::complex<float> *)r.stage[sb].p, r.lp, r.lp_cut);
+	// the boundary: what was pushed so far is folded and demodulated on the old frequency (a held-back half first, as a device push does)
+	if (int rc = flush_pending_demod(fe, false)) return rc;
+	if (int rc = close_half(fe, true)) return rc;
+	HIP_TRY(hipMemcpyAsync(r.pad.p, r.stage[sb].p, sizeof(float2) * ntaps, hipMemcpyHostToDevice, fe->stream));
+	const int slot = fe->slot_of(channel);
+	FftOutLayout lay = fe->tap_layout;
+	lay.chan = slot;
+	float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
+	launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), dst, true, fe->stream, lay, nullptr, NcoJob(), r.staged[sb]);
+	launch_retune_channelizer(fe->d_cc, fe->d_nco, fe->d_ph_cont, channel, k, fe->stream, r.done.signal());
+	fe->demod.enqueue_retune(channel, new_freq_hz, fe->stream_b, fe->stream_d);
+	HIP_TRY(hipGetLastError());
+	fe->order.retune();
+	fe->freqs[(size_t)channel] = new_freq_hz;
+	fe->cc[(size_t)channel] = k;
+	r.calls++;
+	return 0;
 }
 
 // ---------------------------------------------------------------- sync and poll

@@ -281,12 +281,17 @@ inline int fft_side(FftRule rule, bool on_device) { return rule == FFT_RULE_INPU
 //     the next half is then expected in front of the fold as well -- and go behind the LAST serial FFT of the next half, which carries the
 //     event they wait for (hold_after).  A BESIDE FFT carries no such event: it launches what is held back at once, in front of
 //     itself (flush_before), so that nothing ever waits for an event no launch will signal
-struct FftPushPlan { int side; bool wait_switch, wait_set_free, wait_first_fold, flush_before, hold_after; };
+//   - a retune (hfdl_gpu_frontend_retune_channel) closes the half being filled, which puts stream A behind every forward FFT queued so
+//     far wherever it ran (the fold of a half follows its FFTs), and then rewrites one channel's constants and carried NCO state on
+//     stream A: the first FFT after it, BESIDE, waits for the event that kernel carries (wait_retune); SERIAL, stream A orders it, and
+//     a later BESIDE one then finds it behind wait_switch
+struct FftPushPlan { int side; bool wait_switch, wait_set_free, wait_first_fold, flush_before, hold_after, wait_retune; };
 struct HalfClosePlan { bool wait_input, hold_back; };
 struct FftOrder {
 	int prev_side = -1;             // side of the newest forward FFT; -1: none since everything queued was waited for
 	bool half_beside = false;       // an FFT of the half being filled ran BESIDE
 	int halves = 0;                 // halves closed since everything queued was waited for
+	bool retuned = false;           // a retune's kernel is queued on stream A and no forward FFT has been ordered behind it yet
 	// fill: blocks already in the half being filled, target: blocks that close it, held_back: the half before waits for its demodulators
 	FftPushPlan push(int side, int fill, int target, bool held_back)
 	{
@@ -297,6 +302,8 @@ struct FftOrder {
 		p.wait_first_fold = side == FFT_BESIDE && fill == 0 && halves == 1;
 		p.flush_before = side == FFT_BESIDE && held_back;
 		p.hold_after = side == FFT_SERIAL && held_back && fill + 1 == target;
+		p.wait_retune = side == FFT_BESIDE && retuned;
+		retuned = false;
 		prev_side = side;
 		half_beside = half_beside || side == FFT_BESIDE;
 		return p;
@@ -309,7 +316,8 @@ struct FftOrder {
 		halves++;
 		return c;
 	}
-	void drained() { prev_side = -1; halves = 0; }      // every stream has been synchronised
+	void retune() { retuned = true; }                   // the half being filled has been closed (close()) and the retune's kernel queued
+	void drained() { prev_side = -1; halves = 0; retuned = false; }      // every stream has been synchronised
 };
 
 // ---------------------------------------------------------------- the CU partition of the fold-bound geometries

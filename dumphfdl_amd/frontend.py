@@ -80,6 +80,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_spectrum_enable", "hfdl_gpu_frontend_spectrum_read",
     "hfdl_gpu_frontend_spectrum_history", "hfdl_gpu_frontend_spectrum_row_close", "hfdl_gpu_frontend_spectrum_rows",
     "hfdl_gpu_frontend_export_enable", "hfdl_gpu_frontend_export_read",
+    "hfdl_gpu_frontend_retune_channel",
 ]
 
 
@@ -204,6 +205,7 @@ def _bind(L):
     L.hfdl_gpu_frontend_export_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_int32]
     L.hfdl_gpu_frontend_export_read.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int]
+    L.hfdl_gpu_frontend_retune_channel.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     return L
 
 
@@ -537,6 +539,13 @@ class Frontend:
                                                      C.byref(n), C.byref(nxt), int(wait)), self._L)
         m = n.value
         return samples[:m], counts[:m], power[:m], clipped[:m], [int(b) for b in info[:m]], nxt.value
+
+    def retune(self, channel, freq_hz):
+        """Move `channel` (a global index) to freq_hz (include/hfdl_gpu.h hfdl_gpu_frontend_retune_channel): blocks pushed before the
+        call run on the old frequency, blocks pushed after it on the new one, where the channel starts as a freshly created one.  Nothing
+        is drained.  A refusal raises GpuError with the library's text and changes nothing."""
+        _check(self._L.hfdl_gpu_frontend_retune_channel(self._h, int(channel), int(freq_hz)), self._L)
+        self.freqs[channel] = int(freq_hz)
 
     def close(self):
         if self._h:

@@ -13,6 +13,11 @@
 #include "hfdl_host.h"
 #include "hfdl_gpu.h"
 #include "host_internal.h"
+#include "retune_requests.h"
+
+/* A GPU library without the entry point (the CPU stand-in of the tests, an older build) leaves the symbol null: it cannot retune, and a
+ * request is refused. */
+#pragma weak hfdl_gpu_frontend_retune_channel
 
 /* The two optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
  * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
@@ -180,6 +185,49 @@ size_t hfdl_channels_on_connection(struct block_connection *conn, struct hfdl_ch
 	return n;
 }
 
+/* ---- retune requests (retune_requests.h): hfdl_frontend_retune() from any thread, hfdl_frontend_schedule_retune() on the sample clock;
+ * the front-end thread applies them between two pushes.  One mutex guards both lists AND the application of a request, so a request
+ * is always checked against the frequencies the channels will listen on once everything accepted before it has been applied.  Lock
+ * order: g_retune_lock, then g_slot_lock. ---- */
+
+static pthread_mutex_t g_retune_lock = PTHREAD_MUTEX_INITIALIZER;
+static struct retune_list g_retune;
+static struct { double seconds; struct retune_request r; } g_retune_at[HFDL_RETUNE_LIST_MAX];
+static int32_t g_retune_at_cnt;
+
+/* g_retune_lock held */
+static int retune_add_locked(int32_t old_freq, int32_t new_freq)
+{
+	int32_t freqs[MAX_SLOTS];
+	pthread_mutex_lock(&g_slot_lock);
+	const int32_t n = (int32_t)g_slot_cnt;
+	for (int32_t i = 0; i < n; i++) freqs[i] = g_slots[i]->frequency;
+	pthread_mutex_unlock(&g_slot_lock);
+	return retune_list_add(&g_retune, freqs, n, old_freq, new_freq);
+}
+
+int hfdl_frontend_retune(int32_t old_freq, int32_t new_freq)
+{
+	pthread_mutex_lock(&g_retune_lock);
+	const int rc = retune_add_locked(old_freq, new_freq);
+	pthread_mutex_unlock(&g_retune_lock);
+	return rc;
+}
+
+int hfdl_frontend_schedule_retune(double seconds, int32_t old_freq, int32_t new_freq)
+{
+	int rc = -1;
+	pthread_mutex_lock(&g_retune_lock);
+	if (seconds >= 0 && isfinite(seconds) && g_retune_at_cnt < HFDL_RETUNE_LIST_MAX) {
+		g_retune_at[g_retune_at_cnt].seconds = seconds;
+		g_retune_at[g_retune_at_cnt].r = (struct retune_request){ old_freq, new_freq };
+		g_retune_at_cnt++;
+		rc = 0;
+	}
+	pthread_mutex_unlock(&g_retune_lock);
+	return rc;
+}
+
 /* ---- StatsD-style observability (src/hfdl.c:818-840, 1082-1105): fed from the device-resident channel state ---- */
 
 __attribute__((weak)) void statsd_counter_per_channel_increment(int32_t freq, char *counter) { (void)freq; (void)counter; }
@@ -207,7 +255,12 @@ static void publish_counters(hfdl_gpu_frontend *fe, hfdl_gpu_channel_stats *now,
 		g_obs.cnt = nch;
 	}
 	for (int32_t i = 0; i < nch; i++) {
+		/* A channel's counters only grow, except that a retune starts them over (the library reports a retuned channel's as a fresh
+		 * channel's from the call on, and apply_retune() zeroes the snapshot with them).  Should one be found BELOW the snapshot all
+		 * the same, the channel has started over since: counted from zero, never "up" through 2^32. */
+		static const hfdl_gpu_channel_stats fresh;
 		const hfdl_gpu_channel_stats *o = &g_obs.last[i];
+		if (now[i].a2_found < o->a2_found || now[i].m1_found < o->m1_found || now[i].m1_not_found < o->m1_not_found || now[i].frames < o->frames) o = &fresh;
 		for (uint32_t k = o->a2_found; k != now[i].a2_found; k++) statsd_counter_per_channel_increment(now[i].freq, "demod.preamble.A2_found");
 		for (uint32_t k = o->m1_found; k != now[i].m1_found; k++) statsd_counter_per_channel_increment(now[i].freq, "demod.preamble.M1_found");
 		for (uint32_t k = o->m1_not_found; k != now[i].m1_not_found; k++) statsd_counter_per_channel_increment(now[i].freq, "demod.preamble.errors.M1_not_found");
@@ -336,6 +389,7 @@ struct iq_export {
 	int32_t nsel, row;               /* selected channels; samples a row holds (geometry.max_outputs_per_block) */
 	size_t es;                       /* bytes per sample */
 	FILE **files;                    /* NULL = off */
+	int32_t *sel;                    /* [nsel] the channel of each file */
 	char *samples;
 	int32_t *counts;
 	hfdl_gpu_export_block info[IQX_CHUNK];
@@ -351,6 +405,7 @@ struct fe_thread {
 	bool ok;                         /* false once the run has failed: what arrives is dropped until the producer shuts down */
 	size_t nch;
 	int32_t *freqs;
+	struct hfdl_channel_slot **slots; /* [nch] the registered channels, in the front end's channel order */
 	double fs, centerfreq;           /* of the receiver */
 	size_t need;                     /* samples of a block */
 	int gfmt;                        /* HFDL_GPU_SFMT_* of the ring's samples */
@@ -573,6 +628,7 @@ static void iq_export_close(struct iq_export *x)
 	for (int32_t s = 0; x->files != NULL && s < x->nsel; s++)
 		if (x->files[s] != NULL) fclose(x->files[s]);
 	free(x->files);
+	free(x->sel);
 	free(x->samples);
 	free(x->counts);
 	memset(x, 0, sizeof(*x));
@@ -610,9 +666,79 @@ static int iq_export_open(hfdl_gpu_frontend *fe, const struct gpu_fft_block *fb,
 		while ((rc = hfdl_gpu_frontend_export_enable(fe, sel, nsel, set->format, set->scale, ring)) == HFDL_GPU_ERANGE && ring > 2) ring /= 2;
 		if (rc != 0) fprintf(stderr, "iq export: %s\n", hfdl_gpu_last_error());
 	}
-	free(sel);
+	x->sel = sel;
 	if (rc != 0) iq_export_close(x);
 	return rc == 0 ? 0 : -1;
+}
+
+/* One accepted request.  The GPU call closes the half being filled and drains nothing: blocks pushed so far keep the old frequency in
+ * their PDUs however late they are polled, so nothing is collected here.  What the host keeps by frequency follows: the PDU hand-off
+ * takes the frequency from the PDU itself; the slot (and with it t->freqs, the StatsD names -- publish_counters() reads the frequency
+ * from the device library's statistics) changes here.  The counters: what the device has counted up to the call is published first,
+ * under the old frequency; from the call on the library reports the channel's counters as a fresh channel's (zero, then what the new
+ * frequency counts -- never the old values, although the device's own reset runs later, behind the demodulators in flight), so the
+ * thread's snapshot is zeroed with them and publish_counters() never sees one run backwards.  (Events of the blocks still in flight
+ * at the call are in no count: the reset wipes them.)  An exported channel's blocks from before the boundary go to
+ * the old file (they are waited for: the only wait, and only for an exported channel), then a new <freq> file starts.
+ * g_retune_lock: held.  Ring mutex: not held. */
+static void apply_retune(struct fe_thread *t, const struct retune_request *r)
+{
+	size_t c = 0;
+	while (c < t->nch && t->freqs[c] != r->old_freq) c++;
+	const char *why = NULL;
+	if (c == t->nch) why = "no channel of this front end listens there";
+	else if (hfdl_gpu_frontend_retune_channel == NULL) why = "this GPU library cannot retune";
+	else {
+		publish_counters(t->fe, t->stats, (int32_t)t->nch);
+		if (hfdl_gpu_frontend_retune_channel(t->fe, (int32_t)c, r->new_freq) != 0) why = hfdl_gpu_last_error();
+	}
+	if (why != NULL) {
+		fprintf(stderr, "retune %d -> %d Hz refused: %s\n", r->old_freq, r->new_freq, why);
+		return;
+	}
+	t->freqs[c] = r->new_freq;
+	pthread_mutex_lock(&g_slot_lock);
+	t->slots[c]->frequency = r->new_freq;
+	pthread_mutex_unlock(&g_slot_lock);
+	pthread_mutex_lock(&g_obs.lock);
+	if (g_obs.last != NULL && (size_t)g_obs.cnt == t->nch) memset(&g_obs.last[c], 0, sizeof(g_obs.last[c]));
+	pthread_mutex_unlock(&g_obs.lock);
+	struct iq_export *x = &t->iqx;
+	for (int32_t s = 0; x->files != NULL && s < x->nsel; s++) {
+		if (x->sel[s] != (int32_t)c) continue;
+		write_iq_export(t->fe, x, 1);
+		const struct iq_export_settings *set = &t->fb->iqx;
+		const size_t cap = strlen(set->dir) + 32;
+		char *path = hfdl_xcalloc(cap, 1);
+		snprintf(path, cap, "%s/%d.%s", set->dir, r->new_freq, set->format == HFDL_GPU_EXPORT_CS16 ? "cs16" : "cf32");
+		FILE *f = fopen(path, "wb");
+		if (f == NULL) fprintf(stderr, "iq export: cannot open %s; the channel's samples stay in the old file\n", path);
+		else { fclose(x->files[s]); x->files[s] = f; }
+		free(path);
+	}
+	t->rs.retunes++;
+}
+
+/* Between two pushes: the scheduled requests whose time has come -- the next block's first sample lies at or after it -- join the list
+ * as a call of hfdl_frontend_retune() at this moment would, then the list is applied, oldest first.  A request that fails is named
+ * once on stderr and the stream goes on.
+ * Ring mutex: not held. */
+static void retune_step(struct fe_thread *t)
+{
+	pthread_mutex_lock(&g_retune_lock);
+	const double now = (double)t->rs.blocks * (double)t->need / t->fs;
+	int32_t kept = 0;
+	for (int32_t i = 0; i < g_retune_at_cnt; i++) {
+		if (g_retune_at[i].seconds > now) { g_retune_at[kept++] = g_retune_at[i]; continue; }
+		const struct retune_request *r = &g_retune_at[i].r;
+		if (retune_add_locked(r->old_freq, r->new_freq) != 0)
+			fprintf(stderr, "retune %d -> %d Hz refused: no channel listens on the old frequency, or one already listens on the new\n", r->old_freq, r->new_freq);
+	}
+	g_retune_at_cnt = kept;
+	struct retune_request todo[HFDL_RETUNE_LIST_MAX];
+	const int32_t n = retune_list_take(&g_retune, todo);
+	for (int32_t i = 0; i < n; i++) apply_retune(t, &todo[i]);
+	pthread_mutex_unlock(&g_retune_lock);
 }
 
 /* Ring mutex: held. */
@@ -751,7 +877,8 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 	struct hfdl_channel_slot *slots[MAX_SLOTS];
 	t->nch = hfdl_channels_on_connection(down, slots, MAX_SLOTS);
 	t->freqs = hfdl_xcalloc(t->nch ? t->nch : 1, sizeof(int32_t));
-	for (size_t i = 0; i < t->nch; i++) t->freqs[i] = slots[i]->frequency;
+	t->slots = hfdl_xcalloc(t->nch ? t->nch : 1, sizeof(*t->slots));
+	for (size_t i = 0; i < t->nch; i++) { t->freqs[i] = slots[i]->frequency; t->slots[i] = slots[i]; }
 	t->ok = true;
 	if (t->nch == 0) {
 		fail(t, "no channels connected");
@@ -799,6 +926,11 @@ static void frontend_teardown(struct fe_thread *t)
 		spectrum_csv_close(t);
 		if (t->iqx.files != NULL) write_iq_export(t->fe, &t->iqx, 1);
 		publish_counters(t->fe, t->stats, (int32_t)t->nch);
+		/* requests that never came due, or came in after the last push, are not the next front end's */
+		pthread_mutex_lock(&g_retune_lock);
+		g_retune.n = 0;
+		g_retune_at_cnt = 0;
+		pthread_mutex_unlock(&g_retune_lock);
 		t->rs.samples = t->rs.blocks * (uint64_t)t->need;
 		t->rs.seconds = t->rs.blocks ? t_last - t->t_first : 0.0;
 		t->rs.bytes_per_sample = (int32_t)hfdl_ring_elem_size(t->ring->buf);
@@ -816,6 +948,7 @@ static void frontend_teardown(struct fe_thread *t)
 	free(t->pdus);
 	free(t->stats);
 	free(t->freqs);
+	free(t->slots);
 	t->block->running = false;
 }
 
@@ -851,6 +984,7 @@ static void *frontend_thread(void *ctx)
 		const double tw1 = now_s();
 		clock_gettime(CLOCK_REALTIME, &t.last_push);
 		if (t.rs.blocks == 0) t.t_first = tw1; else t.rs.wait_input_s += tw1 - tw0;
+		retune_step(&t);
 		if (!push_block(&t, blk, from_bounce)) continue;
 		if (!from_bounce) upload_ahead(&t);
 		if (t.csv.file != NULL) spectrum_csv_step(&t);

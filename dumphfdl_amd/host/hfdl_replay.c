@@ -4,7 +4,8 @@
  *   hfdl_replay --iq-file FILE --sample-rate HZ --sample-format CF32|CS16|CU8 --centerfreq KHZ [--device N]
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
- *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]] FREQ_KHZ...
+ *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
+ *               [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -17,6 +18,10 @@
  * --iq-export-dir DIR    append the baseband I/Q of every channel of the list to DIR/<freq_hz>.cf32 (or .cs16 = int16 of rint(v * X),
  *               X = 32767 by default), one file per channel (hfdl_frontend_set_iq_export, include/hfdl_host.h); DIR must exist.
  *
+ * --retune SECONDS:OLD_KHZ:NEW_KHZ   move the channel on OLD_KHZ to NEW_KHZ before the first block whose first sample lies at or after
+ *               SECONDS of signal (hfdl_frontend_schedule_retune, include/hfdl_host.h); repeatable, at most 64.  A request that is
+ *               refused when its time comes is named once on stderr and the replay goes on.
+ *
  * --statsd-print stands in for dumphfdl's src/statsd.c: the strong statsd_* hooks below print one "STATSD" line per
  * counter total at exit and one per noise-floor gauge as it arrives (metric names as in doc/STATSD_METRICS.md).
  */
@@ -26,6 +31,7 @@
 #include <string.h>
 #include <unistd.h>
 #include "hfdl_host.h"
+#include "retune_requests.h"
 
 static int statsd_print, bench_mode;
 static unsigned long long bench_pdus, bench_octets;
@@ -110,6 +116,14 @@ int main(int argc, char **argv)
 			iqx_format = !strcmp(f, "cs16");
 		}
 		else if (!strcmp(argv[i], "--iq-export-scale") && i + 1 < argc) iqx_scale = (float)atof(argv[++i]);
+		else if (!strcmp(argv[i], "--retune") && i + 1 < argc) {
+			double at;
+			int32_t old_hz, new_hz;
+			if (hfdl_parse_retune(argv[++i], &at, &old_hz, &new_hz) != 0 || hfdl_frontend_schedule_retune(at, old_hz, new_hz) != 0) {
+				fprintf(stderr, "--retune wants SECONDS:OLD_KHZ:NEW_KHZ, at most %d times\n", HFDL_RETUNE_LIST_MAX);
+				return 1;
+			}
+		}
 		else if (!strcmp(argv[i], "--loop") && i + 1 < argc) hfdl_file_input_set_loops(atoi(argv[++i]));
 		else if (!strcmp(argv[i], "--shard") && i + 1 < argc) {
 			if (sscanf(argv[++i], "%d/%d", &shard_rank, &shard_world) != 2 || shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) {
@@ -174,10 +188,10 @@ int main(int argc, char **argv)
 		struct hfdl_run_stats rs;
 		hfdl_frontend_run_stats(&rs);
 		printf("{\"tool\": \"hfdl_replay --bench\", \"value\": %.3f, \"unit\": \"Msamples/s\", \"samples\": %llu, \"blocks\": %llu, \"seconds\": %.6f, "
-				"\"pdus\": %llu, \"pdu_octets\": %llu, \"channels\": %d, \"block_samples\": %d, \"bytes_per_sample_over_pcie\": %d, \"zero_copy_ring\": %s, \"thread_s\": {\"wait_input\": %.4f, \"enqueue\": %.4f, \"collect\": %.4f, \"release\": %.4f, \"grace\": %.4f}, \"pipeline_drains\": %llu, "
+				"\"pdus\": %llu, \"pdu_octets\": %llu, \"channels\": %d, \"block_samples\": %d, \"bytes_per_sample_over_pcie\": %d, \"zero_copy_ring\": %s, \"thread_s\": {\"wait_input\": %.4f, \"enqueue\": %.4f, \"collect\": %.4f, \"release\": %.4f, \"grace\": %.4f}, \"pipeline_drains\": %llu, \"retunes\": %llu, "
 				"\"lpdu_walk_on_device\": {\"mpdus\": %llu, \"lpdus\": %llu, \"good_fcs\": %llu, \"bad_fcs\": %llu}, \"shard\": \"%d/%d\", \"path\": \"file (page cache) -> file input (parallel pread into the page-locked ring) -> GPU front-end block -> pdu_decoder_queue_push\"}\n",
 				rs.seconds > 0 ? (double)rs.samples / rs.seconds / 1e6 : 0.0, (unsigned long long)rs.samples, (unsigned long long)rs.blocks, rs.seconds,
-				bench_pdus, bench_octets, rs.channels, rs.block_samples, rs.bytes_per_sample, rs.zero_copy ? "true" : "false", rs.wait_input_s, rs.push_s, rs.collect_s, rs.release_s, rs.grace_s, (unsigned long long)rs.drains,
+				bench_pdus, bench_octets, rs.channels, rs.block_samples, rs.bytes_per_sample, rs.zero_copy ? "true" : "false", rs.wait_input_s, rs.push_s, rs.collect_s, rs.release_s, rs.grace_s, (unsigned long long)rs.drains, (unsigned long long)rs.retunes,
 				(unsigned long long)rs.mpdus_walked, (unsigned long long)rs.lpdus_processed, (unsigned long long)rs.lpdus_good, (unsigned long long)rs.lpdus_bad_fcs, shard_rank, shard_world);
 		fflush(stdout);
 	}

@@ -1,7 +1,7 @@
 /* retune_requests.h -- the pure parts of retuning a channel from the host: the list of requests that waits for
  * the front-end thread, and the parser of a "SECONDS:OLD_KHZ:NEW_KHZ" option.  No locking, no device, no allocation: whoever shares a
  * list between threads guards it with a mutex.  tests/hostsim/retune_requests_check.cpp runs both under the sanitizers.  Plain C that a
- * C++ compiler takes as well.  Nothing in the host library calls them yet: the device side of a retune is not in the tree. */
+ * C++ compiler takes as well.  frontend.c keeps the list (hfdl_frontend_retune), hfdl_replay.c parses the option. */
 #pragma once
 #include <math.h>
 #include <stdint.h>

@@ -393,6 +393,23 @@ int  hfdl_gpu_frontend_export_read(hfdl_gpu_frontend *fe, uint64_t from_block, i
 		void *samples, int32_t *counts, float *power, uint32_t *clipped, hfdl_gpu_export_block *info,
 		int32_t *n, uint64_t *next_block, int wait);
 
+/* Retune one channel of a running front end (HFDL ground stations change their active frequencies every few hours): blocks pushed
+ * before the call are channelized, demodulated and labelled with the old frequency, blocks pushed after it with new_freq_hz -- a frame
+ * that finished before the call keeps the old `freq` however late it is polled.  From the call on, `channel` is a freshly created
+ * channel: filter taps and channelizer constants are what a create with new_freq_hz in its place computes, bit for bit; NCO, AGC,
+ * timing, carrier, equaliser, framer and the per-channel counters (symbol_cnt included) start over.  Only sample_cnt goes on -- a PDU's
+ * sample_index stays the position in the stream.  Every other channel, the spectrum monitor and the export are untouched, bit for bit;
+ * an exported channel keeps exporting, on the new frequency.  The call closes the half being filled (as a sync does) but drains
+ * nothing and waits for no kernel: its only wait is for one of two page-locked tap buffers, i.e. for the retune two calls ago.  The
+ * first call also allocates -- two buffers of fft_size cf32 (cfg3: 128 MiB), kept -- which may take what an allocation takes; a front
+ * end that is never retuned allocates and launches nothing for it.  hfdl_gpu_frontend_all_channel_stats(), which waits for nothing,
+ * reports the channel's counters as a fresh channel's from the call on (never the old ones first: the device's own reset runs
+ * behind the demodulators in flight), sample_cnt as it goes on.  HFDL_GPU_EINVAL -- null handle, channel out of range, new_freq_hz outside +-fs/2 of the centre of the
+ * channel's own receiver, a frequency another channel of that receiver listens on, a shift the planner refuses, a front end created
+ * with HFDL_GPU_FOLD_PRUNE (its row windows depend on the pass bands) -- is checked before any device work, and a refusal, like an
+ * HFDL_GPU_ENOMEM of the first call, leaves the front end as it was.  One channel per call. */
+int  hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t channel, int32_t new_freq_hz);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */

@@ -214,6 +214,18 @@ int           hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t
  * channel frequencies in Hz as registered with hfdl_channel_create(); nfreqs = 0 selects every registered channel.  scale: format 1
  * only, finite and > 0.  dir NULL: off.  Returns 0, or -1 for bad arguments. */
 int           hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t nfreqs, int format, float scale);
+/* Retune a channel of the running front end (include/hfdl_gpu.h, hfdl_gpu_frontend_retune_channel); not in the reference, which is
+ * restarted to follow the ground stations' frequency changes.  Callable from any thread: the request old_freq -> new_freq (Hz) joins a
+ * list (at most 64 waiting) that the front-end thread applies between two pushes -- blocks pushed before keep old_freq in their PDUs,
+ * blocks pushed after carry new_freq, StatsD names and the channel's frequency follow, and an exported channel starts a new
+ * <new_freq> file.  0, or -1 when no channel listens on old_freq once the requests already waiting are applied, when one will listen
+ * on new_freq, or when the list is full.  A request the GPU library then refuses (span, a library without the entry point) is named
+ * once on stderr and the stream goes on.
+ * hfdl_frontend_schedule_retune(): the same request made by the front-end thread itself before the first block whose first sample lies
+ * at or after `seconds` of signal (sample clock: a file replay is reproducible; hfdl_replay --retune); it is checked then, and a
+ * refusal is named once on stderr.  0, or -1 for a negative or non-finite time or a full schedule (64). */
+int           hfdl_frontend_retune(int32_t old_freq, int32_t new_freq);
+int           hfdl_frontend_schedule_retune(double seconds, int32_t old_freq, int32_t new_freq);
 /* The line: "date, time, Hz low, Hz high, Hz step, samples, dB, dB, ...\n" -- date / time = UTC of t_unix, Hz low / high = lower edge of
  * the first / upper edge of the last band, Hz step = width of a band, samples = blocks averaged, dB = 10 log10(mean[b]) (dBFS; -200
  * for an empty band).  No device is needed.  Returns the length written (without the terminating 0), -1 if it does not fit. */
@@ -236,6 +248,7 @@ struct hfdl_run_stats {
 	 * the time spent in that grace period */
 	uint64_t drains;
 	double grace_s;
+	uint64_t retunes;                /* retune requests applied */
 };
 void          hfdl_frontend_run_stats(struct hfdl_run_stats *out);
 /* replay a regular input file this many times back to back (default 1); not in the reference */
