@@ -22,6 +22,7 @@ struct DemodImage;                          // demod_host.cpp: host image of the
 struct Demod {
 	int nch = 0, outs = 0, cap = 0;         // cap = max 5400-sps samples per demodulator launch (`batch` blocks)
 	int batch = 1;                          // blocks a launch can take: what was asked for, cut down by fit_batch
+	int frames_per_chan = 1, data_slots = 2;        // frame records per channel and set, data slots per channel: from the launch's signal time (planner.h plan_frame_slots)
 	uint32_t taken = 0, dropped = 0;
 	uint64_t launches = 0, decodes = 0;
 	bool separate_decode = false;           // the burst decoder runs on another stream than the demodulator
@@ -37,8 +38,8 @@ struct Demod {
 	std::unique_ptr<DemodImage> img;
 	DevBuf d_tables;                        // packed DemodTables image
 	DevArray<ChanState> d_states;
-	DevArray<float2> d_data;                // [nch][2][5040] equalised data symbols
-	DevArray<FrameRec> d_frames;            // [2][nch]: frames finished by the demodulator of an even / odd block
+	DevArray<float2> d_data;                // [nch][data_slots][5040] equalised data symbols, a ring of slots per channel
+	DevArray<FrameRec> d_frames;            // [2][nch * frames_per_chan]: frames finished by the demodulator of an even / odd launch
 	DevArray<int> d_counts;                 // [1] pdus produced, [2] pdus dropped, [3] pdus taken by the host, [4..7] frames queued, one counter per block mod 4
 	DevArray<hfdl_gpu_pdu> d_pdus;
 	DevArray<int32_t> d_freqs;
@@ -56,7 +57,7 @@ struct Demod {
 
 	Demod();
 	~Demod();
-	static int fit_batch(int outs, float resamp_rate, int want);     // blocks a launch can take at most, `want` or fewer (16-bit output counts, < 1 s of signal)
+	static int fit_batch(int outs, float resamp_rate, int want);     // blocks a launch can take at most, `want` or fewer (the block table, 16-bit output counts)
 	static size_t workgroup_lds();          // LDS bytes of a demodulator workgroup: the same for every launch length
 	int init(int nch, int outs, float resamp_rate, const int32_t *freqs, hipStream_t st, int batch_want = 1);
 	// K4 of a block.  `done` (optional) is signalled by the kernel's own dispatch packet.  frames_free: the caller has already

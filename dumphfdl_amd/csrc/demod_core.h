@@ -237,13 +237,27 @@ struct DemodInput {
 	int n_in;
 };
 
-__device__ __forceinline__ cf input_sample(const DemodInput &in, int g)
+// The block the fetches have reached, wave-uniform: samples [start, end) are block b's.  The samples are fetched in ascending order, a
+// chunk at a time, so the table is not searched per sample: a fetch starts from the cursor, only the lanes of a chunk that lie past the
+// block at hand walk on from it (once per block), and the cursor is moved up once per chunk (advance()).
+struct BlockCursor {
+	int b = 0, start = 0, end = 0;
+	__device__ __forceinline__ void begin(const DemodInput &in) { b = 0; start = 0; end = __builtin_amdgcn_readfirstlane(in.ends[0]); }
+	// to the block that holds sample g (g wave-uniform, not below start); past the launch's last sample it stays in the last block
+	__device__ __forceinline__ void advance(const DemodInput &in, int g)
+	{
+		g = __builtin_amdgcn_readfirstlane(g);
+		while (g >= end && b < DM_MAX_BLOCKS - 1) { start = end; b++; end = __builtin_amdgcn_readfirstlane(in.ends[b]); }
+	}
+};
+
+// sample g of the launch, start <= g < n_in
+__device__ __forceinline__ cf input_sample(const DemodInput &in, const BlockCursor &at, int g)
 {
-	int b = 0, start = 0;
-#pragma unroll
-	for (int u = 0; u < DM_MAX_BLOCKS - 1; u++) {
-		const int e = in.ends[u];
-		if (g >= e) { b = u + 1; start = e; }
+	int b = at.b, start = at.start;
+	if (__builtin_expect(g >= at.end, 0)) {
+		int e = at.end;
+		do { start = e; b++; e = in.ends[b]; } while (g >= e && b < DM_MAX_BLOCKS - 1);      // (g < n_in = ends[DM_MAX_BLOCKS - 1])
 	}
 	return in.chan[(size_t)b * in.blk_stride + (size_t)(g - start)];
 }
@@ -883,7 +897,9 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 	if (wave == WAVE_TIMING && lane < D_MF - 1) io.agc[(-1 - lane) & DM_AGC_MASK] = a.mf_hist[lane];
 	const int rs0 = n_out < DM_CHUNK ? n_out : DM_CHUNK;
 	int in_loaded = need(rs0 + 2 * DM_CHUNK);
-	for (int g = tid; g < in_loaded; g += DM_THREADS) in.ring[g & DM_IN_MASK] = input_sample(in, g);
+	BlockCursor at;
+	at.begin(in);
+	for (int g = tid; g < in_loaded; g += DM_THREADS) in.ring[g & DM_IN_MASK] = input_sample(in, at, g);
 	if (TAPS && tid == 0) io.tap_counts[1] = 0;
 	__syncthreads();
 	if (wave == WAVE_RESAMPLER) resample_outputs<TAPS>(rs_phase, T, io, in.ring, 0, rs0, lane);
@@ -911,11 +927,12 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 				to = resampler_advance(pp, n_out);
 				// the samples two chunks further on are asked for first and put into the ring last
 				const int hi = need(resampler_fetch_ahead(to, n_out));
+				at.advance(in, in_loaded);            // the block of the first sample this step fetches
 				cf nx[2];
 #pragma unroll
 				for (int u = 0; u < 2; u++) {
 					const int g = in_loaded + 64 * u + lane;
-					nx[u] = g < hi ? input_sample(in, g) : cf{0.f, 0.f};
+					nx[u] = g < hi ? input_sample(in, at, g) : cf{0.f, 0.f};
 				}
 				resample_outputs<TAPS>(rs_phase, T, io, in.ring, pp.rs_ready, to, lane);
 #pragma unroll
@@ -923,7 +940,7 @@ __device__ inline int demod_block(ChanArrays &a, const DemodConst &T, const Bloc
 					const int g = in_loaded + 64 * u + lane;
 					if (g < hi) in.ring[g & DM_IN_MASK] = nx[u];
 				}
-				for (int g = in_loaded + 128 + lane; g < hi; g += 64) in.ring[g & DM_IN_MASK] = input_sample(in, g);      // (a chunk spans fewer than 65 samples)
+				for (int g = in_loaded + 128 + lane; g < hi; g += 64) in.ring[g & DM_IN_MASK] = input_sample(in, at, g);      // (a chunk spans fewer than 65 samples)
 				if (hi > in_loaded) in_loaded = hi;
 			}
 			if (lane == 0) mail.rs_ready = to;

@@ -10,6 +10,7 @@
 #include "demod_launch.h"
 #include "demod_lds.h"
 #include "demod_tables.h"
+#include "planner.h"
 
 namespace hfdl {
 
@@ -42,19 +43,16 @@ static DevTables resolve_tables(const void *d_img, const DemodTables &h)
 
 size_t Demod::workgroup_lds() { return demod_workgroup_lds(0); }
 
+static_assert(DM_MAX_BLOCKS == PLAN_MAX_HALF, "a half that closes full is one demodulator launch");
+
 // blocks a launch can take at most, `want` or fewer: what the kernel's block table holds, a workgroup's LDS (no bound for the product,
-// whose per-sample arrays are rings, demod_lds.h; the test-only strict build keeps whole-launch arrays), output counts that fit 16 bits ...
+// whose per-sample arrays are rings, demod_lds.h; the test-only strict build keeps whole-launch arrays) and output counts that fit 16
+// bits (cum[] in LDS: cfg3's 32 blocks make 2 x 31 734).  The frames a channel can finish in the launch are no bound: init() sizes the
+// frame queue and the data slots from the launch's signal time.
 int Demod::fit_batch(int outs, float resamp_rate, int want)
 {
-	int batch = want < 1 ? 1 : (want > DM_MAX_BLOCKS ? DM_MAX_BLOCKS : want);
-	for (;; batch--) {
-		const int cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
-		if (batch > 1 && demod_workgroup_lds(cap) > 160 * 1024) continue;
-		// ... and less than one second of signal per launch WHATEVER asked for the batch (cap samples at 5400 sps): a channel then finishes
-		// at most one frame per launch -- the frame queue has one entry per channel and the frame buffers two slots (planner.h
-		// plan_batches asks for no more; an override, which it takes as it is, must not get past this)
-		if (batch == 1 || (2 * cap <= 65535 && (double)cap / 5400.0 < 1.0)) break;      // cum[] counts outputs in 16 bits
-	}
+	int batch = fit_output_counts(outs, resamp_rate, want);
+	while (batch > 1 && demod_workgroup_lds(demod_launch_samples(outs, batch, resamp_rate)) > 160 * 1024) batch--;
 	return batch;
 }
 
@@ -64,7 +62,10 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 	if (resamp_rate <= 0.5f || resamp_rate > 1.0f) return fail(HFDL_GPU_ERANGE, "resampling rate %g outside (0.5, 1]", (double)resamp_rate);   // one arbitrary stage, no half-band stages
 	// blocks per launch
 	batch = fit_batch(outs, resamp_rate, batch_want);
-	cap = (int)((double)outs * (double)batch * (double)resamp_rate + 8);
+	cap = demod_launch_samples(outs, batch, resamp_rate);
+	// a launch covers at most cap samples at 5400 sps: frame records per channel and set, data slots per channel
+	const FrameSlots fs = plan_frame_slots((double)cap / 5400.0);
+	frames_per_chan = fs.per_channel; data_slots = fs.data_slots;
 	img = std::make_unique<DemodImage>();
 	build_demod_tables(img->h, resamp_rate);
 	CREATE_TRY(d_tables.alloc(sizeof(DemodTables)));
@@ -75,9 +76,9 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 	for (auto &s : init) chan_state_init(s, img->h.eq_h0);
 	CREATE_TRY(d_states.alloc((size_t)nch));
 	CREATE_TRY(hipMemcpy(d_states, init.data(), sizeof(ChanState) * (size_t)nch, hipMemcpyHostToDevice));
-	CREATE_TRY(d_data.alloc((size_t)nch * 2 * MAX_DATA_SYMBOLS));
-	CREATE_TRY(hipMemsetAsync(d_data, 0, sizeof(float2) * (size_t)nch * 2 * MAX_DATA_SYMBOLS, st));
-	CREATE_TRY(d_frames.alloc(2 * (size_t)nch));
+	CREATE_TRY(d_data.alloc((size_t)nch * data_slots * MAX_DATA_SYMBOLS));
+	CREATE_TRY(hipMemsetAsync(d_data, 0, sizeof(float2) * (size_t)nch * data_slots * MAX_DATA_SYMBOLS, st));
+	CREATE_TRY(d_frames.alloc(2 * (size_t)nch * frames_per_chan));
 	CREATE_TRY(d_counts.alloc(8));
 	CREATE_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * 8, st));
 	CREATE_TRY(h_snap.alloc(8));
@@ -121,8 +122,8 @@ int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk,
 	// the decoder of launch i-2 has read this frame queue.  Every wait or record is a barrier packet of its own in the queue
 	// (~5 us of idle stream each): on the demodulator-bound geometries the caller moves this one to the channelizer's stream
 	if (separate_decode && !frames_free && ev_dec[i & 1]) HIP_TRY(hipStreamWaitEvent(st, ev_dec[i & 1], 0));
-	B.states = d_states; B.data = (cf *)d_data.p; B.frames = d_frames + (size_t)(i & 1) * nch; B.counts = d_counts;
-	B.frame_count = d_counts + 4 + (int)(i & 3); B.frame_cap = nch;
+	B.states = d_states; B.data = (cf *)d_data.p; B.data_slots = data_slots; B.frames = d_frames + (size_t)(i & 1) * nch * frames_per_chan; B.counts = d_counts;
+	B.frame_count = d_counts + 4 + (int)(i & 3); B.frame_cap = nch * frames_per_chan;
 	const bool tw = taps_on && taps_enabled;
 	B.tap_rs = tw ? (cf *)d_tap_rs.p : nullptr; B.tap_mf = (cf *)d_tap_mf.p; B.tap_sym = (cf *)d_tap_sym.p; B.tap_lvl = d_tap_lvl; B.tap_counts = d_tap_counts;
 	B.cap = cap;
@@ -136,8 +137,8 @@ int Demod::enqueue_decode(int buf, hipStream_t st, hipEvent_t start, hipEvent_t 
 	if (!img) return fail(HFDL_GPU_EINVAL, "burst decoder launch before init");
 	const uint64_t i = decodes++;
 	if (i + 1 != launches) return fail(HFDL_GPU_EINVAL, "burst decoder launch %llu without its demodulator launch", (unsigned long long)i);      // one per demodulator launch, in order
-	launch_burst_decode(d_frames + (size_t)(i & 1) * nch, d_counts, d_counts + 4 + (int)(i & 3), d_counts + 4 + (int)((i + 2) & 3), nch,
-			(const cf *)d_data.p, img->t.scrambler, d_freqs, d_pdus, pdu_cap, st, start, stop);
+	launch_burst_decode(d_frames + (size_t)(i & 1) * nch * frames_per_chan, d_counts, d_counts + 4 + (int)(i & 3), d_counts + 4 + (int)((i + 2) & 3), nch * frames_per_chan,
+			(const cf *)d_data.p, data_slots, img->t.scrambler, d_freqs, d_pdus, pdu_cap, st, start, stop);
 	// what the ring holds once this block is done, for a host that collects without draining the pipeline
 	HIP_TRY(hipMemcpyAsync(h_snap.p + 4 * (buf & 1), d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
 	if (separate_decode) {

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(DM_THREADS, 5) void demod_kernel(DevTables T, Demod
 	K.rs_h = l_rs_h; K.ss_mf = nullptr; K.ss_dmf = nullptr; K.mf = l_mf; K.eq_h0 = l_eq; K.m1_hi = l_m1; K.m1_lo = l_m1 + 8; K.corr_tab = l_corr;
 	BlockIo io;
 	io.rs = (cf *)(lds + L.rs); io.agc = (cf *)(lds + L.agc); io.mf = (cf *)(lds + L.mfo); io.lvl = (float *)(lds + L.lvl); io.cap = B.cap;
-	io.data = B.data + (size_t)c * 2 * MAX_DATA_SYMBOLS;
+	io.data = B.data + (size_t)c * B.data_slots * MAX_DATA_SYMBOLS; io.data_slots = B.data_slots;
 	io.frames = B.frames; io.frame_count = B.frame_count; io.frame_cap = B.frame_cap;
 	io.channel = c;
 	DemodInput in;
@@ -362,8 +362,8 @@ struct BurstFrame {
 };
 
 // frame f's parameters, and the scrambler and constellation constants staged at `consts` (DEC_CONST_BYTES of LDS); ends in a barrier
-__device__ __forceinline__ BurstFrame burst_frame(const FrameRec *__restrict__ frames, int f, const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler,
-		unsigned char *consts, int lane)
+__device__ __forceinline__ BurstFrame burst_frame(const FrameRec *__restrict__ frames, int f, const cf *__restrict__ data_all, int data_slots,
+		const uint8_t *__restrict__ scrambler, unsigned char *consts, int lane)
 {
 	BurstFrame b;
 	b.l_scr = consts;
@@ -371,7 +371,7 @@ __device__ __forceinline__ BurstFrame burst_frame(const FrameRec *__restrict__ f
 	b.fr = frames[f];
 	b.mp = mode_params(b.fr.mode);
 	b.nsym = b.mp.segments * 30; b.ncoded = b.nsym * b.mp.arity; b.cols = b.ncoded / 40;
-	b.sym = data_all + ((size_t)b.fr.channel * 2 + b.fr.slot) * MAX_DATA_SYMBOLS;
+	b.sym = data_all + ((size_t)b.fr.channel * data_slots + b.fr.slot) * MAX_DATA_SYMBOLS;
 	b.mask_flip = b.fr.bitmask_lsb ? -1.0f : 1.0f;
 	b.l_scr[lane] = lane < 120 ? scrambler[lane] : 0;
 	if (lane + 64 < 120) b.l_scr[lane + 64] = scrambler[lane + 64];
@@ -429,7 +429,7 @@ __device__ __forceinline__ int burst_soft_wave(const int mode, const int nsym, c
 }
 
 __global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__restrict__ frames, int *counts, const int *nframes_ptr, int *stale_count, int frame_cap,
-		const cf *__restrict__ data_all, const uint8_t *__restrict__ scrambler, const int32_t *__restrict__ freqs,
+		const cf *__restrict__ data_all, int data_slots, const uint8_t *__restrict__ scrambler, const int32_t *__restrict__ freqs,
 		hfdl_gpu_pdu *__restrict__ pdus, int pdu_cap)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -442,7 +442,7 @@ __global__ __launch_bounds__(64) void burst_decode_kernel(const FrameRec *__rest
 	constexpr BurstLds L(true);
 	uint8_t *table = lds + L.table, *vin = lds + L.vin;
 	uint64_t *decw = (uint64_t *)(lds + L.decw);
-	const BurstFrame b = burst_frame(frames, f, data_all, scrambler, lds + L.consts, lane);
+	const BurstFrame b = burst_frame(frames, f, data_all, data_slots, scrambler, lds + L.consts, lane);
 	const FrameRec &fr = b.fr;
 	const ModeParams &mp = b.mp;
 	const int vin_len = burst_soft_wave(fr.mode, b.nsym, b.ncoded, b.cols, b.sym, b.mask_flip, b.l_scr, b.l_psk, table, vin);
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(64) void burst_soft_kernel(const FrameRec *__restri
 	const int f = blockIdx.x, lane = threadIdx.x;
 	constexpr BurstLds L(false);
 	uint8_t *table = lds + L.table, *vin = lds + L.vin;
-	const BurstFrame b = burst_frame(frames, f, data_all, scrambler, lds + L.consts, lane);
+	const BurstFrame b = burst_frame(frames, f, data_all, 2, scrambler, lds + L.consts, lane);
 	const int vin_len = burst_soft_wave(b.fr.mode, b.nsym, b.ncoded, b.cols, b.sym, b.mask_flip, b.l_scr, b.l_psk, table, vin);
 	__syncthreads();
 	uint8_t *dst = vin_out + (size_t)f * HFDL_GPU_LAB_VIN_MAX;
@@ -636,11 +636,11 @@ void launch_demod(bool taps, const DevTables &T, const DemodBuffers &B, const cf
 	else hipExtLaunchKernelGGL(demod_kernel<false>, dim3((unsigned)nch), dim3(DM_THREADS), (unsigned)lds, st, start, stop, 0, T, B, chan_out, n_in, outs_stride, nblk, nch);
 }
 
-void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data,
+void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data, int data_slots,
 		const uint8_t *scrambler, const int32_t *freqs, hfdl_gpu_pdu *pdus, int pdu_cap, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
 	hipExtLaunchKernelGGL(burst_decode_kernel, dim3((unsigned)frame_cap), dim3(64), (unsigned)burst_decode_lds(), st, start, stop, 0, frames, counts,
-			nframes, stale_count, frame_cap, data, scrambler, freqs, pdus, pdu_cap);
+			nframes, stale_count, frame_cap, data, data_slots, scrambler, freqs, pdus, pdu_cap);
 }
 
 void launch_retune_demod(ChanState *states, const ChanState *image, int c, hipStream_t st, hipEvent_t done)

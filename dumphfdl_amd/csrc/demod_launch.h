@@ -19,7 +19,8 @@ struct DevTables {            // device image, pointers resolved on the host
 
 struct DemodBuffers {
 	ChanState *states;
-	cf *data;
+	cf *data;                   // [nch][data_slots][MAX_DATA_SYMBOLS]
+	int data_slots;
 	FrameRec *frames;
 	int *counts;
 	int *frame_count;           // this launch's frames-queued counter (four, rotating: see Demod::enqueue_demod)
@@ -37,8 +38,8 @@ int prepare_burst_decode();                  // ... of K5 alone: a process that 
 // K4: one workgroup per channel, `lds` = demod_workgroup_lds(B.cap); start / stop (optional) ride on the kernel's dispatch
 void launch_demod(bool taps, const DevTables &T, const DemodBuffers &B, const cf *chan_out, const int *n_in, int outs_stride, int nblk, int nch,
 		size_t lds, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-// K5: one wavefront per entry of the frame queue (`frame_cap` of them)
-void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data,
+// K5: one wavefront per entry of the frame queue (`frame_cap` of them); data: [channel][data_slots][MAX_DATA_SYMBOLS]
+void launch_burst_decode(const FrameRec *frames, int *counts, const int *nframes, int *stale_count, int frame_cap, const cf *data, int data_slots,
 		const uint8_t *scrambler, const int32_t *freqs, hfdl_gpu_pdu *pdus, int pdu_cap, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 // retune: states[c] = *image except sample_cnt and data_slot (the demodulators' stream; `done`, optional, rides on the dispatch);
 // freqs[c] = freq (the burst decoders' stream)

@@ -2,8 +2,8 @@
 // Plain C++ over demod_logic.h's state structs: the kernel, the host-side size computation and tests/hostsim read the same constructor.
 //
 // Every per-sample array is a power-of-two RING indexed by the sample's index in the launch: a workgroup's LDS does not depend on how
-// many blocks the launch takes (37 KiB: four workgroups per CU), and the batch is bounded by the 16-bit output counts and the frame
-// queue alone (Demod::fit_batch).  What keeps a ring entry alive until its last reader is done is the distance the stages may run apart,
+// many blocks the launch takes (37 KiB: four workgroups per CU), and the batch is bounded by the block table and the 16-bit output
+// counts alone (Demod::fit_batch).  What keeps a ring entry alive until its last reader is done is the distance the stages may run apart,
 // all of them measured from the carrier wave's progress s3_done.  The rules are code, below the ring sizes they depend on:
 // resampler_advance(), agc_advance(), timing_advance(), carrier_advance() say how far a stage may go in a step of the pipeline, and the
 // step loops of demod_core.h demod_block call them (and keep no clamp of their own).  tests/hostsim/demod_pipe_check.cpp steps the four stages through the mailbox under
@@ -42,10 +42,9 @@ static_assert(DM_AGC_RING >= DM_CHUNK + D_MF - 1 && DM_CHUNK <= 64, "AGC ring");
 // resampling rate > 0.5 a chunk of outputs spans fewer than 2 DM_CHUNK + 1 inputs, plus D_RS_TAPS - 1 of history
 constexpr int DM_IN_RING = 256, DM_IN_MASK = DM_IN_RING - 1;
 static_assert(DM_IN_RING >= 3 * (2 * DM_CHUNK + 1) + D_RS_TAPS, "input ring");
-// Blocks per launch at most (the block table in LDS).  Seven is what the whole-launch arrays of the earlier layout let the small
-// geometries take, and what every measurement of them was made with: cfg2's half of 8 blocks is two launches of 4, the first launch's
-// burst decoder beside the second.  Eight (one launch per half there) has not been measured.
-constexpr int DM_MAX_BLOCKS = 7;
+// Blocks per launch at most (the block table in LDS): a whole half (planner.h PLAN_MAX_HALF), so that a half that closes full can be
+// ONE launch.  The resampler wave does not search the table per sample: it carries the block at hand (demod_core.h BlockCursor).
+constexpr int DM_MAX_BLOCKS = 32;
 constexpr size_t DM_LDS_BUDGET = 40 * 1024;  // per workgroup: four to a CU's 160 KiB
 
 // What the four waves tell each other at a step's barrier (demod_core.h demod_block).  Two of these in LDS, written in turn: a step's

@@ -118,7 +118,8 @@ struct BlockIo {
 	cf *rs, *agc, *mf;             // scratch [cap]
 	float *lvl;                    // scratch [cap]
 	int cap;
-	cf *data;                      // global [2][MAX_DATA_SYMBOLS] of this channel
+	cf *data;                      // global [data_slots][MAX_DATA_SYMBOLS] of this channel: a ring, a finished frame keeps its slot
+	int data_slots = 2;            // (planner.h plan_frame_slots)
 	FrameRec *frames;              // global queue
 	int *frame_count;
 	int frame_cap;
@@ -531,7 +532,7 @@ HFDL_FN void on_symbol(ChanScalars &s, ChanScalars &c, ChanArrays &a, const Demo
 					io.frames[slot] = fr;
 				}
 			}
-			s.data_slot ^= 1;
+			s.data_slot = s.data_slot + 1 < io.data_slots ? s.data_slot + 1 : 0;
 			c.cnt_frames++;
 			framer_reset(s, c, a, T.eq_h0);
 			s.symbol_cnt = 0;

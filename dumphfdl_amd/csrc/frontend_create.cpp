@@ -286,7 +286,7 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	fe->fold_bound = lab.fold_bound < 0 ? nch >= 128 : lab.fold_bound != 0;
 	const float resamp_rate = (float)(1800 * 3) / ((float)fe->sample_rate / (float)fe->decimation);
 	BatchOverrides ov;
-	ov.demod_batch = (int)env_long("HFDL_GPU_DEMOD_BATCH", 1, 8, 0);
+	ov.demod_batch = (int)env_long("HFDL_GPU_DEMOD_BATCH", 1, hfdl_gpu_frontend::MAX_HALF, 0);
 	ov.fold_batch = (int)env_long("HFDL_GPU_FOLD_BATCH", 1, hfdl_gpu_frontend::MAX_HALF, 0);
 	ov.pruned = fe->prune_tol > 0;
 	ov.fold_slices = lab.fold_slices;

@@ -168,7 +168,7 @@ inline int pick_slices(int nch, int rows)
 
 // What the environment (the shim reads it; include/hfdl_gpu.h documents the names) and the laboratory build ask for; 0 / false = not asked
 struct BatchOverrides {
-	int demod_batch = 0;        // HFDL_GPU_DEMOD_BATCH 1..8: taken as it is
+	int demod_batch = 0;        // HFDL_GPU_DEMOD_BATCH 1..32: taken as it is
 	int fold_batch = 0;         // HFDL_GPU_FOLD_BATCH 1..32
 	bool pruned = false;        // HFDL_GPU_FOLD_PRUNE: one slice, the row windows are the parallelism
 	int fold_slices = 0;        // laboratory A/B: slices of alias rows per channel and bin (a power of two; a slice keeps at least 16 rows)
@@ -188,7 +188,7 @@ constexpr int PLAN_MAX_HALF = 32;       // blocks per half at most: what one fol
 constexpr int PLAN_MAX_STAGE = 18;      // staging buffers at most: uploads run at most 17 blocks ahead (HFDL_GPU_PREFETCH_MAX + 1)
 
 // n / input_size / pre: the block geometry (Plan).  fold_bound: the fold bounds the block (128 channels and more).  demod_fit(want):
-// blocks a demodulator launch can take, `want` or fewer (Demod::fit_batch: 16-bit output counts, < 1 s of signal).
+// blocks a demodulator launch can take, `want` or fewer (Demod::fit_batch: the block table, 16-bit output counts).
 template <typename Fit>
 inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sample_rate, int pre, bool fold_bound, Fit demod_fit, const BatchOverrides &ov)
 {
@@ -216,17 +216,13 @@ inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sampl
 	// to ONE launch, which treats them as one longer stretch of samples -- the per-channel state is carried sample by sample, so the
 	// result is that of block-by-block processing.  A caller that waits for its PDUs after every block (live input: poll / sync) still
 	// gets a launch per block: a partial batch is launched by any call that needs the results.  Bounds (Demod::fit_batch): the kernel's
-	// block table, output counts that fit 16 bits, and one second of signal -- less than half the shortest frame (2.34 s), so that a channel
-	// finishes at most one frame per launch (frame queue: one entry per channel; two data slots).  The LDS is no bound: a workgroup's
-	// per-sample arrays are rings (demod_lds.h).
+	// block table (a whole half) and output counts that fit 16 bits.  Neither the LDS (a workgroup's per-sample arrays are rings,
+	// demod_lds.h) nor the frames a channel finishes in a launch bound it: the frame queue and the channels' data slots are sized from
+	// the launch's signal time (plan_frame_slots below).
+	// A half that closes full is one launch: the larger of a second's worth of blocks (at most 8) and the fold's launch.
 	int want = (int)std::floor(1.0 / ((double)input_size / (double)sample_rate));
 	want = std::max(1, std::min(8, want));
-	// Where the fold bounds the block: three.  The measurement behind it predates the rings -- the demodulator workgroups (one per channel)
-	// must stay CO-RESIDENT with the fold's (34 KiB of LDS per workgroup in the thirty-two-column form) and a forward-FFT tile, and with
-	// whole-launch arrays three cfg3 blocks took 117 KiB of a CU's 160 KiB; one block more and the kernels took turns (round 5, at 159 KiB:
-	// a demodulator launch beside a 4.8 ms fold took 5.5 ms, profiles/r05_experiments.md).  A workgroup takes 37 KiB today whatever the
-	// launch's length (demod_lds.h), so the LDS no longer argues for three; more has not been measured since.
-	if (fold_bound) want = std::min(want, 3);
+	want = std::max(want, b.fold_nb);
 	if (ov.demod_batch) want = ov.demod_batch;                              // 1 = a launch per block
 	want = demod_fit(want);
 	if (nrx > 1) {
@@ -254,6 +250,42 @@ inline BatchPlan plan_batches(int nch, int nrx, int n, int input_size, int sampl
 	b.half_first = (fold_bound && b.half_blocks > 16 && !ov.no_ramp) ? 16 : b.half_blocks;
 	b.n_stage = std::min(b.half_blocks + 2, PLAN_MAX_STAGE);      // a 32-block half is not uploaded a whole half ahead: 17 blocks of link time cover a 6 ms fold five times over
 	return b;
+}
+
+// ---------------------------------------------------------------- what a demodulator launch can take
+
+// 5400-sps samples a launch of `batch` blocks produces at most: `outs` channelizer samples per block and channel at most, resampled by `rate`
+inline int demod_launch_samples(int outs, int batch, float rate) { return (int)((double)outs * (double)batch * (double)rate + 8); }
+// Blocks a launch can take, `want` or fewer, by the block table (a whole half) and the output counts: the timing recovery yields at most two
+// outputs per sample in the long run, and the running count of a launch's outputs is kept in 16 bits per sample in LDS (demod_lds.h cum[]).
+// cfg3's 32 blocks fit (2 x 31 734); a geometry whose half holds more than 6 s of signal is cut.
+inline int fit_output_counts(int outs, float rate, int want)
+{
+	int batch = std::max(1, std::min(PLAN_MAX_HALF, want));
+	while (batch > 1 && 2 * demod_launch_samples(outs, batch, rate) > 65535) batch--;
+	return batch;
+}
+
+// ---------------------------------------------------------------- frames a launch can finish, and how long their symbols must stay
+
+// A demodulator launch covers up to t_launch seconds of signal (T_L) and can finish several frames of one channel.  The frames of
+// launch i are queued in the frame queue of set i & 1 and decoded by the burst decoder of launch i, which reads their data symbols from
+// the channel's ring of data slots: a finished frame keeps its slot, the next frame takes the next one.
+//   T_F  the shortest distance between two frame ends of a channel.  The framer finds a frame by its A sequences and needs no prekey:
+//        2 A + M1 + M2 + nine T + 72 data segments = 3771 symbols at 1800 Bd, 2.095 s (a frame on the air, prekey included, lasts 2.344 s).
+//   F    frame records per channel and set: ends at least T_F apart, so at most floor(T_L / T_F) + 1 of them lie in one launch.
+//   S    data slots per channel.  The slot of a frame that ended in launch i is written again by the S-th frame after it, whose data
+//        follow the end of the (S - 1)-th: at least (S - 1) T_F later.  The burst decoder of launch i is only known to be done when the
+//        demodulator of launch i + 2 starts (Demod::enqueue_demod waits for it there and nowhere earlier), so the write must not fall
+//        into launch i or i + 1: those cover less than 2 T_L of signal behind the frame's end.  (S - 1) T_F >= 2 T_L holds with
+//        S = floor(2 T_L / T_F) + 2; one slot fewer and a frame that ends at the start of launch i loses its symbols to a frame of
+//        launch i + 1 (tests/hostsim/frame_slots_check.cpp steps both).
+// One second of signal per launch gives F = 1 and S = 2, a 32-block launch of cfg3 (5.9 s) F = 3 and S = 7 (72 MB of symbols).
+constexpr double PLAN_MIN_FRAME_S = 3771.0 / 1800.0;
+struct FrameSlots { int per_channel, data_slots; };       // F, S
+inline FrameSlots plan_frame_slots(double t_launch, double t_frame = PLAN_MIN_FRAME_S)
+{
+	return FrameSlots{ (int)std::floor(t_launch / t_frame) + 1, (int)std::floor(2.0 * t_launch / t_frame) + 2 };
 }
 
 // ---------------------------------------------------------------- which stream a block's forward FFT runs on

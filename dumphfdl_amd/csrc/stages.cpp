@@ -102,7 +102,7 @@ extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int
 	HIP_TRY(d_pdus.alloc(sizeof(hfdl_gpu_pdu) * (size_t)nframes));
 	if ((rc = prepare_burst_decode())) return rc;
 	StageTimer tm;
-	launch_burst_decode(in.frames.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, nullptr, nframes, in.data.as<const cf>(),
+	launch_burst_decode(in.frames.as<const FrameRec>(), d_counts.as<int>(), d_counts.as<int>() + 4, nullptr, nframes, in.data.as<const cf>(), 2,
 			in.scrambler.as<const uint8_t>(), d_freqs.as<const int32_t>(), d_pdus.as<hfdl_gpu_pdu>(), nframes, nullptr, nullptr, nullptr);
 	g_stage_ms = tm.stop();
 	if ((rc = finish_stage())) return rc;

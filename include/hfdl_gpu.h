@@ -70,9 +70,10 @@ typedef struct {
 	int32_t max_outputs_per_block;   /* ceil(post_input_size / post_decimation): what a block can emit when the carried
 	                                    decimation remainder is non-zero (post_input_size not a multiple of post_decimation);
 	                                    size HFDL_GPU_TAP_CHAN_OUT buffers from this */
-	int32_t demod_batch;             /* blocks one demodulator launch takes when they are pushed faster than they are collected (up to one second
-	                                    of signal, cut down to what fits the LDS: 3 at 40 Msps, up to 8 on the small geometries).  Results do not
-	                                    depend on it; a poll / sync always demodulates what has been pushed.  HFDL_GPU_DEMOD_BATCH=1..8 overrides
+	int32_t demod_batch;             /* blocks one demodulator launch takes when they are pushed faster than they are collected (a half that
+	                                    closes full is one launch, cut down where a launch's output counts would not fit 16 bits: 32 at 40 Msps, 8 on
+	                                    the small geometries).  Results do not
+	                                    depend on it; a poll / sync always demodulates what has been pushed.  HFDL_GPU_DEMOD_BATCH=1..32 overrides
 	                                    the default at create time.  0 from hfdl_gpu_plan_geometry() */
 	int32_t fold_batch;              /* blocks whose spectra one fold launch multiplies against ONE pass over the per-channel filter taps when
 	                                    they are pushed faster than they are collected (src/fastddc.c:123-150 run for that many blocks; the taps are
@@ -92,7 +93,7 @@ typedef struct {
 
 /* Create-time configuration read from the environment by hfdl_gpu_frontend_create() (every create reads it afresh; nothing is cached):
  *   HFDL_GPU_FOLD_BATCH   1..32  blocks per fold launch (geometry.fold_batch)
- *   HFDL_GPU_DEMOD_BATCH  1..8   blocks per demodulator launch (geometry.demod_batch)
+ *   HFDL_GPU_DEMOD_BATCH  1..32  blocks per demodulator launch (geometry.demod_batch)
  *   HFDL_GPU_HOST_THREADS >= 1   host threads that design the filter taps (default: one per core; set to cores / processes when several
  *                                front ends are created at once on one host)
  *   HFDL_GPU_PDU_RING     >= 1   capacity of the device PDU ring (default max(4096, 64 per channel))
