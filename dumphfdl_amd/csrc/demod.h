@@ -1,4 +1,5 @@
-// demod.h -- host-side owner of the per-channel demodulator / burst decoder device state (K4 + K5).
+// demod.h -- host-side owner of the per-channel demodulator / burst decoder device state (K4 + K5) and of a closed half's way through
+// them: from "this half is yours" (launch_half) to "these PDUs are ready" (collect_ready).  planner.h DemodOrder is the ordering rule.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -8,6 +9,8 @@
 #include "../../include/hfdl_gpu.h"
 #include "hip_handles.h"
 #include "kernels.h"
+#include "launch_timers.h"
+#include "planner.h"
 
 namespace hfdl {
 
@@ -24,8 +27,7 @@ struct Demod {
 	int batch = 1;                          // blocks a launch can take: what was asked for, cut down by fit_batch
 	int frames_per_chan = 1, data_slots = 2;        // frame records per channel and set, data slots per channel: from the launch's signal time (planner.h plan_frame_slots)
 	uint32_t taken = 0, dropped = 0;
-	uint64_t launches = 0, decodes = 0;
-	bool separate_decode = false;           // the burst decoder runs on another stream than the demodulator
+	DemodOrder order;                       // which frame queue, counter, wait and done event a launch gets; which snapshot a poll reads
 	int bounce_cap = 0;
 	int pdu_cap = 0;
 	bool taps_on = true;                    // stage-tap buffers allocated
@@ -40,7 +42,7 @@ struct Demod {
 	DevArray<ChanState> d_states;
 	DevArray<float2> d_data;                // [nch][data_slots][5040] equalised data symbols, a ring of slots per channel
 	DevArray<FrameRec> d_frames;            // [2][nch * frames_per_chan]: frames finished by the demodulator of an even / odd launch
-	DevArray<int> d_counts;                 // [1] pdus produced, [2] pdus dropped, [3] pdus taken by the host, [4..7] frames queued, one counter per block mod 4
+	DevArray<int> d_counts;                 // [1] pdus produced, [2] pdus dropped, [3] pdus taken by the host, [4..7] frames queued, one counter per launch mod 4
 	DevArray<hfdl_gpu_pdu> d_pdus;
 	DevArray<int32_t> d_freqs;
 	DevArray<ChanState> d_state_image;      // one ChanState as chan_state_init() makes it: allocated by the first retune, never otherwise
@@ -49,25 +51,33 @@ struct Demod {
 	DevArray<float2> d_tap_rs, d_tap_mf, d_tap_sym;      // stage taps
 	DevArray<float> d_tap_lvl;
 	DevArray<int> d_tap_counts;             // [nch][2]
-	PinnedBuf<int> h_snap;                  // [2][4]: d_counts as of the end of the block that used buffer 0 / 1
+	PinnedBuf<int> h_snap;                  // [2][4]: d_counts as of the end of the newest launch of half 0 / 1
 	PinnedBuf<hfdl_gpu_pdu> h_pdu_bounce;   // [bounce_cap]
 	PinnedBuf<ChanScalars> h_stats_bounce;  // [nch]
 	Event ev_dec[2];                        // decoder of an even / odd launch done: its frame queue and counter may be reused (made by the first such decoder)
 	Event ev_retuned;                       // rides on the newest retune_demod_kernel (made by the first retune)
+	// demodulator launch of the half in buffer 0 / 1 done (its decoder may start), the LAST launch of the half at [0]: the half is free
+	DoneEvent dm[2][PLAN_MAX_HALF];
+	Event ev_demod[3];                      // recorded behind the last burst decoder of a half, in turn (DemodOrder::decoded_event)
 
 	Demod();
 	~Demod();
 	static int fit_batch(int outs, float resamp_rate, int want);     // blocks a launch can take at most, `want` or fewer (the block table, 16-bit output counts)
 	static size_t workgroup_lds();          // LDS bytes of a demodulator workgroup: the same for every launch length
 	int init(int nch, int outs, float resamp_rate, const int32_t *freqs, hipStream_t st, int batch_want = 1);
-	// K4 of a block.  `done` (optional) is signalled by the kernel's own dispatch packet.  frames_free: the caller has already
-	// ordered this launch after the decoder of launch i-2 (frames_free_event()), so no wait is queued in front of the kernel.
-	// chan_out / out_count: `nblk` consecutive blocks, [nblk][nch][outs] and [nblk][nch]
-	int enqueue_demod(const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done = nullptr, bool frames_free = false, hipEvent_t start = nullptr);
-	hipEvent_t frames_free_event() const { return separate_decode ? ev_dec[launches & 1].e : nullptr; }   // of the NEXT launch; may be null
-	int enqueue_decode(int buf, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);   // K5 + PDU-ring snapshot of the same block; the events ride on the kernel's dispatch (timing)
+	// A closed half of `nblk` consecutive blocks -- chan_out [nblk][nch][outs], out_count [nblk][nch] -- `batch` blocks per launch, each
+	// launch followed by its burst decoder.  Stream B first waits for `ready` (the half's channelizer output is there; null: it is
+	// there already).  Every done event rides on its kernel's dispatch; timed launches take their pairs from `timers`.
+	int launch_half(const float2 *chan_out, const int *out_count, int nblk, int half, hipEvent_t ready, hipStream_t st_b, hipStream_t st_d, LaunchTimers &timers);
+	hipEvent_t half_read_event(int half) const { return dm[half][0].pending() ? dm[half][0].event() : nullptr; }      // what the inverse FFT into `half` waits for; null: nothing
+	// What stream A waits for so that the next launch needs no wait of its own for the decoder of two launches ago (null: nothing, and
+	// the launch needs none either).  Only with a decode stream of its own; the launch is told (DemodOrder::wait_on_a).
+	hipEvent_t frames_free_event() { return order.wait_on_a() ? ev_dec[order.next_set()].e : nullptr; }
+	void settle() { for (auto &half : dm) for (DoneEvent &d : half) d.settle(); }        // everything queued is complete
 	int collect(hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);                    // stream idle: everything produced
-	int collect_snapshot(int buf, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);  // up to the end of that buffer's block
+	// the pipeline keeps running: what the ring is known to hold once the last demodulator of the half before the newest is done --
+	// waited for, or (wait = false) asked after: not done yet, nothing is taken
+	int collect_ready(bool wait, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);
 	int take(unsigned produced, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);
 	// Retune of channel c (hfdl_gpu_frontend_retune_channel): prepare_retune() makes the state image (the first call allocates it and
 	// queues its upload on `st_b`; nothing else changes if it fails); enqueue_retune() queues the state reset behind the demodulators
@@ -80,6 +90,12 @@ struct Demod {
 	int tap(int what, int channel, const void **src, size_t *nfloats);
 	int stats(int channel, hfdl_gpu_channel_stats *out);
 	int read_constants(void *tables, size_t tables_bytes, void *constants, size_t constants_bytes);   // laboratory read-back: sizeof(DemodTables), sizeof(HfdlConstants)
+private:
+	// the two kernels of launch `p`: K4 (`done` is signalled by its dispatch packet), then K5 + the PDU-ring snapshot of `half`; the
+	// start / stop events ride on the dispatches (timing)
+	int enqueue_demod(const DemodLaunch &p, const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, hipEvent_t start);
+	int enqueue_decode(const DemodLaunch &p, int half, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+	int collect_snapshot(int slot, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);  // up to the end of the launch that wrote the slot
 };
 
 }  // namespace hfdl

@@ -1,6 +1,6 @@
 // demod_host.cpp -- Demod: the host-side owner of the per-channel demodulator / burst decoder state (K4 + K5) of a front end -- its
-// device memory, the PDU ring's host logic, the statistics read-back.  The kernels and their launchers are demod_kernels.hip's
-// (demod_launch.h).
+// device memory, the launches of a closed half and what orders them (planner.h DemodOrder has the rule), the PDU ring's host logic,
+// the statistics read-back.  The kernels and their launchers are demod_kernels.hip's (demod_launch.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -96,6 +96,8 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 	CREATE_TRY(h_stats_bounce.alloc((size_t)nch));
 	CREATE_TRY(d_freqs.alloc((size_t)nch));
 	CREATE_TRY(hipMemcpyAsync(d_freqs, freqs, sizeof(int32_t) * (size_t)nch, hipMemcpyHostToDevice, st));
+	for (Event &e : ev_demod) CREATE_TRY(e.create(EV_NO_TIMING));
+	for (auto &half : dm) for (DoneEvent &d : half) CREATE_TRY(d.own.create(EV_NO_TIMING));
 	if (taps_on) {
 		CREATE_TRY(d_tap_rs.alloc((size_t)nch * cap));
 		CREATE_TRY(d_tap_mf.alloc((size_t)nch * cap));
@@ -109,21 +111,41 @@ int Demod::init(int nch_, int outs_, float resamp_rate, const int32_t *freqs, hi
 	return prepare_demod_kernels(lds_bytes);
 }
 
-// Frames finished by the demodulator of launch i are queued in d_frames[i & 1] and counted in d_counts[4 + (i & 3)].  The
-// burst decoder of launch i may run on another stream than the demodulator of launch i+1; it zeroes the counter of launch i+2,
-// whose previous users (launch i-2) are done and whose next user (the demodulator of launch i+2) is made to wait for this
-// decoder by the caller -- no memset launch per block, no counter shared by two kernels that can overlap.
-int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, bool frames_free, hipEvent_t start)
+// A half of `nblk` blocks is demodulated `batch` blocks per launch, each launch followed by its burst decoder.  One launch index serves
+// both kernels of a launch: planner.h DemodOrder says which frame queue and counters they share, what the demodulator waits for and
+// which of the half's done events it carries.
+int Demod::launch_half(const float2 *chan_out, const int *out_count, int nblk, int half, hipEvent_t ready, hipStream_t st_b, hipStream_t st_d, LaunchTimers &timers)
 {
-	if (!img || nblk < 1 || nblk > batch || nblk > DM_MAX_BLOCKS)       // (the kernel's block table holds DM_MAX_BLOCKS)
-		return fail(HFDL_GPU_EINVAL, "demodulator launch of %d blocks: 1 .. %d", nblk, batch);
+	if (!img || nblk < 1 || batch > DM_MAX_BLOCKS)       // (the kernel's block table holds DM_MAX_BLOCKS)
+		return fail(HFDL_GPU_EINVAL, "demodulator launches of %d blocks, up to %d each, before init or past the block table", nblk, batch);
+	if (ready) HIP_TRY(hipStreamWaitEvent(st_b, ready, 0));
+	const int k = (nblk + batch - 1) / batch;
+	for (int j0 = 0, l = 0; j0 < nblk; j0 += batch, l++) {
+		const int take = std::min(batch, nblk - j0);
+		const DemodLaunch p = order.launch(l, k);
+		// the done event rides on the kernel's dispatch; with the decoder on its own stream the channelizer may have waited for the frame
+		// queue already (frames_free_event), so on the demodulator-bound geometries ONE barrier packet separates consecutive demodulators
+		DoneEvent &done = dm[half][p.done_event];
+		hipEvent_t t_start = nullptr;
+		if (int rc = timers.arm(ST_DEMOD, take, done, t_start)) return rc;
+		if (int rc = enqueue_demod(p, chan_out + (size_t)j0 * nch * outs, out_count + (size_t)j0 * nch, take, st_b, done.event(), t_start)) return rc;
+		if (order.own_decode) HIP_TRY(hipStreamWaitEvent(st_d, done.event(), 0));
+		hipEvent_t k5_start = nullptr, k5_stop = nullptr;
+		if (int rc = timers.arm(ST_DECODE, take, k5_start, k5_stop)) return rc;
+		if (int rc = enqueue_decode(p, half, st_d, k5_start, k5_stop)) return rc;
+	}
+	HIP_TRY(hipEventRecord(ev_demod[order.decoded_event(0)], st_d));      // (launches follow their hand-over: this half is the newest)
+	return 0;
+}
+
+int Demod::enqueue_demod(const DemodLaunch &p, const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, hipEvent_t start)
+{
 	DemodBuffers B;
-	const uint64_t i = launches++;          // per demodulator launch (not per block: channelize-only blocks launch none)
-	// the decoder of launch i-2 has read this frame queue.  Every wait or record is a barrier packet of its own in the queue
-	// (~5 us of idle stream each): on the demodulator-bound geometries the caller moves this one to the channelizer's stream
-	if (separate_decode && !frames_free && ev_dec[i & 1]) HIP_TRY(hipStreamWaitEvent(st, ev_dec[i & 1], 0));
-	B.states = d_states; B.data = (cf *)d_data.p; B.data_slots = data_slots; B.frames = d_frames + (size_t)(i & 1) * nch * frames_per_chan; B.counts = d_counts;
-	B.frame_count = d_counts + 4 + (int)(i & 3); B.frame_cap = nch * frames_per_chan;
+	// the decoder of two launches ago has read this frame queue.  Every wait or record is a barrier packet of its own in the queue
+	// (~5 us of idle stream each): on the demodulator-bound geometries the front end moves this one to the channelizer's stream
+	if (p.wait_decoder) HIP_TRY(hipStreamWaitEvent(st, ev_dec[p.set], 0));
+	B.states = d_states; B.data = (cf *)d_data.p; B.data_slots = data_slots; B.frames = d_frames + (size_t)p.set * nch * frames_per_chan; B.counts = d_counts;
+	B.frame_count = d_counts + 4 + p.counter; B.frame_cap = nch * frames_per_chan;
 	const bool tw = taps_on && taps_enabled;
 	B.tap_rs = tw ? (cf *)d_tap_rs.p : nullptr; B.tap_mf = (cf *)d_tap_mf.p; B.tap_sym = (cf *)d_tap_sym.p; B.tap_lvl = d_tap_lvl; B.tap_counts = d_tap_counts;
 	B.cap = cap;
@@ -132,18 +154,15 @@ int Demod::enqueue_demod(const float2 *chan_out, const int *out_count, int nblk,
 	return 0;
 }
 
-int Demod::enqueue_decode(int buf, hipStream_t st, hipEvent_t start, hipEvent_t stop)
+int Demod::enqueue_decode(const DemodLaunch &p, int half, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
-	if (!img) return fail(HFDL_GPU_EINVAL, "burst decoder launch before init");
-	const uint64_t i = decodes++;
-	if (i + 1 != launches) return fail(HFDL_GPU_EINVAL, "burst decoder launch %llu without its demodulator launch", (unsigned long long)i);      // one per demodulator launch, in order
-	launch_burst_decode(d_frames + (size_t)(i & 1) * nch * frames_per_chan, d_counts, d_counts + 4 + (int)(i & 3), d_counts + 4 + (int)((i + 2) & 3), nch * frames_per_chan,
+	launch_burst_decode(d_frames + (size_t)p.set * nch * frames_per_chan, d_counts, d_counts + 4 + p.counter, d_counts + 4 + p.zeroed, nch * frames_per_chan,
 			(const cf *)d_data.p, data_slots, img->t.scrambler, d_freqs, d_pdus, pdu_cap, st, start, stop);
-	// what the ring holds once this block is done, for a host that collects without draining the pipeline
-	HIP_TRY(hipMemcpyAsync(h_snap.p + 4 * (buf & 1), d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-	if (separate_decode) {
-		if (!ev_dec[i & 1]) HIP_TRY(ev_dec[i & 1].create(EV_NO_TIMING));
-		HIP_TRY(hipEventRecord(ev_dec[i & 1], st));
+	// what the ring holds once this launch is done, for a host that collects without draining the pipeline
+	HIP_TRY(hipMemcpyAsync(h_snap.p + 4 * half, d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+	if (order.own_decode) {
+		if (!ev_dec[p.set]) HIP_TRY(ev_dec[p.set].create(EV_NO_TIMING));
+		HIP_TRY(hipEventRecord(ev_dec[p.set], st));
 	}
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -212,9 +231,41 @@ int Demod::collect(hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
 	return take((unsigned)counts[1], out, max, n, st);
 }
 
-int Demod::collect_snapshot(int buf, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
+// Leave the newest half running: wait for the last DEMODULATOR of the half before it -- that is the flow control: the caller may
+// queue the next blocks, the demodulator stream will not run dry -- and take what the PDU ring is known to hold: the snapshot
+// written after that half's last burst decoder if it has finished too, else the one written a half earlier (a stale snapshot
+// yields nothing new; those PDUs come with the next call).  Waiting for the burst decoder here (0.3 ms when a long frame ended)
+// left the demodulator idle for as long on the demodulator-bound geometries (profiles/r03_experiments.md).
+int Demod::collect_ready(bool wait, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
 {
-	const volatile int *snap = h_snap.p + 4 * (buf & 1);
+	const int half = order.poll_half();
+	if (half < 0) return 0;                             // fewer than two halves: nothing is known to be done
+	const hipEvent_t ev = dm[half][0].event();          // the last demodulator launch of that half
+	if (!wait) {
+		// no waiting at all: a caller whose flow control is elsewhere (the C host: the page-locked ring slots it leases to the
+		// uploads) only takes what is complete, and comes back
+		const hipError_t q = hipEventQuery(ev);
+		if (q == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+		if (q != hipSuccess) return fail(HFDL_GPU_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
+	} else {
+		HIP_TRY(hipEventSynchronize(ev));
+	}
+	// A snapshot slot is written by its half's burst decoders' 16-byte copies: read only once the last of them is known to be done
+	// (ev_demod is recorded behind it).  "Not ready" is an answer, not an error to be found by a later check.
+	auto decoded = [&](int back) {
+		const int e = order.decoded_event(back);
+		const bool yes = e >= 0 && hipEventQuery(ev_demod[e]) == hipSuccess;
+		if (!yes) (void)hipGetLastError();
+		return yes;
+	};
+	const bool newer = decoded(1);
+	const int slot = order.snapshot_slot(newer, !newer && decoded(2));
+	return slot < 0 ? 0 : collect_snapshot(slot, out, max, n, st);
+}
+
+int Demod::collect_snapshot(int slot, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
+{
+	const volatile int *snap = h_snap.p + 4 * slot;
 	const uint32_t d = (uint32_t)snap[2];
 	if ((int32_t)(d - dropped) > 0) dropped = d;       // monotone: an older snapshot never takes the count back
 	return take((unsigned)snap[1], out, max, n, st);

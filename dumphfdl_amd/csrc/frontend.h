@@ -1,6 +1,7 @@
-// frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h, its launch ledger, and what the
-// translation units of the shim share (namespace hfdl).  hfdl_gpu.cpp is the pipeline, frontend_create.cpp builds a front end,
-// frontend_query.cpp reads one, demod_host.cpp owns its demodulator state, stages.cpp holds the one-shot stage entry points (checks, staging
+// frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h and what the translation units of the
+// shim share (namespace hfdl; the launch ledger and the done events are launch_timers.h's).  hfdl_gpu.cpp is the pipeline,
+// frontend_create.cpp builds a front end, frontend_query.cpp reads one, demod_host.cpp owns its demodulator state and a closed half's
+// way through demodulator and burst decoder (demod.h), stages.cpp holds the one-shot stage entry points (checks, staging
 // and read-back; the kernels' launchers are beside the kernels), lab.cpp the laboratory build's switches, probes and stage.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include "kernels.h"
 #include "planner.h"
 #include "retune_launch.h"
+#include "launch_timers.h"
 #include "demod.h"
 #include "spectrum.h"
 #include "export_ring.h"
@@ -54,53 +56,6 @@ int finish_stage();
 struct StageFrames {
 	DevBuf frames, data, scrambler;
 	int upload(const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb, int32_t nframes);
-};
-
-// ---------------------------------------------------------------- launch timing
-
-// What the next stream waits for.  A launch site owns one fixed event; a TIMED launch carries a pooled start / stop pair on its dispatch
-// (one dispatch carries one start and one stop), so its stop event doubles as its done event.  event() is what the newest launch
-// signalled.  settle(), once everything queued is complete, puts the fixed event back in the pooled one's place before the pool hands
-// that one out again: a completed event stands for "done" as well as any other.
-struct DoneEvent {
-	Event own;
-	hipEvent_t cur = nullptr;
-	hipEvent_t signal() { return cur = own; }                     // an untimed launch: its dispatch signals the fixed event
-	hipEvent_t event() const { return cur ? cur : own.e; }
-	bool pending() const { return cur != nullptr; }               // a launch has signalled it: there is something to wait for (not before the first launch)
-	void settle() { if (cur) cur = own; }
-};
-
-// The timed kernel launches of a front end (hfdl_gpu_frontend_reset_timers), by stage in the order of hfdl_gpu_frontend_stage_times().
-// A timed launch carries a start / stop event pair on its own dispatch (hipExtLaunchKernelGGL): no extra packet in the queue.  The
-// pairs come from a pool filled outside any timed region and are read back and returned to it by the next drain (a sync / poll).
-enum Stage { ST_FFT, ST_FOLD, ST_IFFT, ST_DEMOD, ST_DECODE, ST_N };
-static_assert(ST_N == 5, "hfdl_gpu_frontend_stage_times() reports five stages");
-struct LaunchTimers {
-	struct Timed { Event start, stop; int blocks; };
-	struct Totals { double ms = 0; int64_t launches = 0, blocks = 0; std::vector<Timed> pending; };     // read so far; launched, not yet read
-	bool on = false;
-	Totals stage[ST_N];
-	std::vector<Timed> pool;            // free pairs, made by reset() outside any timed region
-	int64_t fold_shapes[FOLD_MAX_BLOCKS + 1] = {};   // fold launches by block count
-	double fold_shape_ms[FOLD_MAX_BLOCKS + 1] = {};  // ... and their kernel time
-	Event first_fold;                   // start of the first timed fold since the reset: anchor of the steady-state step period
-	double span_ms = 0;                 // first timed fold start -> last timed fold start
-	int64_t fold_last_blocks = 0;       // blocks of the last timed fold
-
-	// timing on: a pair from the pool (made here when a long run without a drain has used it up -- a timed launch is never silently
-	// untimed) into `start` / `stop`.  Timing off: both are left as they are.
-	int arm(Stage s, int blocks, hipEvent_t &start, hipEvent_t &stop);
-	// ... for a launch other streams wait for: the stop event stands in as its done event; timing off, the launch signals `done`'s own
-	int arm(Stage s, int blocks, DoneEvent &done, hipEvent_t &start)
-	{
-		hipEvent_t stop = done.signal();
-		const int rc = arm(s, blocks, start, stop);
-		done.cur = stop;
-		return rc;
-	}
-	int drain();                // every timed launch is complete: add it up, the pairs go back to the pool
-	int reset(bool enable);     // after a drain: every total to zero; timing on fills the pool with enough pairs for the launches between two drains
 };
 
 // ---------------------------------------------------------------- front end
@@ -217,7 +172,7 @@ struct hfdl_gpu_frontend {
 	// (its own stream, memory and events, in that order: they go between the front end's events and its memory.  Safe, because the
 	// destructor has synchronised every stream, the demodulator's collection stream among them, before the first member goes, and
 	// nothing the front end owns is queued on that stream or waits for those events afterwards.)
-	hfdl::Demod demod;
+	hfdl::Demod demod;                  // from "this half is yours" to "these PDUs are ready": the launches, their done events, what a poll reads
 	int4 *d_rx = nullptr, *d_grp = nullptr;      // device copies: receiver table, fold group tables (kernels.h Geometry::grp_tab)
 	float2 *d_hist[2] = { nullptr, nullptr }, *d_work = nullptr, *d_spec = nullptr, *d_taps = nullptr, *d_partial = nullptr;
 	float2 *d_tw_m = nullptr;
@@ -245,13 +200,10 @@ struct hfdl_gpu_frontend {
 	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
 
 	// ---- events
-	// demodulator launch j of the half in buffer 0 / 1 done (the decoder may start), the LAST launch of the half at [0]: chan_out is free
-	hfdl::DoneEvent dm[2][MAX_HALF];
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)
 	hfdl::DoneEvent fft_done;           // the last forward FFT of a half on stream A: what the held-back demodulators wait for
 	hfdl::DoneEvent spec[2];            // newest forward FFT BESIDE the fold (stream C / F) of the half in spectrum set 0 / 1 done (rides on its last pass): what the half's fold waits for
 	hfdl::Event ev_switch;              // recorded on the stream of the forward FFT before, where a block's FFT runs on the other one
-	hfdl::Event ev_demod[2];            // recorded behind the last burst decoder of the half
 	hfdl::Event ev_stage_ready[MAX_STAGE];      // copy of the host block in this buffer done: what its forward FFT and input_done_upto() wait for
 	hfdl::Event ev_stage_free[MAX_STAGE];       // pass 1 of the forward FFT that read this buffer done (rides on that dispatch): the copy stream may refill it
 	hfdl::LaunchTimers timers;
@@ -313,9 +265,6 @@ struct hfdl_gpu_frontend {
 	hfdl::FftOutLayout tap_layout;
 	int pending_demod_buf = -1;         // half whose demodulator launches are held back until the next half's forward FFTs are queued ...
 	int pending_demod_nblk = 0;         // ... and the blocks in it
-	bool frames_wait_on_a = false;      // stream A has waited for the frame queue the next demodulator launch reuses
-	int demod_buf = -1;                 // half / snapshot slot of the newest demodulator launch
-	int prev_demod_buf = -1;            // ... and of the one before it
 
 	~hfdl_gpu_frontend();
 };

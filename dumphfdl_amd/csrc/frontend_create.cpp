@@ -237,7 +237,7 @@ static int create_streams(hfdl_gpu_frontend *fe, const LabConfig &lab)
 	// channels the round-4 timeline shows a 1.18 ms decoder launch serially ahead of a half's first demodulator).
 	if (lab.decode_stream) CREATE_TRY(fe->stream_d.create());
 	else fe->stream_d.alias(fe->stream_b);
-	fe->demod.separate_decode = fe->own_decode_stream();
+	fe->demod.order.own_decode = fe->own_decode_stream();
 	// Forward FFTs of the half being filled beside the fold of the half before (two sets of spectra / phasor tables / state snapshots).
 	// The product decides per push by where the block lies (planner.h FftRule): a device-resident block's FFT runs on the input stream C,
 	// which carries no copy for such a block; an uploaded block's stays in front of the fold on stream A (a stream of their own for ALL
@@ -301,8 +301,6 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	for (int i = 0; i < 2; i++) {
 		CREATE_TRY(fe->spec[i].own.create(EV_NO_TIMING));
 		CREATE_TRY(fe->chan[i].own.create(EV_NO_TIMING));
-		CREATE_TRY(fe->ev_demod[i].create(EV_NO_TIMING));
-		for (DoneEvent &d : fe->dm[i]) CREATE_TRY(d.own.create(EV_NO_TIMING));
 	}
 	CREATE_TRY(fe->fft_done.own.create(EV_NO_TIMING));
 	CREATE_TRY(fe->ev_switch.create(EV_NO_TIMING));

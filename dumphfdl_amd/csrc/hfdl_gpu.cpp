@@ -75,7 +75,7 @@ int hfdl_gpu_frontend::settle_events()
 {
 	if (int rc = timers.drain()) return rc;
 	// everything is complete: the pooled events may be reused
-	for (auto &half : dm) for (DoneEvent &d : half) d.settle();
+	demod.settle();
 	for (DoneEvent *d : { &chan[0], &chan[1], &fft_done, &spec[0], &spec[1] }) d->settle();
 	return 0;
 }
@@ -209,31 +209,22 @@ extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 // 2.56 ms or 2.87 ms per launch (profiles/r01_experiments.md).  So the demodulator launches of a half are held back until the
 // forward FFTs of the NEXT half have been queued on stream A: the workgroups then arrive while only the LDS-free fold kernel is resident, spread
 // evenly, and the fold time is the good one every time.  A sync / poll launches held-back demodulators at once.
-// A half of `nblk` blocks is demodulated `batch` blocks per launch, each launch followed by its burst decoder.
-static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, bool after_fft)
+// The launches themselves, their burst decoders and what orders them are Demod::launch_half's.
+static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, hipEvent_t ready)
 {
-	// the forward FFTs of the next half follow this half's inverse FFT on stream A, so their event covers the half's own too
-	HIP_TRY(hipStreamWaitEvent(fe->stream_b, after_fft ? fe->fft_done.event() : fe->chan[buf].event(), 0));
-	const int launches = (nblk + fe->batch - 1) / fe->batch;
-	for (int j0 = 0, l = 0; j0 < nblk; j0 += fe->batch, l++) {
-		const int take = std::min(fe->batch, nblk - j0);
-		// the done event rides on the kernel's dispatch; with the decoder on its own stream the channelizer has already waited for the
-		// frame queue (close_half), so on the demodulator-bound geometries ONE barrier packet separates consecutive demodulators
-		DoneEvent &done = fe->dm[buf][launches - 1 - l];        // the LAST launch of the half at [0]
-		hipEvent_t t_start = nullptr;
-		int rc = fe->timers.arm(ST_DEMOD, take, done, t_start);
-		if (rc) return rc;
-		const int slot = buf * fe->half_blocks + j0;
-		rc = fe->demod.enqueue_demod(fe->chan_slot(slot), fe->cnt_slot(slot), take, fe->stream_b, done.event(), l == 0 && fe->frames_wait_on_a, t_start);
-		if (rc) return rc;
-		if (fe->own_decode_stream()) HIP_TRY(hipStreamWaitEvent(fe->stream_d, done.event(), 0));
-		hipEvent_t k5_start = nullptr, k5_stop = nullptr;
-		if ((rc = fe->timers.arm(ST_DECODE, take, k5_start, k5_stop))) return rc;
-		if ((rc = fe->demod.enqueue_decode(buf, fe->stream_d, k5_start, k5_stop))) return rc;
-	}
-	fe->frames_wait_on_a = false;
-	HIP_TRY(hipEventRecord(fe->ev_demod[buf], fe->stream_d));
-	return 0;
+	const int slot0 = buf * fe->half_blocks;
+	return fe->demod.launch_half(fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, buf, ready, fe->stream_b, fe->stream_d, fe->timers);
+}
+
+// The half being filled is left with `nblk` blocks in it: its last block is the newest channelized one, the other half is filled next.
+// with_demod: the half goes to the demodulator (launched now or held back).
+static void leave_half(hfdl_gpu_frontend *fe, int nblk, bool with_demod)
+{
+	const int half = fe->cur_half;
+	fe->last_slot = half * fe->half_blocks + nblk - 1;
+	fe->last_index = nblk - 1;              // (one block: nothing further back to read, read_tap_block)
+	fe->cur_half ^= 1;
+	if (with_demod) fe->demod.order.hand_over(half);      // what poll_pdus_ready(.., 1) waits for: the half before the newest one
 }
 
 static int flush_pending_demod(hfdl_gpu_frontend *fe, bool after_fft)
@@ -241,7 +232,8 @@ static int flush_pending_demod(hfdl_gpu_frontend *fe, bool after_fft)
 	if (fe->pending_demod_buf < 0) return 0;
 	const int buf = fe->pending_demod_buf, nblk = fe->pending_demod_nblk;
 	fe->pending_demod_buf = -1;
-	return launch_demod(fe, buf, nblk, after_fft);
+	// the forward FFTs of the next half follow this half's inverse FFT on stream A, so their event covers the half's own too
+	return launch_demod(fe, buf, nblk, after_fft ? fe->fft_done.event() : fe->chan[buf].event());
 }
 
 // When a block is pushed: its forward FFT into the next spectrum slot of the half being filled (the block's NCO phasor table and carried
@@ -352,15 +344,13 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 			return fail(HFDL_GPU_EINVAL, "no fold launch of %d blocks on this geometry", take);
 	}
 	// this half is free once the demodulator launches that read it last (two halves ago) are done
-	if (fe->dm[half][0].pending()) HIP_TRY(hipStreamWaitEvent(fe->stream, fe->dm[half][0].event(), 0));
+	if (hipEvent_t e = fe->demod.half_read_event(half)) HIP_TRY(hipStreamWaitEvent(fe->stream, e, 0));
 	if (with_demod && fe->own_decode_stream() && !fe->fold_bound) {
 		// this half's first demodulator (launched right after this kernel, on stream B) reuses the frame queue the decoder of two
 		// launches ago read: on the demodulator-bound geometries wait for it HERE, where the stream has slack, instead of in front of
 		// the demodulator.  (Where the fold bounds the block stream A is the critical one and must not wait for a burst decoder:
-		// measured, a 4.3 ms hole in front of every inverse FFT.  There the demodulator waits itself, enqueue_demod.)
-		hipEvent_t e = fe->demod.frames_free_event();
-		if (e) HIP_TRY(hipStreamWaitEvent(fe->stream, e, 0));
-		fe->frames_wait_on_a = true;
+		// measured, a 4.3 ms hole in front of every inverse FFT.  There the demodulator waits itself, planner.h DemodOrder.)
+		if (hipEvent_t e = fe->demod.frames_free_event()) HIP_TRY(hipStreamWaitEvent(fe->stream, e, 0));
 	}
 	const int slot0 = half * fe->half_blocks;
 	hipEvent_t ifft_start = nullptr;
@@ -382,16 +372,12 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 		}
 	}
 	HIP_TRY(hipGetLastError());
-	fe->last_slot = slot0 + nblk - 1;
-	fe->last_index = nblk - 1;
 	fe->last_set = half;
-	fe->cur_half ^= 1;
 	fe->batch_fill = 0;
+	leave_half(fe, nblk, with_demod);
 	if (!with_demod) return 0;                   // channelize-only: the half is simply left behind
-	fe->prev_demod_buf = fe->demod_buf;          // what poll_pdus_ready(.., 1) waits for: the half before the newest one
-	fe->demod_buf = half;
 	// (forward FFTs beside the fold run beside everything anyway: there is no quiet moment to hold the demodulators back for)
-	if (!plan.hold_back) return launch_demod(fe, half, nblk, false);
+	if (!plan.hold_back) return launch_demod(fe, half, nblk, fe->chan[half].event());
 	fe->pending_demod_buf = half;
 	fe->pending_demod_nblk = nblk;
 	return 0;
@@ -426,12 +412,8 @@ extern "C" int hfdl_gpu_frontend_push_baseband(hfdl_gpu_frontend *fe, const floa
 	const int half = fe->cur_half, slot0 = half * fe->half_blocks;
 	HIP_TRY(hipMemcpy(fe->chan_slot(slot0), chan_out, sizeof(float2) * (size_t)g.nch * (size_t)g.outs, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(fe->cnt_slot(slot0), counts, sizeof(int32_t) * (size_t)g.nch, hipMemcpyHostToDevice));
-	fe->last_slot = slot0;
-	fe->last_index = 0;                                     // one block in this half: nothing further back to read (read_tap_block)
-	fe->cur_half ^= 1;
-	fe->prev_demod_buf = fe->demod_buf;
-	fe->demod_buf = half;
-	return launch_demod(fe, half, 1, false);
+	leave_half(fe, 1, true);
+	return launch_demod(fe, half, 1, nullptr);               // no inverse FFT filled this half: the copies above are done, there is no event to wait for
 }
 
 // one step: raw[0 .. nrx - 1] = a block of every receiver
@@ -572,28 +554,8 @@ extern "C" int hfdl_gpu_frontend_poll_pdus_ready(hfdl_gpu_frontend *fe, hfdl_gpu
 	if (max_in_flight <= 0) return hfdl_gpu_frontend_poll_pdus(fe, out, max, n);
 	if (int rc = check_poll_args(fe, out, max, n)) return rc;
 	*n = 0;
-	// Leave the newest launch running: wait for the DEMODULATOR of the one before it -- that is the flow control: the caller may
-	// queue the next blocks, the demodulator stream will not run dry -- and take what the PDU ring is known to hold: the snapshot
-	// written after that launch's burst decoder if it has finished too, else the one written two launches earlier (a stale snapshot
-	// yields nothing new; those PDUs come with the next call).  Waiting for the burst decoder here (0.3 ms when a long frame ended)
-	// left the demodulator idle for as long on the demodulator-bound geometries (profiles/r03_experiments.md).
-	const int buf = fe->prev_demod_buf;
-	if (buf < 0) return 0;                              // fewer than two launches: nothing is known to be done
+	// the newest half is left running (Demod::collect_ready): max_in_flight 1 waits for the demodulators of the half before it, 2 and more
+	// wait for nothing
 	HIP_TRY(hipSetDevice(fe->device));
-	const hipEvent_t ev = fe->dm[buf][0].event();       // the last demodulator launch of that half
-	if (max_in_flight >= 2) {
-		// no waiting at all: a caller whose flow control is elsewhere (the C host: the page-locked ring slots it leases to the
-		// uploads) only takes what is complete, and comes back
-		const hipError_t q = hipEventQuery(ev);
-		if (q == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-		if (q != hipSuccess) return fail(HFDL_GPU_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
-	} else {
-		HIP_TRY(hipEventSynchronize(ev));
-	}
-	// The snapshot slot of that half is written by its burst decoders' 16-byte copies: read it only once the last of them is known to be
-	// done (ev_demod is recorded behind it); until then the OTHER slot is the stable one -- it was written two halves ago, and the
-	// newest half's decoders, which write it next, sit behind this half's on their stream.
-	const bool decoded = hipEventQuery(fe->ev_demod[buf]) == hipSuccess;
-	if (!decoded) (void)hipGetLastError();            // "not ready" is an answer, not an error to be found by a later check
-	return fe->demod.collect_snapshot(decoded ? buf : buf ^ 1, out, max, n, fe->stream_d);
+	return fe->demod.collect_ready(max_in_flight < 2, out, max, n, fe->stream_d);
 }

@@ -276,7 +276,7 @@ inline int fit_output_counts(int outs, float rate, int want)
 //   F    frame records per channel and set: ends at least T_F apart, so at most floor(T_L / T_F) + 1 of them lie in one launch.
 //   S    data slots per channel.  The slot of a frame that ended in launch i is written again by the S-th frame after it, whose data
 //        follow the end of the (S - 1)-th: at least (S - 1) T_F later.  The burst decoder of launch i is only known to be done when the
-//        demodulator of launch i + 2 starts (Demod::enqueue_demod waits for it there and nowhere earlier), so the write must not fall
+//        demodulator of launch i + 2 starts (DemodOrder below, hazard 1: the wait goes there and nowhere earlier), so the write must not fall
 //        into launch i or i + 1: those cover less than 2 T_L of signal behind the frame's end.  (S - 1) T_F >= 2 T_L holds with
 //        S = floor(2 T_L / T_F) + 2; one slot fewer and a frame that ends at the start of launch i loses its symbols to a frame of
 //        launch i + 1 (tests/hostsim/frame_slots_check.cpp steps both).
@@ -350,6 +350,62 @@ struct FftOrder {
 	}
 	void retune() { retuned = true; }                   // the half being filled has been closed (close()) and the retune's kernel queued
 	void drained() { prev_side = -1; halves = 0; retuned = false; }      // every stream has been synchronised
+};
+
+// ---------------------------------------------------------------- a closed half's way through demodulator and burst decoder
+
+// A half handed to the demodulator is taken in k launches of up to `batch` blocks, numbered i = 0, 1, .. over the front end's life; each
+// is a demodulator kernel on stream B and then its burst decoder, with the 16-byte snapshot of the PDU ring's counts behind it, on
+// stream D (a stream of their own; in a laboratory A/B run D is B).  The frames the demodulator of launch i finishes are queued in frame
+// queue set i mod 2 and counted in frame counter i mod 4; the decoder of launch i reads both and zeroes the counter of launch i + 2,
+// whose users before (launch i - 2) are done -- no memset launch per block, no counter shared by two kernels that can overlap.  The
+// snapshot goes to the slot of the launch's HALF (0 / 1).  The contract -- four hazards, none of which may lose a frame or a PDU or
+// show one half-written:
+//   1. the demodulator of launch i does not start before the decoder of launch i - 2 is done: it reuses that decoder's frame queue, and
+//      that decoder zeroes its counter.  D = B: stream order.  Else launch i carries the wait on stream B in front of its kernel
+//      (wait_decoder) -- unless it is a half's first launch and stream A has taken the wait in front of the half's inverse FFT
+//      (wait_on_a(): where the demodulator bounds the block stream A has the slack and B then needs ONE barrier packet between
+//      consecutive demodulators; the front end decides when, Demod remembers that it did).  So "the decoder of launch i is done" is
+//      established no later than the start of the demodulator of launch i + 2, and nowhere earlier: plan_frame_slots above rests on it
+//   2. the decoder of launch i waits for the demodulator of launch i: for the done event the launch carries, unless D = B
+//   3. the inverse FFT into a half waits for the last demodulator launch that read that half: the half's done event 0 -- the launches
+//      of a half carry its done events k - 1 .. 0 (done_event), the LAST one event 0, however many there are
+//   4. a poll that leaves the pipeline running (hfdl_gpu_frontend_poll_pdus_ready) waits for, or asks after, the last DEMODULATOR of
+//      the half before the newest (poll_half) and reads a snapshot slot only when the decoders that write it are done: that half's own
+//      slot if its last decoder is found done too; else the slot of the half before THAT, if its last decoder is found done and the
+//      slot is another one -- the newest half's decoders, which write it next, sit behind the unfinished one on their stream; else
+//      none (snapshot_slot).  The demodulator the poll waited for says nothing about the decoder of the launch before it (hazard 1
+//      reaches two launches back), and with one launch per half that is the half whose slot is read: so it is asked after.  A half's
+//      last decoder carries one of three events in turn (decoded_event): the newest half's record leaves the two before it alone
+// tests/hostsim/demod_order_check.cpp runs the rule inside a front end reduced to launches and waits over every short call sequence.
+struct DemodLaunch { int set, counter, zeroed; bool wait_decoder; int done_event; };
+struct DemodOrder {
+	uint64_t launches = 0;          // demodulator launches so far = the index of the next one (channelize-only blocks launch none)
+	bool own_decode = false;        // the burst decoders have a stream of their own
+	bool waited_on_a = false;       // stream A has taken the next launch's wait for the decoder of two launches ago
+	uint64_t halves = 0;            // halves handed to the demodulator so far (launched or held back)
+	int newest = -1, before = -1, before2 = -1;     // the newest of them, the one before it and the one before that (0 / 1; -1: none)
+	void hand_over(int half) { before2 = before; before = newest; newest = half; halves++; }
+	int decoded_event(int back) const { return halves > (uint64_t)back ? (int)((halves - 1 - (uint64_t)back) % 3) : -1; }     // of the newest half (0), the one before (1), before that (2); -1: none
+	int next_set() const { return (int)(launches & 1); }        // the decoder whose event wait_on_a() is about
+	// stream A takes the next launch's wait (own_decode only); false: there is no such decoder yet, nothing to wait for
+	bool wait_on_a() { waited_on_a = true; return launches >= 2; }
+	// launch l of the k a half is taken in
+	DemodLaunch launch(int l, int k)
+	{
+		const uint64_t i = launches++;
+		const DemodLaunch p{ (int)(i & 1), (int)(i & 3), (int)((i + 2) & 3), own_decode && i >= 2 && !(l == 0 && waited_on_a), k - 1 - l };
+		waited_on_a = false;
+		return p;
+	}
+	int poll_half() const { return before; }                    // -1: fewer than two halves, nothing is known to be done
+	// the slot a poll reads: the last decoder of poll_half() found done / not, that of the half before it found done / not; -1: none
+	// (a channelize-only half in between gives consecutive halves the same slot: the newer one's decoders may be writing it)
+	int snapshot_slot(bool decoded, bool older_decoded) const
+	{
+		const int older = before2 >= 0 && before2 != before ? before2 : -1;
+		return decoded ? (before != newest ? before : older) : older_decoded ? older : -1;
+	}
 };
 
 // ---------------------------------------------------------------- the CU partition of the fold-bound geometries

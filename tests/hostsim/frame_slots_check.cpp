@@ -6,7 +6,7 @@
 // start on them) until the frame's own end, when its record is queued in the set of the launch at hand (launch i: set i & 1) and the
 // channel moves on to the next slot of its ring.  Launches cut the signal anywhere, each covering at most T_L, one-block launches included.
 // The burst decoder of launch i reads the records of its set and their slots; it is done at some moment that is only known to lie before
-// the demodulator of launch i + 2 starts (Demod::enqueue_demod waits for it there), so until then neither its set nor the slots of its
+// the demodulator of launch i + 2 starts (planner.h DemodOrder, hazard 1: the wait goes there), so until then neither its set nor the slots of its
 // frames may be written.
 //
 // Checked in every step: no write touches a slot whose frame has not been read yet; no set holds more than F records of one channel.
