@@ -21,7 +21,9 @@ pids=""
 objs=""
 for o in $KERNEL_OBJS; do
 	case " $NO_CONTRACT_OBJS " in *" $o "*) contract=-ffp-contract=off ;; *) contract= ;; esac
-	$HIPCC $COMMON $contract -c $o.hip -o $BUILD/$o.o & pids="$pids $!"
+	riders=INCLUDED_$o; included=""
+	for r in ${!riders}; do included="$included --include=$r.hip"; done
+	$HIPCC $COMMON $contract $included -c $o.hip -o $BUILD/$o.o & pids="$pids $!"
 	objs="$objs $BUILD/$o.o"
 done
 for o in $SHIM_OBJS; do
@@ -32,7 +34,7 @@ for p in $pids; do wait $p; done          # set -e: a failed compile stops the b
 # -Bsymbolic: calls between the library's own entry points stay inside THIS library when the product and the laboratory build
 # are loaded into one process.  The product library is linked without a static symbol table (-s; the dynamic one, which is what a
 # caller binds to, stays): a change to the link alone, every object file is what it was.  The laboratory build keeps its table for
-# profiles and backtraces.
+# profiles and backtraces.  exports.map: only the public entry points are dynamic symbols (a change to the link alone as well).
 [ "$1" = "lab" ] && STRIP= || STRIP=-Wl,-s
-$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic $STRIP -o $OUT $objs
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -Wl,--version-script=exports.map $STRIP -o $OUT $objs
 echo "built $(readlink -f $OUT)"

@@ -20,6 +20,22 @@ struct FrameRec;
 
 struct DemodImage;                          // demod_host.cpp: host image of the tables + the device image's resolved pointers
 
+// Frame quality records (hfdl_gpu_frontend_quality_enable; quality.h): off = none, no launch.  One launch behind the burst decoder of
+// every demodulator launch, on its stream; a ring claimed like the PDU ring, its counts snapshot behind the launch like h_snap.
+struct FrameQuality {
+	static constexpr int CHUNK = 32;        // records a collection copies per wait on its stream (with symbols: 1.3 MB)
+	int ring = 0;
+	uint32_t taken = 0, dropped = 0;
+	DevArray<hfdl_gpu_frame_quality> d_recs;        // [ring]
+	DevArray<float2> d_syms;                // [ring][5040] with HFDL_GPU_QUALITY_SYMBOLS, else null
+	DevArray<int> d_counts;                 // [1] records produced, [2] frames dropped, [3] records taken by the host
+	PinnedBuf<int> h_snap;                  // [2][4]: d_counts as of the end of the newest launch of half 0 / 1
+	PinnedBuf<hfdl_gpu_frame_quality> h_recs;       // [CHUNK] bounce buffers of a collection
+	PinnedBuf<float2> h_syms;               // [CHUNK][5040]
+	Event ev_last;                          // recorded behind the newest quality launch and its snapshot
+	bool launched = false;
+};
+
 // Members in the order streams, memory, events (destroyed in reverse, frontend.h).  Nothing here waits for the collection stream when it
 // goes: ~hfdl_gpu_frontend() synchronises it with the front end's own streams, before any member of either is destroyed.
 struct Demod {
@@ -59,6 +75,8 @@ struct Demod {
 	// demodulator launch of the half in buffer 0 / 1 done (its decoder may start), the LAST launch of the half at [0]: the half is free
 	DoneEvent dm[2][PLAN_MAX_HALF];
 	Event ev_demod[3];                      // recorded behind the last burst decoder of a half, in turn (DemodOrder::decoded_event)
+	uint64_t halves_launched = 0;           // order.halves as of the newest launch_half(): equal = the newest half's ev_demod has been recorded
+	std::unique_ptr<FrameQuality> quality;  // null: off (its memory and its event go before the members above: nothing queued uses them then, quality_enable)
 
 	Demod();
 	~Demod();
@@ -86,6 +104,12 @@ struct Demod {
 	// never the old ones, so a reader never sees a counter rise and then run backwards.
 	int prepare_retune(hipStream_t st_b);
 	void enqueue_retune(int c, int32_t freq, hipStream_t st_b, hipStream_t st_d);
+	// Frame quality records.  quality_enable: ring = 0 turns them off; else a fresh, empty ring from the next launch queued on; either way
+	// it first waits for the quality launches queued so far, and an allocation that fails leaves everything as it was.  quality_read:
+	// the oldest records not taken yet that are KNOWN to be complete: it asks after the halves' last burst decoders (the quality launch
+	// and its snapshot sit in front of the event they carry) and believes the snapshot DemodOrder allows, never waiting for a kernel.
+	int quality_enable(int ring, bool symbols);
+	int quality_read(hfdl_gpu_frame_quality *out, float *symbols, int32_t max, int32_t *n, uint32_t *dropped, hipStream_t st);
 	int stats_all(hfdl_gpu_channel_stats *out, int n);
 	int tap(int what, int channel, const void **src, size_t *nfloats);
 	int stats(int channel, hfdl_gpu_channel_stats *out);
@@ -96,6 +120,7 @@ private:
 	int enqueue_demod(const DemodLaunch &p, const float2 *chan_out, const int *out_count, int nblk, hipStream_t st, hipEvent_t done, hipEvent_t start);
 	int enqueue_decode(const DemodLaunch &p, int half, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 	int collect_snapshot(int slot, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st);  // up to the end of the launch that wrote the slot
+	bool decoded(int back);                 // the last burst decoder of the newest half (0), the one before (1), before that (2) is found done
 };
 
 }  // namespace hfdl

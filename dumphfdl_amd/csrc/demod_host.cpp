@@ -11,6 +11,7 @@
 #include "demod_lds.h"
 #include "demod_tables.h"
 #include "planner.h"
+#include "quality.h"
 
 namespace hfdl {
 
@@ -135,6 +136,7 @@ int Demod::launch_half(const float2 *chan_out, const int *out_count, int nblk, i
 		if (int rc = enqueue_decode(p, half, st_d, k5_start, k5_stop)) return rc;
 	}
 	HIP_TRY(hipEventRecord(ev_demod[order.decoded_event(0)], st_d));      // (launches follow their hand-over: this half is the newest)
+	halves_launched = order.halves;
 	return 0;
 }
 
@@ -158,6 +160,16 @@ int Demod::enqueue_decode(const DemodLaunch &p, int half, hipStream_t st, hipEve
 {
 	launch_burst_decode(d_frames + (size_t)p.set * nch * frames_per_chan, d_counts, d_counts + 4 + p.counter, d_counts + 4 + p.zeroed, nch * frames_per_chan,
 			(const cf *)d_data.p, data_slots, img->t.scrambler, d_freqs, d_pdus, pdu_cap, st, start, stop);
+	// the frame quality records of the same frame queue: part of "the decoder of launch i" for DemodOrder's hazards 1 and 4 -- behind
+	// the burst decoder, in front of ev_dec and of the half's decoded event, so the queue, its counter and the data slots are guarded
+	// for it exactly as for the decoder's own reads; its ring's counts ride behind it as the PDU ring's do
+	if (FrameQuality *q = quality.get()) {
+		launch_frame_quality(d_frames + (size_t)p.set * nch * frames_per_chan, d_counts + 4 + p.counter, nch * frames_per_chan, (const cf *)d_data.p, data_slots,
+				img->t.c.psk_pts, d_freqs, q->d_counts, q->d_recs, (cf *)q->d_syms.p, q->ring, st);
+		HIP_TRY(hipMemcpyAsync(q->h_snap.p + 4 * half, q->d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipEventRecord(q->ev_last, st));
+		q->launched = true;
+	}
 	// what the ring holds once this launch is done, for a host that collects without draining the pipeline
 	HIP_TRY(hipMemcpyAsync(h_snap.p + 4 * half, d_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
 	if (order.own_decode) {
@@ -250,17 +262,19 @@ int Demod::collect_ready(bool wait, hfdl_gpu_pdu *out, int32_t max, int32_t *n, 
 	} else {
 		HIP_TRY(hipEventSynchronize(ev));
 	}
-	// A snapshot slot is written by its half's burst decoders' 16-byte copies: read only once the last of them is known to be done
-	// (ev_demod is recorded behind it).  "Not ready" is an answer, not an error to be found by a later check.
-	auto decoded = [&](int back) {
-		const int e = order.decoded_event(back);
-		const bool yes = e >= 0 && hipEventQuery(ev_demod[e]) == hipSuccess;
-		if (!yes) (void)hipGetLastError();
-		return yes;
-	};
 	const bool newer = decoded(1);
 	const int slot = order.snapshot_slot(newer, !newer && decoded(2));
 	return slot < 0 ? 0 : collect_snapshot(slot, out, max, n, st);
+}
+
+// A snapshot slot is written by its half's burst decoders' 16-byte copies: read only once the last of them is known to be done
+// (ev_demod is recorded behind it).  "Not ready" is an answer, not an error to be found by a later check.
+bool Demod::decoded(int back)
+{
+	const int e = order.decoded_event(back);
+	const bool yes = e >= 0 && hipEventQuery(ev_demod[e]) == hipSuccess;
+	if (!yes) (void)hipGetLastError();
+	return yes;
 }
 
 int Demod::collect_snapshot(int slot, hfdl_gpu_pdu *out, int32_t max, int32_t *n, hipStream_t st)
@@ -269,6 +283,73 @@ int Demod::collect_snapshot(int slot, hfdl_gpu_pdu *out, int32_t max, int32_t *n
 	const uint32_t d = (uint32_t)snap[2];
 	if ((int32_t)(d - dropped) > 0) dropped = d;       // monotone: an older snapshot never takes the count back
 	return take((unsigned)snap[1], out, max, n, st);
+}
+
+// ---------------------------------------------------------------- frame quality records
+
+int Demod::quality_enable(int ring, bool symbols)
+{
+	std::unique_ptr<FrameQuality> q;
+	if (ring > 0) {
+		q = std::make_unique<FrameQuality>();
+		const size_t chunk = (size_t)std::min(ring, FrameQuality::CHUNK);
+		CREATE_TRY(q->d_recs.alloc((size_t)ring));
+		if (symbols) CREATE_TRY(q->d_syms.alloc((size_t)ring * MAX_DATA_SYMBOLS));
+		CREATE_TRY(q->d_counts.alloc(4));
+		CREATE_TRY(q->h_snap.alloc(8));
+		CREATE_TRY(q->h_recs.alloc(chunk));
+		if (symbols) CREATE_TRY(q->h_syms.alloc(chunk * MAX_DATA_SYMBOLS));
+		CREATE_TRY(q->ev_last.create(EV_NO_TIMING));
+		CREATE_TRY(hipMemsetAsync(q->d_counts, 0, sizeof(int) * 4, st_collect));
+		CREATE_TRY(hipStreamSynchronize(st_collect));
+		std::memset(q->h_snap.p, 0, sizeof(int) * 8);
+		q->ring = ring;
+	}
+	// the old ring goes once nothing queued writes into it any more: wait for the quality launches queued so far, nothing else
+	if (quality && quality->launched) (void)hipEventSynchronize(quality->ev_last);
+	quality = std::move(q);
+	return 0;
+}
+
+int Demod::quality_read(hfdl_gpu_frame_quality *out, float *symbols, int32_t max, int32_t *n, uint32_t *dropped_out, hipStream_t st)
+{
+	FrameQuality &q = *quality;
+	*n = 0;
+	// Which snapshot may be believed: the newest half's own if its last decoder has been queued and is found done (after a sync, a
+	// draining poll: everything); else what a poll that leaves the pipeline running reads (DemodOrder::snapshot_slot).  A slot no
+	// quality launch has written holds zeros.
+	int slot;
+	if (order.newest >= 0 && halves_launched == order.halves && decoded(0)) slot = order.newest;
+	else {
+		const bool newer = decoded(1);
+		slot = order.snapshot_slot(newer, !newer && decoded(2));
+	}
+	if (slot >= 0) {
+		const volatile int *snap = q.h_snap.p + 4 * slot;
+		const uint32_t d = (uint32_t)snap[2];
+		if ((int32_t)(d - q.dropped) > 0) q.dropped = d;      // monotone: an older snapshot never takes the count back
+		const int32_t avail = (int32_t)((unsigned)snap[1] - q.taken);      // signed: a stale snapshot yields nothing
+		const unsigned cnt = avail <= 0 || max <= 0 ? 0u : (unsigned)std::min(std::min(avail, q.ring), max);
+		// ring entries [taken, taken + cnt) in pieces that neither wrap nor exceed the bounce buffers, copied on the collection stream
+		// beside whatever kernels are running
+		for (unsigned done = 0; done < cnt;) {
+			const unsigned first = (q.taken + done) % (unsigned)q.ring;
+			const unsigned n1 = std::min(std::min(cnt - done, (unsigned)q.ring - first), (unsigned)FrameQuality::CHUNK);
+			HIP_TRY(hipMemcpyAsync(q.h_recs.p, q.d_recs + first, sizeof(hfdl_gpu_frame_quality) * n1, hipMemcpyDeviceToHost, st_collect));
+			if (symbols) HIP_TRY(hipMemcpyAsync(q.h_syms.p, q.d_syms + (size_t)first * MAX_DATA_SYMBOLS, sizeof(float2) * MAX_DATA_SYMBOLS * n1, hipMemcpyDeviceToHost, st_collect));
+			HIP_TRY(hipStreamSynchronize(st_collect));
+			std::memcpy(out + done, q.h_recs.p, sizeof(hfdl_gpu_frame_quality) * n1);
+			if (symbols) std::memcpy(symbols + (size_t)done * 2 * MAX_DATA_SYMBOLS, q.h_syms.p, sizeof(float2) * MAX_DATA_SYMBOLS * n1);
+			done += n1;
+		}
+		if (cnt) {
+			q.taken += cnt;
+			HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(q.d_counts + 3), (int)q.taken, 1, st));    // ordered after the launches already queued
+		}
+		*n = (int32_t)cnt;
+	}
+	if (dropped_out) *dropped_out = q.dropped;
+	return 0;
 }
 
 int Demod::tap(int what, int channel, const void **src, size_t *nfloats)

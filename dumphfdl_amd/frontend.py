@@ -46,6 +46,14 @@ class ChannelStats(C.Structure):
                 ("train_bits_bad", C.c_uint32), ("train_bits_total", C.c_uint32)]
 
 
+class FrameQuality(C.Structure):
+    _fields_ = [("sample_index", C.c_uint64), ("channel", C.c_int32), ("freq", C.c_int32), ("mode", C.c_int32), ("bitmask_lsb", C.c_int32),
+                ("nsym", C.c_int32), ("segments", C.c_int32), ("train_bits_bad", C.c_int32), ("train_bits_total", C.c_int32),
+                ("freq_err_hz", C.c_float), ("rssi_db", C.c_float), ("noise_floor_db", C.c_float),
+                ("sym_power", C.c_float), ("err_power", C.c_float), ("err_max", C.c_float), ("gain_re", C.c_float), ("gain_im", C.c_float),
+                ("seg_err_power", C.c_float * 168)]
+
+
 class SpectrumRow(C.Structure):
     _fields_ = [("row", C.c_uint64), ("first_block", C.c_uint64), ("blocks", C.c_uint32), ("pad", C.c_uint32)]
 
@@ -81,6 +89,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_spectrum_history", "hfdl_gpu_frontend_spectrum_row_close", "hfdl_gpu_frontend_spectrum_rows",
     "hfdl_gpu_frontend_export_enable", "hfdl_gpu_frontend_export_read",
     "hfdl_gpu_frontend_retune_channel",
+    "hfdl_gpu_frontend_quality_enable", "hfdl_gpu_frontend_quality_read", "hfdl_gpu_frame_quality_batch",
 ]
 
 
@@ -90,6 +99,8 @@ SPECTRUM_HANN, SPECTRUM_MAXHOLD = 1, 2     # HFDL_GPU_SPECTRUM_*
 SPECTRUM_ROWS_MAX = 1024   # HFDL_GPU_SPECTRUM_ROWS_MAX
 EXPORT_CF32, EXPORT_CS16 = 0, 1            # HFDL_GPU_EXPORT_*
 EXPORT_RING_MAX = 4096     # HFDL_GPU_EXPORT_RING_MAX
+QUALITY_SYMBOLS = 1        # HFDL_GPU_QUALITY_SYMBOLS
+QUALITY_SEGMENTS_MAX, QUALITY_SYMBOLS_MAX, QUALITY_RING_MAX = 168, 5040, 65536     # HFDL_GPU_QUALITY_*
 
 # what include/hfdl_gpu_lab.h adds in the laboratory build (libhfdl_gpu_lab.so)
 LAB_EXPORTS = ["hfdl_gpu_lab_fold_variant_count", "hfdl_gpu_lab_fold_variant_describe", "hfdl_gpu_lab_fold_variant_probe", "hfdl_gpu_lab_stream_read_probe",
@@ -206,6 +217,9 @@ def _bind(L):
     L.hfdl_gpu_frontend_export_read.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int]
     L.hfdl_gpu_frontend_retune_channel.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.hfdl_gpu_frontend_quality_enable.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+    L.hfdl_gpu_frontend_quality_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int]
+    L.hfdl_gpu_frame_quality_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     return L
 
 
@@ -547,6 +561,33 @@ class Frontend:
         _check(self._L.hfdl_gpu_frontend_retune_channel(self._h, int(channel), int(freq_hz)), self._L)
         self.freqs[channel] = int(freq_hz)
 
+    def quality_enable(self, ring_frames=4096, symbols=False):
+        """Frame quality records (include/hfdl_gpu.h): from the next demodulator launch queued on, one record per finished frame in a
+        ring of ring_frames (2 .. QUALITY_RING_MAX) records; symbols=True keeps each frame's data symbols too.  ring_frames = 0: off.
+        Calling it again starts over with an empty ring."""
+        _check(self._L.hfdl_gpu_frontend_quality_enable(self._h, int(ring_frames), QUALITY_SYMBOLS if symbols else 0), self._L)
+        self._quality = (int(ring_frames), bool(symbols))
+
+    def quality_read_raw(self, max_frames=None, wait=False, out=None):
+        """The C structs as the library hands them over: (ctypes array of hfdl_gpu_frame_quality, symbols [max_frames, 5040] complex64 or
+        None, count, dropped).  out = (array, symbols) of an earlier call: filled again instead of allocating (a caller that reads after
+        every push)."""
+        ring, with_sym = getattr(self, "_quality", (0, False))
+        cap = ring if max_frames is None else int(max_frames)
+        if out is None:
+            out = ((FrameQuality * max(cap, 1))(), np.zeros((max(cap, 0), QUALITY_SYMBOLS_MAX), np.complex64) if with_sym else None)
+        buf, sym = out
+        n, dropped = C.c_int32(0), C.c_uint32(0)
+        _check(self._L.hfdl_gpu_frontend_quality_read(self._h, buf, _p(sym) if sym is not None else None, cap, C.byref(n), C.byref(dropped), int(wait)), self._L)
+        return buf, sym, n.value, dropped.value
+
+    def quality_read(self, max_frames=None, wait=False):
+        """(records as dicts, symbols [n, 5040] complex64 with zeros past nsym -- None unless enabled with symbols=True --, frames
+        dropped since the enable).  wait=False never waits for a kernel stream: only records known to be complete; wait=True syncs
+        first.  A record belongs to the PDU with the same (channel, sample_index)."""
+        buf, sym, n, dropped = self.quality_read_raw(max_frames, wait)
+        return [quality_to_dict(buf[i]) for i in range(n)], (sym[:n] if sym is not None else None), dropped
+
     def close(self):
         if self._h:
             self._L.hfdl_gpu_frontend_destroy(self._h)
@@ -652,6 +693,25 @@ def burst_decode(symbol_list, modes, bitmask_lsb=None, device=0):
     lens = np.zeros(n, np.int32)
     _check(load().hfdl_gpu_burst_decode(device, _p(sym), _p(modes), _p(bm), n, _p(octets), _p(lens)))
     return [bytes(octets[i, :lens[i]]) for i in range(n)]
+
+
+def quality_to_dict(q):
+    """A hfdl_gpu_frame_quality as a dict; seg_err_power as a float32 array of `segments` entries, `raw` = the struct's 744 bytes."""
+    d = {k: getattr(q, k) for k, _ in FrameQuality._fields_ if k != "seg_err_power"}
+    d["seg_err_power"] = np.frombuffer(bytes(q), np.float32, QUALITY_SEGMENTS_MAX, FrameQuality.seg_err_power.offset).copy()
+    d["raw"] = bytes(q)
+    return d
+
+
+def frame_quality(symbol_list, modes, device=0):
+    """The frame quality figures of a batch of frames by the device function of the front end's records (hfdl_gpu_frame_quality_batch);
+    symbol_list[i] = the segments*30 equalised data symbols of frame i.  One dict per frame."""
+    n = len(symbol_list)
+    modes = np.ascontiguousarray(modes, dtype=np.int32)
+    sym = np.ascontiguousarray(np.concatenate([np.asarray(s, np.complex64) for s in symbol_list]), dtype=np.complex64)
+    out = (FrameQuality * n)()
+    _check(load().hfdl_gpu_frame_quality_batch(device, _p(sym), _p(modes), n, out))
+    return [quality_to_dict(out[i]) for i in range(n)]
 
 
 def lab_burst_soft(symbol_list, modes, bitmask_lsb=None, device=0):

@@ -18,8 +18,11 @@
 /* A GPU library without the entry point (the CPU stand-in of the tests, an older build) leaves the symbol null: it cannot retune, and a
  * request is refused. */
 #pragma weak hfdl_gpu_frontend_retune_channel
+/* ... and the frame quality records likewise: a frame log asked of such a library is refused when the front end is created */
+#pragma weak hfdl_gpu_frontend_quality_enable
+#pragma weak hfdl_gpu_frontend_quality_read
 
-/* The two optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
+/* The optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
  * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
 struct spectrum_settings { const char *path; int32_t bins, interval_s; int hann; };                         /* path NULL = off */
 struct iq_export_settings { const char *dir; const int32_t *freqs; int32_t nfreqs; int format; float scale; };  /* dir NULL = off */
@@ -58,6 +61,7 @@ struct gpu_fft_block {
 	hfdl_gpu_geometry geo;
 	struct spectrum_settings spectrum;       /* as set when fft_create() ran */
 	struct iq_export_settings iqx;
+	char *frame_log;                         /* path, NULL = off */
 };
 
 static int g_device = 0;
@@ -81,6 +85,14 @@ int hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t n
 	const struct iq_export_settings given = { dir, freqs, nfreqs, format, scale };
 	iq_export_settings_free(&g_iqx);
 	g_iqx = iq_export_settings_copy(&given);
+	return 0;
+}
+
+static char *g_frame_log;
+int hfdl_frontend_set_frame_log(const char *path)
+{
+	free(g_frame_log);
+	g_frame_log = path ? strdup(path) : NULL;
 	return 0;
 }
 
@@ -397,6 +409,16 @@ struct iq_export {
 	uint64_t lost;                   /* blocks the ring overwrote before they could be written: named once, counted, the total reported at the end */
 };
 
+/* Frame log: one text line per frame from the device's frame quality records, collected FLOG_CHUNK at a time (wait = 0 after every
+ * collection of PDUs: never waits for a kernel stream; wait = 1 at shutdown: everything). */
+#define FLOG_CHUNK 16
+#define FLOG_RING 4096
+struct frame_log {
+	FILE *file;                      /* NULL = off */
+	hfdl_gpu_frame_quality *recs;    /* [FLOG_CHUNK] */
+	uint32_t dropped;                /* frames the device's ring dropped because the log fell behind */
+};
+
 struct fe_thread {
 	struct block *block;
 	struct gpu_fft_block *fb;
@@ -419,6 +441,7 @@ struct fe_thread {
 	double grace;
 	struct spectrum_csv csv;
 	struct iq_export iqx;
+	struct frame_log flog;
 	double t_first;
 	struct hfdl_run_stats rs;        /* where this thread's time went and what it moved; published once, at shutdown */
 };
@@ -428,6 +451,18 @@ static void fail(struct fe_thread *t, const char *text)
 	fprintf(stderr, "GPU front end: %s\n", text);
 	do_exit = 1;
 	t->ok = false;
+}
+
+/* start of frame = A2 detection - (prekey + 2 A) symbols (src/hfdl.c:657-660), on the stream's sample clock: a PDU's timestamp and
+ * the time of its frame's line in the frame log */
+static struct timeval frame_time(const struct fe_thread *t, uint64_t sample_index)
+{
+	const double ts = (double)t->t0.tv_sec + 1e-6 * (double)t->t0.tv_usec + (double)sample_index / (HFDL_SYMBOL_RATE * SPS)
+		- (448.0 + 2 * 127.0) / HFDL_SYMBOL_RATE;
+	struct timeval tv;
+	tv.tv_sec = (time_t)floor(ts);
+	tv.tv_usec = (suseconds_t)((ts - floor(ts)) * 1e6);
+	return tv;
 }
 
 static void push_pdu(struct fe_thread *t, const hfdl_gpu_pdu *p)
@@ -444,11 +479,7 @@ static void push_pdu(struct fe_thread *t, const hfdl_gpu_pdu *p)
 	hm->noise_floor = p->noise_floor_db;
 	hm->bit_rate = p->bit_rate;
 	hm->slot = p->slot;
-	/* start of frame = A2 detection - (prekey + 2 A) symbols (src/hfdl.c:657-660), on the stream's sample clock */
-	double ts = (double)t->t0.tv_sec + 1e-6 * (double)t->t0.tv_usec + (double)p->sample_index / (HFDL_SYMBOL_RATE * SPS)
-		- (448.0 + 2 * 127.0) / HFDL_SYMBOL_RATE;
-	m->rx_timestamp.tv_sec = (time_t)floor(ts);
-	m->rx_timestamp.tv_usec = (suseconds_t)((ts - floor(ts)) * 1e6);
+	m->rx_timestamp = frame_time(t, p->sample_index);
 	uint8_t *copy = hfdl_xcalloc((size_t)p->len ? (size_t)p->len : 1, 1);
 	memcpy(copy, p->octets, (size_t)p->len);
 	pdu_decoder_queue_push(m, octet_string_new(copy, (size_t)p->len), 0);
@@ -620,6 +651,55 @@ static void write_iq_export(hfdl_gpu_frontend *fe, struct iq_export *x, int wait
 		x->next = after;
 		if (n < IQX_CHUNK) return;
 	}
+}
+
+/* One line per frame: time of the frame's start (the PDU's timestamp), frequency, mode, slot, MER = -10 log10(err_power) in dB, mean
+ * symbol power, |gain|, the gain's phase in degrees, the worst data segment and its MER.  The figures are decision-directed
+ * (include/hfdl_gpu.h): at low SNR they overstate the quality. */
+static void write_frame_log(struct fe_thread *t, int wait)
+{
+	struct frame_log *g = &t->flog;
+	int32_t n = 0;
+	do {
+		if (hfdl_gpu_frontend_quality_read(t->fe, g->recs, NULL, FLOG_CHUNK, &n, &g->dropped, wait) != 0) {
+			fprintf(stderr, "frame log: %s\n", hfdl_gpu_last_error());
+			return;
+		}
+		for (int32_t i = 0; i < n; i++) {
+			const hfdl_gpu_frame_quality *q = &g->recs[i];
+			const struct timeval tv = frame_time(t, q->sample_index);
+			int32_t worst = 0;
+			for (int32_t s = 1; s < q->segments && s < HFDL_GPU_QUALITY_SEGMENTS_MAX; s++)
+				if (q->seg_err_power[s] > q->seg_err_power[worst]) worst = s;
+			fprintf(g->file, "FRAME ts=%ld.%06ld freq=%d mode=%d slot=%c mer_db=%.2f sym_power=%.4f gain=%.4f gain_phase_deg=%.2f worst_segment=%d worst_mer_db=%.2f\n",
+					(long)tv.tv_sec, (long)tv.tv_usec, q->freq, q->mode, q->segments == 72 ? 'S' : 'D', -10.0 * log10((double)q->err_power),
+					(double)q->sym_power, hypot((double)q->gain_re, (double)q->gain_im), atan2((double)q->gain_im, (double)q->gain_re) * (180.0 / M_PI),
+					worst, -10.0 * log10((double)q->seg_err_power[worst]));
+		}
+		wait = 0;                                /* the sync has been done */
+	} while (n == FLOG_CHUNK);
+	fflush(g->file);
+}
+
+static void frame_log_close(struct frame_log *g)
+{
+	if (g->dropped > 0) fprintf(stderr, "frame log: %u frames have no line (the log fell behind the device's ring)\n", g->dropped);
+	if (g->file != NULL) fclose(g->file);
+	free(g->recs);
+	memset(g, 0, sizeof(*g));
+}
+
+static int frame_log_open(struct fe_thread *t)
+{
+	struct frame_log *g = &t->flog;
+	if ((g->file = fopen(t->fb->frame_log, "w")) == NULL) { fprintf(stderr, "frame log: cannot open %s\n", t->fb->frame_log); return -1; }
+	g->recs = hfdl_xcalloc(FLOG_CHUNK, sizeof(*g->recs));
+	if (hfdl_gpu_frontend_quality_enable(t->fe, FLOG_RING, 0) != 0) {
+		fprintf(stderr, "frame log: %s\n", hfdl_gpu_last_error());
+		frame_log_close(g);
+		return -1;
+	}
+	return 0;
 }
 
 static void iq_export_close(struct iq_export *x)
@@ -897,7 +977,8 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 	t->need = t->ok ? (size_t)fb->geo.input_size : 1;
 	t->gfmt = gpu_format_of(hfdl_ring_format(t->ring->buf));
 	if (t->ok && ((fb->spectrum.path != NULL && spectrum_csv_open(t) != 0)
-			|| (fb->iqx.dir != NULL && iq_export_open(t->fe, fb, slots, t->nch, &t->iqx) != 0))) {
+			|| (fb->iqx.dir != NULL && iq_export_open(t->fe, fb, slots, t->nch, &t->iqx) != 0)
+			|| (fb->frame_log != NULL && frame_log_open(t) != 0))) {
 		do_exit = 1;
 		t->ok = false;
 	}
@@ -925,6 +1006,7 @@ static void frontend_teardown(struct fe_thread *t)
 		const double t_last = now_s();
 		spectrum_csv_close(t);
 		if (t->iqx.files != NULL) write_iq_export(t->fe, &t->iqx, 1);
+		if (t->flog.file != NULL && t->flog.recs != NULL) write_frame_log(t, 1);
 		publish_counters(t->fe, t->stats, (int32_t)t->nch);
 		/* requests that never came due, or came in after the last push, are not the next front end's */
 		pthread_mutex_lock(&g_retune_lock);
@@ -944,6 +1026,7 @@ static void frontend_teardown(struct fe_thread *t)
 	block_connection_one2many_shutdown(t->block->producer.out);
 	if (t->fe) hfdl_gpu_frontend_destroy(t->fe);
 	iq_export_close(&t->iqx);
+	frame_log_close(&t->flog);
 	free(t->bounce);
 	free(t->pdus);
 	free(t->stats);
@@ -992,6 +1075,7 @@ static void *frontend_thread(void *ctx)
 		const double tw2 = now_s();
 		t.rs.push_s += tw2 - tw1;
 		deliver_pdus(&t, false);
+		if (t.flog.file != NULL) write_frame_log(&t, 0);
 		const double tw3 = now_s();
 		t.rs.collect_s += tw3 - tw2;
 		release_copied(&t, false);               /* nothing is waited for here */
@@ -1019,6 +1103,12 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 		free(fb);
 		return NULL;
 	}
+	if (g_frame_log != NULL && (hfdl_gpu_frontend_quality_enable == NULL || hfdl_gpu_frontend_quality_read == NULL)) {
+		fprintf(stderr, "frame log: this GPU library has no frame quality records\n");
+		free(fb);
+		return NULL;
+	}
+	fb->frame_log = g_frame_log ? strdup(g_frame_log) : NULL;
 	fb->decimation = decimation;
 	fb->transition_bw = transition_bw;
 	fb->device = g_device;
@@ -1038,5 +1128,6 @@ void fft_destroy(struct block *fft_block)
 	struct gpu_fft_block *fb = container_of(fft_block, struct gpu_fft_block, block);
 	spectrum_settings_free(&fb->spectrum);
 	iq_export_settings_free(&fb->iqx);
+	free(fb->frame_log);
 	free(fb);
 }

@@ -5,7 +5,7 @@
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
  *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
- *               [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
+ *               [--frame-log FILE] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -17,6 +17,9 @@
  *               (hfdl_frontend_set_spectrum, include/hfdl_host.h); --spectrum-hann: Hann instead of the rectangular window.
  * --iq-export-dir DIR    append the baseband I/Q of every channel of the list to DIR/<freq_hz>.cf32 (or .cs16 = int16 of rint(v * X),
  *               X = 32767 by default), one file per channel (hfdl_frontend_set_iq_export, include/hfdl_host.h); DIR must exist.
+ *
+ * --frame-log FILE      one text line per received frame to FILE (hfdl_frontend_set_frame_log, include/hfdl_host.h): the frame's time
+ *               (its PDU's ts) and frequency, mode, slot, MER in dB, symbol power, gain magnitude and phase, the worst data segment.
  *
  * --retune SECONDS:OLD_KHZ:NEW_KHZ   move the channel on OLD_KHZ to NEW_KHZ before the first block whose first sample lies at or after
  *               SECONDS of signal (hfdl_frontend_schedule_retune, include/hfdl_host.h); repeatable, at most 64.  A request that is
@@ -93,7 +96,7 @@ int main(int argc, char **argv)
 	int nfreq = 0, shard_rank = 0, shard_world = 1;
 	const char *spec_path = NULL;
 	int spec_bins = 1024, spec_interval = 1, spec_hann = 0;
-	const char *iqx_dir = NULL;
+	const char *iqx_dir = NULL, *frame_log = NULL;
 	int iqx_format = 0;                  /* 0 = cf32, 1 = cs16 */
 	float iqx_scale = 32767.f;
 	for (int i = 1; i < argc; i++) {
@@ -116,6 +119,7 @@ int main(int argc, char **argv)
 			iqx_format = !strcmp(f, "cs16");
 		}
 		else if (!strcmp(argv[i], "--iq-export-scale") && i + 1 < argc) iqx_scale = (float)atof(argv[++i]);
+		else if (!strcmp(argv[i], "--frame-log") && i + 1 < argc) frame_log = argv[++i];
 		else if (!strcmp(argv[i], "--retune") && i + 1 < argc) {
 			double at;
 			int32_t old_hz, new_hz;
@@ -170,8 +174,13 @@ int main(int argc, char **argv)
 		fprintf(stderr, "--iq-export-scale wants a finite number above 0\n");
 		return 1;
 	}
+	hfdl_frontend_set_frame_log(frame_log);
 	struct block *fft = fft_create(decimation, tbw);
-	if (fft == NULL) return 1;
+	if (fft == NULL) {               /* (the reason is on stderr) */
+		input_destroy(input);
+		input_cfg_destroy(cfg);
+		return 1;
+	}
 	hfdl_init_globals();
 	struct block **channels = calloc((size_t)nfreq, sizeof(*channels));
 	for (int i = 0; i < nfreq; i++) {

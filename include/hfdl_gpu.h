@@ -411,6 +411,53 @@ int  hfdl_gpu_frontend_export_read(hfdl_gpu_frontend *fe, uint64_t from_block, i
  * HFDL_GPU_ENOMEM of the first call, leaves the front end as it was.  One channel per call. */
 int  hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t channel, int32_t new_freq_hz);
 
+/* Frame quality records (off by default: nothing is allocated or launched): how well a frame was received, measured on the equalised
+ * data symbols the burst decoder sliced -- rssi_db, noise_floor_db and freq_err_hz of a PDU describe the channel in front of the
+ * equaliser.  Behind the burst decoder of every demodulator launch, on its stream, one more kernel makes a record for every frame
+ * of the launch's frame queue -- also for a frame whose PDU was dropped from a full PDU ring -- in a ring of ring_frames records in HBM.  A
+ * record belongs to the PDU with the same (channel, sample_index); the order of the records of one launch is unspecified.  With
+ * p[i] the constellation point nearest to data symbol x[i] (the decoder's own slicer and table) and e[i] = x[i] - p[i], in fp32:
+ *   seg_err_power[s]   mean |e|^2 over the 30 symbols of data segment s, s < segments; +0.0 above (a frame lasts 2.3 - 4.2 s and fades)
+ *   err_power          mean of seg_err_power[0 .. segments); MER in dB = -10 log10(err_power)
+ *   err_max            max |e|^2;   sym_power   mean |x|^2;   gain_re + j gain_im   mean x conj(p)
+ * summed in a fixed order (dumphfdl_amd/csrc/quality.h): bit-identical from run to run and independent of how the caller pushes,
+ * polls or batches.  The figures are DECISION-DIRECTED: below about the SNR where the slicer starts to err, a wrong decision counts
+ * the distance to the wrong, nearer point, err_power saturates and overstates the quality.  sym_power - |gain|^2 is the gain- and
+ * phase-corrected error power for who wants it.  The symbols are taken as stored, in front of the descrambler: descrambler and
+ * bitmask_lsb multiply a symbol by +-1, which maps every HFDL constellation onto itself and changes none of the figures. */
+#define HFDL_GPU_QUALITY_SYMBOLS       1u     /* keep each frame's data symbols too */
+#define HFDL_GPU_QUALITY_SEGMENTS_MAX  168
+#define HFDL_GPU_QUALITY_SYMBOLS_MAX   5040
+#define HFDL_GPU_QUALITY_RING_MAX      65536
+typedef struct {
+	uint64_t sample_index;                  /* = the PDU's */
+	int32_t  channel, freq, mode, bitmask_lsb;
+	int32_t  nsym, segments;
+	int32_t  train_bits_bad, train_bits_total;
+	float    freq_err_hz, rssi_db, noise_floor_db;    /* bit for bit the PDU's */
+	float    sym_power, err_power, err_max, gain_re, gain_im;
+	float    seg_err_power[HFDL_GPU_QUALITY_SEGMENTS_MAX];
+} hfdl_gpu_frame_quality;                   /* 744 bytes */
+/* ring_frames = 0: off, the buffers freed.  ring_frames = 2 .. HFDL_GPU_QUALITY_RING_MAX: on, from the next demodulator launch
+ * QUEUED (frames of halves handed to the demodulator before the call get no record); the call closes no half and drains nothing.
+ * flags: HFDL_GPU_QUALITY_SYMBOLS adds a second ring of ring_frames x 5040 cf32 (40 320 bytes a frame).  A frame that finds the ring
+ * full is dropped and counted, never left half-written, and leaves no hole; reading makes room.  Calling it again starts over with
+ * an empty ring and a dropped count of 0 (it waits for the quality launches queued so far before the old ring goes).
+ * HFDL_GPU_EINVAL (null handle, unknown flag, ring_frames outside 0, 2 .. 65536) / HFDL_GPU_ERANGE (rings above 1 GiB) are checked
+ * before any device work; HFDL_GPU_ENOMEM leaves the feature as it was. */
+int  hfdl_gpu_frontend_quality_enable(hfdl_gpu_frontend *fe, int32_t ring_frames, uint32_t flags);
+/* The oldest records not read yet, at most max_frames: out[i], and with `symbols` (may be NULL; HFDL_GPU_EINVAL if given without
+ * HFDL_GPU_QUALITY_SYMBOLS) the frame's data symbols at symbols[i * 2 * 5040 ..], re, im, zeros past nsym; *n = records written,
+ * *dropped (may be NULL) = frames dropped since the enable.  wait = 0: only records known to be complete -- those of launches whose
+ * burst decoders are known to be done, as for hfdl_gpu_frontend_poll_pdus_ready(.., 2); the call asks (hipEventQuery) and never
+ * waits for a kernel stream.  After a sync or a draining poll that is every record of every frame decoded so far.  wait != 0: first
+ * does what hfdl_gpu_frontend_sync() does.  The records are copied on the collection stream through a page-locked buffer beside
+ * the kernels in flight.  HFDL_GPU_EINVAL for a null n, max_frames < 0 or a null out with max_frames > 0 is returned before the
+ * handle is looked at and nothing is written; a null handle, the feature off or `symbols` without the flag likewise before any
+ * device work. */
+int  hfdl_gpu_frontend_quality_read(hfdl_gpu_frontend *fe, hfdl_gpu_frame_quality *out, float *symbols,
+		int32_t max_frames, int32_t *n, uint32_t *dropped, int wait);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */
@@ -468,6 +515,11 @@ int  hfdl_gpu_viterbi27(int device, const uint8_t *soft, int32_t nbits, int32_t 
  * bitmask bit per frame; octets = nframes * HFDL_GPU_PDU_MAX_OCTETS, lens[nframes] */
 int  hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb,
 		int32_t nframes, uint8_t *octets, int32_t *lens);
+/* the frame quality figures (hfdl_gpu_frame_quality above) of a batch, by the device function of the front end's records: symbols
+ * and modes as for hfdl_gpu_burst_decode; out[nframes].  mode, nsym, segments and the five figures with seg_err_power are filled;
+ * what only a front end knows (sample_index, channel, freq, bitmask_lsb, the training counts, the three channel fields) is 0. */
+int  hfdl_gpu_frame_quality_batch(int device, const float *symbols, const int32_t *modes, int32_t nframes,
+		hfdl_gpu_frame_quality *out);
 
 /* decimating_shift_addition_cc(input, output, input_size, decimating_shift_addition_init(rate, decimation), decimation, status)
  * (src/libcsdr_gpl.c:26-74): out[k] = in[remain + decimation k] e^{j phi_k} with the reference's fp32 phasor recurrence; the

@@ -214,6 +214,15 @@ int           hfdl_frontend_set_spectrum(const char *path, int32_t bins, int32_t
  * channel frequencies in Hz as registered with hfdl_channel_create(); nfreqs = 0 selects every registered channel.  scale: format 1
  * only, finite and > 0.  dir NULL: off.  Returns 0, or -1 for bad arguments. */
 int           hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs, int32_t nfreqs, int format, float scale);
+/* Frame log of the front end created by the next fft_create() (include/hfdl_gpu.h, "Frame quality records"); not in the reference.
+ * The front-end thread reads the device's records without waiting after every collection of PDUs, and once more, waiting, after the
+ * final drain, and writes one text line per frame to `path` (created or truncated when the front end starts):
+ *   FRAME ts=<the PDU's timestamp> freq=<Hz> mode=<0..7> slot=<S|D> mer_db=<-10 log10(err_power)> sym_power=.. gain=<|gain|>
+ *         gain_phase_deg=.. worst_segment=<index> worst_mer_db=<that data segment's MER>
+ * The figures are decision-directed: below about the SNR where the slicer starts to err they overstate the quality.  Frames the
+ * device's ring dropped because the log fell behind are counted on stderr when the front end stops.  path NULL: off.  Returns 0.  With a
+ * GPU library that lacks the records, fft_create() fails with a message on stderr. */
+int           hfdl_frontend_set_frame_log(const char *path);
 /* Retune a channel of the running front end (include/hfdl_gpu.h, hfdl_gpu_frontend_retune_channel); not in the reference, which is
  * restarted to follow the ground stations' frequency changes.  Callable from any thread: the request old_freq -> new_freq (Hz) joins a
  * list (at most 64 waiting) that the front-end thread applies between two pushes -- blocks pushed before keep old_freq in their PDUs,
