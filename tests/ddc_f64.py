@@ -152,6 +152,15 @@ def channel_plan(oracle, fs, cf, freq):
     return d, taps.astype(np.complex128)
 
 
+def channel_plan_f64(fs, cf, freq):
+    """The same pair with nothing borrowed: the record and the taps of tests/ddc_design_f64.py, written from the definition (the taps in
+    the form that carries the reference's fp32 phase register and normalising sum; `nco_rate` is the fp32 word, as in channel_plan)."""
+    import ddc_design_f64 as D
+    plan = D.channel(fs, cf, freq)
+    plan.nco_rate = plan.nco_rate32
+    return plan, D.channel_taps(fs, cf, freq)["phase32+sum32"]
+
+
 def alias_tone_offset(fs, cf, freq, all_freqs, pre, margin=0.3):
     """A frequency (Hz from the receiver's centre) on an alias of the channel centre, f0 + k fs / pre with k != 0, inside +-fs / 2 and at
     least margin * fs / pre away from every channel's centre (a channel's pass band is +-fs / (4 pre) wide), or None if pre == 1."""
