@@ -145,7 +145,11 @@ void hfdl_gpu_host_free(void *ptr);
 /* ---- whole front end ---- */
 
 /* frequencies in Hz as in hfdl_channel_create(); decimation / transition_bw are derived exactly as
- * main() does (src/main.c:699-704): compute_fft_decimation_rate(fs, 5400), 250 Hz / fs. */
+ * main() does (src/main.c:699-704): compute_fft_decimation_rate(fs, 5400), 250 Hz / fs.
+ * sample_rate >= 5400, as the reference's main() asks.  A receiver below 10 800 sps (decimation 1) is accepted as the reference
+ * accepts it and, there as here, decodes nothing: with pre_decimation = post_decimation = 1 the reference's bin arithmetic leaves
+ * its channel half the channel's own sample rate off (the output times (-1)^k), which this library reproduces (oracle/PINNING.md
+ * section 3).  From 10 800 sps up channels decode. */
 int  hfdl_gpu_frontend_create(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t centerfreq,
 		const int32_t *freqs, int32_t nch);
 void hfdl_gpu_frontend_destroy(hfdl_gpu_frontend *fe);

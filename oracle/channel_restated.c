@@ -622,6 +622,8 @@ void orc_channel_destroy(orc_channel *c)
 
 const orc_ddc *orc_channel_ddc(const orc_channel *c) { return &c->ddc; }
 
+void orc_channel_nco(const orc_channel *c, orc_nco_state *s) { *s = c->nco; }
+
 void orc_channel_counters(const orc_channel *c, uint32_t out[4], float *noise_floor, int *framer_state)
 {
 	out[0] = c->cnt_a2_found; out[1] = c->cnt_m1_found; out[2] = c->cnt_m1_not_found; out[3] = c->cnt_frames;

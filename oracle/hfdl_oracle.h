@@ -172,6 +172,8 @@ orc_channel *orc_channel_create(int32_t sample_rate, int32_t decimation, float t
 		int32_t centerfreq, int32_t frequency, int want_channelizer);  /* src/hfdl.c:468-534 */
 void orc_channel_destroy(orc_channel *c);
 const orc_ddc *orc_channel_ddc(const orc_channel *c);
+/* what the decimator carries into the next block (shift_addition_cc's return, src/libcsdr_gpl.c:41-74) */
+void orc_channel_nco(const orc_channel *c, orc_nco_state *s);
 const orc_cf *orc_channel_taps(const orc_channel *c);
 /* StatsD counters of the hot path (src/hfdl.c:818,828,840) + noise floor (linear) + framer state */
 void orc_channel_counters(const orc_channel *c, uint32_t out[4], float *noise_floor, int *framer_state);

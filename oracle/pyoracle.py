@@ -125,6 +125,7 @@ def lib():
         L.orc_channel_destroy.argtypes = [C.c_void_p]
         L.orc_channel_ddc.restype = C.POINTER(Ddc)
         L.orc_channel_ddc.argtypes = [C.c_void_p]
+        L.orc_channel_nco.argtypes = [C.c_void_p, C.POINTER(NcoState)]
         L.orc_channel_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.orc_channel_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_variant_default.argtypes = [C.POINTER(Variant)]
@@ -409,6 +410,12 @@ class Frontend:
         out = Channel.summary(ch)
         ch.h = None
         return out
+
+    def channel_nco(self, i):
+        """What channel i's decimator carries into the next block: (decimation_remain, starting_phase, output_size of the last block)."""
+        s = NcoState()
+        lib().orc_channel_nco(lib().orc_frontend_channel(self.h, i), C.byref(s))
+        return s.decimation_remain, s.starting_phase, s.output_size
 
     def channel_view(self, i):
         ch = Channel.__new__(Channel)

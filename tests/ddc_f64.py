@@ -36,6 +36,8 @@ Two NCO modes:
 
 Nothing is fitted and nothing is skipped: block 0 is compared too (its history is zero on both sides).
 """
+import math
+
 import numpy as np
 
 
@@ -127,6 +129,13 @@ def ddc_reference(x, taps, plan, nco_phasors=None, blocks=None, fast=False, taps
     return outs
 
 
+def half_rate_sign(g):
+    """(-1)^g for stream output indices g: what the reference's bin arithmetic leaves on the output of a receiver with
+    pre_decimation = post_decimation = 1 (below 10 800 sps; oracle/PINNING.md section 3).  The model above does not contain it:
+    the tests of those rates multiply it in, and say so."""
+    return 1.0 - 2.0 * (np.asarray(g, np.int64) & 1)
+
+
 def errors(got, want):
     """(relative RMS error, worst element error / RMS of the model output) of one block."""
     got = np.asarray(got, np.complex128)
@@ -137,6 +146,14 @@ def errors(got, want):
 
 
 # ---------------------------------------------------------------- the channel's plan and taps, and the test signal
+
+def channel_offsets(fs, overlap):
+    """Channel centres (Hz from the receiver centre, before the 1440 Hz of the carrier): one within 1 kHz of +fs / 2, one exactly on
+    a bin that is a multiple of v (f0 = j fs / overlap an integer number of Hz; 0 where no other exists inside the band), one ordinary."""
+    step = fs // math.gcd(fs, overlap)
+    on_bin = step * max(1, int(0.21 * fs) // step) if step < fs // 2 else 0
+    return [fs // 2 - 600, on_bin, -int(0.3137 * fs)]
+
 
 def channel_plan(oracle, fs, cf, freq):
     """(planner record, time-domain band-pass taps as complex128) of one channel: the oracle's planner and tap design with the

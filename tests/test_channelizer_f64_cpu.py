@@ -1,8 +1,7 @@
 """CPU tests: the float64 direct-form model of the channelizer (tests/ddc_f64.py) and the oracle pinned to each other, with no
-fitted rotation and no skipped start-up, at five sample rates; the model's fast path pinned to its definition; the oracle's
-single-precision FFT inside the worst-element gate the GPU FFT tests use."""
-import math
-
+fitted rotation and no skipped start-up, at twelve sample rates from 12 ksps to 2.4 Msps (1 .. 128 alias rows); the half-rate shift the
+reference's arithmetic leaves below 10 800 sps pinned from both sides, and why 12 ksps escapes it; the model's fast path pinned to
+its definition; the oracle's single-precision FFT inside the worst-element gate the GPU FFT tests use."""
 import numpy as np
 import pytest
 
@@ -16,16 +15,21 @@ CF = 10_000_000
 # digit.  The figures are relative to the RMS of the model output, whose in-band level lies 60 dB below the alias-frequency tone.
 # That input level is why they sit near 1e-4 and not 1e-7: the fp32 rounding of the strong tone (amplitude 1) is 1e-7 of ITS level,
 # which is 1e-4 of the 1e-3 in-band level the error is divided by.
-MEASURED = {12_000: (1.8e-5, 6.2e-5), 250_000: (6.3e-5, 1.6e-4), 345_599: (5.0e-5, 1.3e-4), 1_000_000: (2.8e-5, 6.8e-5), 2_400_000: (3.6e-5, 1.3e-4)}
-GATE_RMS, GATE_MAX = 3e-4, 7e-4                # 4 x (6.3e-5, 1.53e-4) = (2.5e-4, 6.1e-4), rounded up to one digit
+MEASURED = {12_000: (1.8e-5, 6.2e-5), 250_000: (6.3e-5, 1.6e-4), 345_599: (5.0e-5, 1.3e-4), 1_000_000: (2.8e-5, 6.8e-5), 2_400_000: (3.6e-5, 1.3e-4),
+            # the geometries of 1 .. 8 alias rows, measured when they were added; the gates below were NOT re-derived from them
+            # (the worst, 64 000 sps, uses 0.36 of the RMS gate and 0.45 of the worst-element gate)
+            16_000: (3.0e-5, 1.2e-4), 24_000: (6.6e-5, 1.9e-4), 48_000: (9.9e-5, 2.5e-4), 64_000: (1.1e-4, 3.2e-4), 86_399: (9.0e-5, 2.6e-4),
+            96_000: (6.2e-5, 1.7e-4), 172_799: (6.9e-5, 1.9e-4)}
+# the same against the model times (-1)^K (test_half_rate_shift_below_10800_sps); against the unmodified model: 1.41 .. 1.44
+MEASURED_HALF_RATE = {5_400: (1.5e-5, 5.9e-5), 8_000: (9.2e-6, 3.8e-5), 10_799: (3.2e-5, 1.3e-4)}
+GATE_RMS, GATE_MAX = 3e-4, 7e-4                # 4 x (6.3e-5, 1.53e-4) = (2.5e-4, 6.1e-4) of the first five rates, rounded up to one digit
+# (pre_decimation, post_decimation, inverse FFT size) of the rates below 250 ksps: the geometries of 1 .. 8 alias rows
+SMALL_GEOMETRY = {5_400: (1, 1, 1024), 8_000: (1, 1, 2048), 10_799: (1, 1, 2048), 12_000: (1, 2, 2048), 16_000: (1, 2, 4096),
+                  24_000: (2, 2, 2048), 32_000: (2, 2, 4096), 48_000: (4, 2, 2048), 64_000: (4, 2, 4096), 86_399: (4, 2, 4096),
+                  86_400: (8, 2, 2048), 96_000: (8, 2, 2048), 172_799: (8, 2, 4096)}
 
 
-def channel_offsets(fs, overlap):
-    """Channel centres (Hz from the receiver centre, before the 1440 Hz of the carrier): one within 1 kHz of +fs / 2, one exactly on
-    a bin that is a multiple of v (f0 = j fs / overlap an integer number of Hz; 0 where no other exists inside the band), one ordinary."""
-    step = fs // math.gcd(fs, overlap)
-    on_bin = step * max(1, int(0.21 * fs) // step) if step < fs // 2 else 0
-    return [fs // 2 - 600, on_bin, -int(0.3137 * fs)]
+channel_offsets = M.channel_offsets             # shared with the device tests (tests/ddc_f64.py)
 
 
 def run_case(oracle, fs, nblk=4, seed=7):
@@ -44,11 +48,13 @@ def run_case(oracle, fs, nblk=4, seed=7):
     return g, freqs, x, got
 
 
-@pytest.mark.parametrize("fs", [12_000, 250_000, 345_599, 1_000_000, 2_400_000])
+@pytest.mark.parametrize("fs", [12_000, 16_000, 24_000, 48_000, 64_000, 86_399, 96_000, 172_799, 250_000, 345_599, 1_000_000, 2_400_000])
 def test_oracle_channelizer_vs_float64_direct_form(oracle, fs):
     """Four blocks of in-band tones + noise + a tone 60 dB up on an alias of each channel's centre + one on the pass-band edge:
-    the oracle's chan_out against ddc_reference per block and channel, nothing fitted, block 0 included."""
+    the oracle's chan_out against ddc_reference per block and channel, nothing fitted, block 0 included.  Below 250 ksps these are
+    the geometries of 1, 2, 4 and 8 alias rows (pre_decimation), where every row reaches the output."""
     g, freqs, x, got = run_case(oracle, fs)
+    assert (g.pre_decimation, g.post_decimation, g.fft_inv_size) == SMALL_GEOMETRY.get(fs, (g.pre_decimation, g.post_decimation, g.fft_inv_size))
     worst = [0.0, 0.0]
     for c, f in enumerate(freqs):
         plan, taps = M.channel_plan(oracle, fs, CF, f)
@@ -63,6 +69,52 @@ def test_oracle_channelizer_vs_float64_direct_form(oracle, fs):
             worst = [max(worst[0], e[0]), max(worst[1], e[1])]
     print("fs %d worst: rel rms %.3g  worst/rms %.3g" % (fs, worst[0], worst[1]))
     assert worst[0] <= GATE_RMS and worst[1] <= GATE_MAX, worst
+
+
+@pytest.mark.parametrize("fs", [5_400, 8_000, 10_799])
+def test_half_rate_shift_below_10800_sps(oracle, fs):
+    """pre_decimation = post_decimation = 1 (M = N): the reference's bin arithmetic leaves a shift of N / 2 bins, half the channel's
+    own sample rate (oracle/PINNING.md section 3 has the derivation), so its chan_out is the model's times (-1)^K, K the absolute
+    output index of the stream.  Both sides of that are asserted: with the factor the oracle is inside the gates of every other rate,
+    and against the unmodified model it is off by more than the model's own RMS -- a `corrected` oracle fails here, not silently."""
+    g, freqs, x, got = run_case(oracle, fs)
+    assert (g.pre_decimation, g.post_decimation, g.fft_inv_size) == SMALL_GEOMETRY[fs] and g.fft_inv_size == g.fft_size
+    P = g.post_input_size
+    worst, plain = [0.0, 0.0], 10.0
+    for c, f in enumerate(freqs):
+        plan, taps = M.channel_plan(oracle, fs, CF, f)
+        want = M.ddc_reference(x, taps, plan)
+        for b in range(len(want)):
+            assert len(got[c][b]) == len(want[b]) == P
+            e = M.errors(got[c][b], want[b] * M.half_rate_sign(b * P + np.arange(P)))
+            e0 = M.errors(got[c][b], want[b])
+            print("fs %d ch %d block %d: with (-1)^K rel rms %.3g  worst/rms %.3g | unmodified model rel rms %.3g" % (fs, c, b, e[0], e[1], e0[0]))
+            worst = [max(worst[0], e[0]), max(worst[1], e[1])]
+            plain = min(plain, e0[0])
+    print("fs %d worst with (-1)^K: rel rms %.3g  worst/rms %.3g; best against the unmodified model: %.3g" % (fs, worst[0], worst[1], plain))
+    assert worst[0] <= GATE_RMS and worst[1] <= GATE_MAX, worst
+    assert plain > 1.0, plain
+
+
+def test_why_12000_sps_escapes_the_half_rate_shift(oracle):
+    """12 000 - 21 599 sps have pre_decimation 1 as well, and the same N / 2 bins are left over before the decimator; but
+    post_decimation is 2 and post_input_size even, so the decimator starts every block at sample 0 (the oracle's decimation_remain
+    is 0 after every block) and keeps the even samples g = 2 K of the stream, where (-1)^g = 1."""
+    fs = 12_000
+    _, _, g = oracle.geometry(fs)
+    assert (g.pre_decimation, g.post_decimation) == (1, 2) and g.fft_inv_size == g.fft_size and g.post_input_size % 2 == 0
+    freqs = [CF + f - 1440 for f in channel_offsets(fs, g.overlap_length)]
+    dec = oracle.lib().orc_compute_fft_decimation_rate(fs, 5400)
+    x = M.make_signal(fs, CF, freqs, freqs, 5 * g.input_size, 7, dec, g.pre_decimation)
+    fe = oracle.Frontend(fs, CF, freqs)
+    for b in range(5):
+        fe.push_block(x[b * g.input_size:(b + 1) * g.input_size])
+        for c in range(len(freqs)):
+            remain, _, n_out = fe.channel_nco(c)
+            assert (remain, n_out) == (0, g.post_input_size // 2), (b, c, remain, n_out)
+        kept = b * g.post_input_size + np.arange(0, g.post_input_size, 2)       # stream indices the decimator keeps of block b
+        assert np.all(M.half_rate_sign(kept) == 1.0)
+    fe.close()
 
 
 def test_model_fast_path_is_the_definition(oracle):

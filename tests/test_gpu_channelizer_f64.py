@@ -10,7 +10,14 @@ with floor = the oracle-against-model figures of oracle/PINNING.md for the geome
 the same sums with different FFT factorisations and summation orders; a wrong alias row, bin, scrap index or block column is orders
 of magnitude outside a factor of 4.  For e_gpu the model runs with the device's own NCO phasor tables (tap 9: the fp32 phasor recurrence's drift is not the
 fold's; the tables themselves are bounded against the float64 phase); e_ora, the calibrating side, uses the float64 phase.  The
-device is never compared with itself."""
+device is never compared with itself.
+
+Both fold paths are covered.  The matrix-pipe fold (pre_decimation a multiple of 8: 96 ksps, its smallest geometry, 250 ksps, 2.048,
+2.4, 40 and 80 Msps) and, in the second half of the file, the plain-VALU fold_ref_kernel on the unpadded tap layout, which is the
+shipped fold of every receiver below 86 400 sps (pre_decimation 1, 2 or 4): its passes of four blocks, full and ragged, its branch
+for fewer than four alias rows, several receivers, a retune, post_decimation = 1 and the inverse FFT at M = N.  Where the comparison
+is between two runs of the device (batching, retune, HFDL_GPU_FOLD_PRUNE) it is a comparison of uint32 words that says "this launch
+shape changes nothing"; what the words ARE is held to the model by the tests beside it on the same geometry."""
 import numpy as np
 import pytest
 
@@ -21,8 +28,16 @@ pytestmark = pytest.mark.gpu
 
 RMS_TOL = 1e-4
 # oracle against model as measured on the CPU (oracle/PINNING.md, tests/test_channelizer_f64_cpu.py): (relative RMS, worst / RMS)
-FLOOR = {250_000: (6.3e-5, 1.6e-4), 2_400_000: (3.6e-5, 1.3e-4)}
-FLOOR_ANY = (6.3e-5, 1.6e-4)          # the worst over the five rates measured: geometries outside that table
+FLOOR = {250_000: (6.3e-5, 1.6e-4), 2_400_000: (3.6e-5, 1.3e-4),
+         # the geometries of 1 .. 8 alias rows (MEASURED of the CPU test; PINNING section 3's table)
+         12_000: (1.8e-5, 6.2e-5), 24_000: (6.6e-5, 1.9e-4), 48_000: (9.9e-5, 2.5e-4), 64_000: (1.1e-4, 3.2e-4), 96_000: (6.2e-5, 1.7e-4),
+         # pre = post = 1, against the model times (-1)^K (MEASURED_HALF_RATE of the CPU test)
+         8_000: (9.2e-6, 3.8e-5), 10_799: (3.2e-5, 1.3e-4)}
+FLOOR_ANY = (6.3e-5, 1.6e-4)          # the worst over the five rates measured first: the large geometries outside that table
+# (pre_decimation, inverse FFT size) of the receivers below 250 ksps.  pre < 8: TAPL_PLAIN, the unpadded tap layout, which
+# fold_ref_kernel folds on the vector ALUs (frontend_create.cpp, fold_kernels.hip pick_variant); pre = 8: the smallest geometry of the
+# matrix-pipe fold, one look-ahead group of two quads of alias rows
+SMALL_RATES = {8_000: (1, 2048), 10_799: (1, 2048), 12_000: (1, 2048), 24_000: (2, 2048), 48_000: (4, 2048), 64_000: (4, 4096), 96_000: (8, 2048)}
 
 
 def read_blocks(fe, held, first_block, channels, dev):
@@ -34,8 +49,9 @@ def read_blocks(fe, held, first_block, channels, dev):
         dev[first_block + j] = {c: (fe.read_tap(F.TAP_CHAN_OUT, c, back=back), fe.read_tap(F.TAP_NCO_PHASORS, c, back=back)) for c in channels}
 
 
-def compare(tag, oracle, fs, cf, freqs, x, dev, floor, gate=True, rms_tol=None):
-    """dev: {block: {index into freqs: (chan_out, phasors)}} of one receiver's stream x.  Returns the worst (e_gpu, e_ora, ratio) pairs."""
+def compare(tag, oracle, fs, cf, freqs, x, dev, floor, gate=True, rms_tol=None, half_rate=False):
+    """dev: {block: {index into freqs: (chan_out, phasors)}} of one receiver's stream x.  Returns the worst (e_gpu, e_ora, ratio) pairs.
+    half_rate: the model times (-1)^K on both sides (pre_decimation = post_decimation = 1: oracle/PINNING.md section 3)."""
     plans = [M.channel_plan(oracle, fs, cf, f) for f in freqs]
     st = M.Stream(x, plans[0][0])
     H = [M.taps_spectrum(t, st.L) for _, t in plans]
@@ -54,6 +70,9 @@ def compare(tag, oracle, fs, cf, freqs, x, dev, floor, gate=True, rms_tol=None):
             # the table against the float64 phase: fp32 start phase (<= 2 ulp(pi) a block) + a recurrence of len(ph) steps of <= 4 roundings
             K = b * len(ph) + np.arange(len(ph))
             assert plan.post_input_size % plan.post_decimation == 0
+            if half_rate:
+                assert plan.pre_decimation == plan.post_decimation == 1
+                model = model * M.half_rate_sign(K)
             dph = float(np.abs(ph.astype(np.complex128) - np.exp(1j * M.nco_phase(plan, K))).max())
             worst["ph"] = max(worst["ph"], dph)
             assert dph <= (4 * len(ph) + 4 * (b + 1)) * 2.0 ** -23, (tag, b, c, dph)
@@ -94,7 +113,8 @@ def test_every_fold_form_against_the_float64_model(gpu, oracle, monkeypatch, fs,
     without polling and closed by a sync: the four-, sixteen- and thirty-two-column forms each against the model, every block of every
     half.  130 channels at 2.4 Msps: full 64-channel workgroups, left-over octets, six padding slots; the first half after a sync
     closes at 16 blocks there, so the halves above 16 are preceded by 16 blocks that are not read.  Both geometries fold on the
-    matrix pipe (rows per slice a multiple of 4: asserted), the plain-VALU fall-back is not what is covered here."""
+    matrix pipe (rows per slice a multiple of 4: asserted); the plain-VALU fold has
+    test_small_geometries_in_every_launch_shape_against_the_float64_model below."""
     cf = 10_000_000
     freqs = case1_freqs(fs, nch)
     watch = spread(nch)
@@ -325,3 +345,297 @@ def test_low_level_burst_keeps_the_demodulator_state_finite(gpu, oracle):
     fe.close()
     assert got == sorted((p["freq"], p["octets"]) for p in ora.pdus) and len(got) == 1
     assert all(np.isfinite(v) for st in stats for v in st.values()), stats
+
+
+# ---------------------------------------------------------------- the receivers below 250 ksps: 1 .. 8 alias rows
+
+def u32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def small_rate_freqs(oracle, fs, cf, pick=(0, 1, 2), extra=()):
+    """Channels as the CPU test picks them (ddc_f64.channel_offsets: within 1 kHz of +fs / 2, on a multiple of v, ordinary) + extra offsets."""
+    _, _, d = oracle.geometry(fs)
+    offs = M.channel_offsets(fs, d.overlap_length)
+    return [cf + f - 1440 for f in [offs[i] for i in pick] + list(extra)]
+
+
+def assert_fold_path(g, fs):
+    """The geometry is the one meant and the fold path the one meant: True where fold_ref_kernel folds (the plain layout)."""
+    pre, m = SMALL_RATES[fs]
+    assert (g.pre_decimation, g.fft_inv_size, g.fold_slices, g.fold_rows) == (pre, m, 1, pre)
+    rows = g.pre_decimation // g.fold_slices
+    if pre % 8 == 0:
+        assert rows == 8 and g.fft_inv_size % 16 == 0, "the matrix form is not what folds here"
+        return False
+    assert rows % 4 != 0 or rows < 8, "the matrix-pipe fold on this geometry: the plain-VALU kernel is not covered"
+    return True
+
+
+def fold_launches(k, nb_max, thirty_two):
+    """Launch sizes of a half of k blocks: fold_launch_blocks (fold_kernels.hip) as it reads, unpruned.  Up to nb_max (at most 32) blocks a
+    launch; 17 .. 20 go as sixteen and the rest; more than 16 need a thirty-two-column tiling, which only an octet layout has."""
+    out = []
+    while k:
+        take = min(k, nb_max, 32)
+        if 16 < take <= 20 or (take > 16 and not thirty_two):
+            take = 16
+        out.append(take)
+        k -= take
+    return out
+
+
+def shape_counts(halves, nb_max, thirty_two):
+    want = {}
+    for k in halves:
+        for nb in fold_launches(k, nb_max, thirty_two):
+            want[nb] = want.get(nb, 0) + 1
+    return want
+
+
+@pytest.mark.parametrize("fs", [12_000, 24_000, 48_000, 64_000, 96_000])
+def test_small_geometries_in_every_launch_shape_against_the_float64_model(gpu, oracle, monkeypatch, fs):
+    """1, 2 and 4 alias rows (fold_ref_kernel on the plain layout: its `rows - r < 4` branch at 1 and 2 rows, M = 2048 and 4096 at 4) and
+    8 rows (the matrix-pipe fold's smallest geometry), where EVERY alias row reaches the output.  One continuous stream in halves of
+    1, 3, 4, 5, 8, 9, 16 and 21 blocks, each closed by a sync, every block of every half against the model: fold_ref_kernel's passes of
+    four blocks full, ragged (3, 5 = 4 + 1, 9 = 4 + 4 + 1) and repeated; 21 blocks are 16 + 5 on the plain layout (no thirty-two-column
+    tiling) and one launch at 96 ksps."""
+    cf = 10_000_000
+    freqs = small_rate_freqs(oracle, fs, cf, extra=[int(0.127 * fs)] + ([-fs // 2 + 2200] if fs >= 24_000 else []))
+    counts = [1, 3, 4, 5, 8, 9, 16, 21]
+    monkeypatch.setenv("HFDL_GPU_FOLD_BATCH", "32")
+    fe = gpu.Frontend(fs, cf, freqs)
+    g = fe.geometry
+    assert g.fold_batch == 32
+    plain = assert_fold_path(g, fs)
+    n = fe.input_size
+    dec = oracle.lib().orc_compute_fft_decimation_rate(fs, 5400)
+    x = M.make_signal(fs, cf, freqs, freqs, sum(counts) * n, 600 + fs // 1000, dec, g.pre_decimation)
+    fe.reset_timers(True)
+    dev, b = {}, 0
+    for k in counts:
+        for j in range(k):
+            fe.push_block(x[(b + j) * n:(b + j + 1) * n])
+        fe.sync()
+        read_blocks(fe, k, b, list(range(len(freqs))), dev)
+        b += k
+    shapes = fe.fold_launch_shapes()
+    stats = fe.all_channel_stats()
+    fe.close()
+    want = shape_counts(counts, 32, not plain)
+    print("fs %d (%s layout) fold launches by block count:" % (fs, "plain" if plain else "octet"), shapes)
+    assert shapes == want, (shapes, want)
+    assert want == ({1: 1, 3: 1, 4: 1, 5: 2, 8: 1, 9: 1, 16: 2} if plain else {1: 1, 3: 1, 4: 1, 5: 1, 8: 1, 9: 1, 16: 1, 21: 1})
+    assert all(np.isfinite(v) for st in stats for v in st.values()), stats
+    compare("fs %d x %d channels, %d alias rows, %d blocks" % (fs, len(freqs), g.pre_decimation, len(dev)), oracle, fs, cf, freqs, x, dev, FLOOR[fs])
+
+
+@pytest.mark.parametrize("fs,offs", [(12_000, [-2_000]), (48_000, [-15_000, 9_000, 20_500])])
+def test_fold_batching_changes_nothing_on_the_plain_layout(gpu, oracle, monkeypatch, fs, offs):
+    """The reduced twin of test_gpu_parity.py::test_fold_batching_changes_nothing where fold_ref_kernel is the shipped fold: chan_out of
+    every block as uint32, every PDU and every statistic of a launch per block (HFDL_GPU_FOLD_BATCH=1) against batches of 4, 8 and 16 cut
+    ragged by draining polls (13, 3, 1, 5, 9 blocks: halves that close full on the way and passes of one to four blocks).  31 blocks
+    with one burst per channel; the bursts decode, and as the oracle decodes them."""
+    import hfdl_synth as synth
+    cf = 10_000_000
+    freqs = [cf + o for o in offs]
+    rng = np.random.default_rng(fs)
+    bursts = [dict(freq=f, mode=int(rng.integers(0, 4)), octets=b"", t0=0.4 + 0.1 * i, amp=0.05, cfo=float(rng.uniform(-10, 10))) for i, f in enumerate(freqs)]
+    for bu in bursts:
+        bu["octets"] = synth.make_pdu(rng, bu["mode"])
+    dec, _, d = oracle.geometry(fs)
+    n, nblk = d.input_size, 31
+    x = synth.synth_wideband(fs, cf, nblk * n, bursts, noise_sigma=0.01 * np.sqrt(dec / 32.0), seed=3)
+    chans = list(range(len(freqs)))
+
+    def run(fold_env, cuts):
+        monkeypatch.setenv("HFDL_GPU_FOLD_BATCH", str(fold_env))
+        fe = gpu.Frontend(fs, cf, freqs)
+        g = fe.geometry
+        assert g.fold_batch == fold_env and fe.input_size == n and assert_fold_path(g, fs)
+        half = min(32, -(-max(g.fold_batch, g.demod_batch) // g.fold_batch) * g.fold_batch)      # blocks a half holds (planner.h plan_batches, half_blocks)
+        outs, got, b, i = {}, [], 0, 0
+        while b < nblk:
+            k = min(cuts[i % len(cuts)], nblk - b)
+            i += 1
+            for j in range(k):
+                fe.push_block(x[(b + j) * n:(b + j + 1) * n])
+            got += fe.poll_pdus()                 # closes the half as it is
+            held = k % half or min(k, half)       # blocks of the newest half: what read_tap(back=...) still reaches
+            for j in range(held):
+                outs[b + k - held + j] = [u32(fe.read_tap(F.TAP_CHAN_OUT, c, back=held - 1 - j)).copy() for c in chans]
+            b += k
+        stats = fe.all_channel_stats()
+        fe.close()
+        return outs, sorted(got, key=lambda p: (p["freq"], p["sample_index"])), stats
+
+    ref_outs, ref_pdus, ref_stats = run(1, [1])
+    assert sorted(ref_outs) == list(range(nblk)) and all(len(a) == 2 * (d.post_input_size // d.post_decimation) for v in ref_outs.values() for a in v)
+    ora = oracle.Frontend(fs, cf, freqs)
+    for b in range(nblk):
+        ora.push_block(x[b * n:(b + 1) * n])
+    want = sorted((p["freq"], p["sample_index"], p["octets"]) for p in ora.pdus)
+    ora.close()
+    assert [(p["freq"], p["sample_index"], p["octets"]) for p in ref_pdus] == want and len(want) == len(freqs)
+    for fold_env in (4, 8, 16):
+        outs, pdus, stats = run(fold_env, [13, 3, 1, 5, 9])
+        assert len(outs) >= 5, (fold_env, sorted(outs))
+        for blk, v in outs.items():
+            for c, a in zip(chans, v):
+                assert np.array_equal(a, ref_outs[blk][c]), (fold_env, blk, c)
+        assert pdus == ref_pdus, fold_env               # every field of every PDU
+        assert stats == ref_stats, fold_env
+
+
+@pytest.mark.parametrize("fs,pick", [(8_000, (0, 2)), (10_799, (2,))])
+def test_post_decimation_1_against_the_float64_model_and_the_oracle(gpu, oracle, fs, pick):
+    """Below 10 800 sps pre_decimation = post_decimation = 1: the inverse FFT has the forward FFT's size, every sample of it past the
+    scrap is an output, and the reference's bin arithmetic leaves (-1)^K on the output (oracle/PINNING.md section 3;
+    tests/test_channelizer_f64_cpu.py::test_half_rate_shift_below_10800_sps).  The device is held to the REFERENCE's arithmetic: its
+    chan_out against the model times (-1)^K under the gate of every other geometry, six blocks in one half; every block yields
+    post_input_size outputs; the statistics stay finite; and on a stream with one clean burst the PDU list is the oracle's, which is
+    empty: such a receiver is accepted, as the reference accepts it, and decodes nothing.  10 799 sps: resampling rate 0.50005, the
+    resampler's lower edge."""
+    import hfdl_synth as synth
+    cf = 10_000_000
+    freqs = small_rate_freqs(oracle, fs, cf, pick=pick)
+    fe = gpu.Frontend(fs, cf, freqs)
+    g = fe.geometry
+    assert assert_fold_path(g, fs) and g.post_decimation == 1 and g.fft_inv_size == g.fft_size
+    assert abs(g.resamp_rate - 5400.0 / fs) < 1e-6 and 0.5 < g.resamp_rate < (0.5001 if fs == 10_799 else 0.7)
+    n = fe.input_size
+    x = M.make_signal(fs, cf, freqs, freqs, 6 * n, 700 + fs // 1000, 1, 1)
+    fe.reset_timers(True)
+    for b in range(6):
+        fe.push_block(x[b * n:(b + 1) * n])
+    fe.sync()
+    dev = {}
+    read_blocks(fe, 6, 0, list(range(len(freqs))), dev)
+    assert fe.fold_launch_shapes() == {6: 1}
+    for b, v in dev.items():
+        for c, (out, ph) in v.items():
+            assert len(out) == len(ph) == g.post_input_size, (b, c, len(out))
+    stats = fe.all_channel_stats()
+    fe.close()
+    assert all(np.isfinite(v) for st in stats for v in st.values()), stats
+    compare("fs %d x %d channels, post_decimation 1" % (fs, len(freqs)), oracle, fs, cf, freqs, x, dev, FLOOR[fs], half_rate=True)
+    # one clean burst on channel 0, the stream of test_other_sample_rates: decoded at 12 ksps, not here
+    rng = np.random.default_rng(fs)
+    mode = int(rng.integers(0, 4))
+    bursts = [dict(freq=freqs[0], mode=mode, octets=synth.make_pdu(rng, mode), t0=0.4, amp=0.05, cfo=float(rng.uniform(-10, 10)))]
+    nblk = int(3.4 * fs) // n + 1
+    y = synth.synth_wideband(fs, cf, nblk * n, bursts, noise_sigma=0.01 * np.sqrt(1 / 32.0), seed=3)
+    fe = gpu.Frontend(fs, cf, freqs)
+    ora = oracle.Frontend(fs, cf, freqs)
+    for b in range(nblk):
+        fe.push_block(y[b * n:(b + 1) * n])
+        ora.push_block(y[b * n:(b + 1) * n])
+    got = sorted((p["freq"], p["sample_index"], p["octets"]) for p in fe.poll_pdus())
+    stats = fe.all_channel_stats()
+    fe.close()
+    want = sorted((p["freq"], p["sample_index"], p["octets"]) for p in ora.pdus)
+    ora.close()
+    assert got == want and want == []
+    assert all(np.isfinite(v) for st in stats for v in st.values()), stats
+
+
+def test_three_receivers_on_the_plain_layout_against_the_float64_model(gpu, oracle, monkeypatch):
+    """Receivers of 3, 1 and 2 channels at 48 ksps with centres and streams of their own, nine blocks in one half.  The plain layout
+    pads nothing (tap_layout_group = 1): slot = channel, and fold_ref_kernel finds a channel's spectrum by rx_of_channel.  Every
+    channel against the model of ITS receiver's centre and stream."""
+    fs = 48_000
+    centres = [10_000_000, 11_500_000, 8_700_000]
+    picks = [((0, 1, 2), ()), ((2,), ()), ((0,), (int(0.127 * fs),))]
+    recv = [(cf, small_rate_freqs(oracle, fs, cf, pick=p, extra=e)) for cf, (p, e) in zip(centres, picks)]
+    nchs = [len(fr) for _, fr in recv]
+    monkeypatch.setenv("HFDL_GPU_FOLD_BATCH", "32")
+    fe = gpu.MultiFrontend(fs, recv)
+    g = fe.geometry
+    assert g.fold_batch == 32 and g.channels == 6 and nchs == [3, 1, 2] and assert_fold_path(g, fs)
+    n = fe.input_size
+    dec = oracle.lib().orc_compute_fft_decimation_rate(fs, 5400)
+    xs = [M.make_signal(fs, cf, fr, fr, 9 * n, 800 + r, dec, g.pre_decimation) for r, (cf, fr) in enumerate(recv)]
+    fe.reset_timers(True)
+    for b in range(9):
+        fe.push_blocks([x[b * n:(b + 1) * n] for x in xs])
+    fe.sync()
+    dev = {}
+    read_blocks(fe, 9, 0, list(range(6)), dev)
+    shapes = fe.fold_launch_shapes()
+    fe.close()
+    assert shapes == {9: 1}, shapes
+    base = np.concatenate([[0], np.cumsum(nchs)])
+    for r, (cf, fr) in enumerate(recv):
+        d = {blk: {i: v[int(base[r]) + i] for i in range(nchs[r])} for blk, v in dev.items()}
+        compare("receiver %d (%d channels) of 3 on the plain layout, fs %d" % (r, nchs[r], fs), oracle, fs, cf, fr, xs[r], d, FLOOR[fs])
+
+
+def test_retune_on_the_plain_layout(gpu, oracle):
+    """Cases 1 - 3 of tests/test_gpu_retune.py at 48 ksps, where the retuned channel's taps go through store_out's plain branch into the
+    unpadded layout: channel 1 of 3 moves at block 5 of 10, everything pushed at once (the retune closes the half of five).  Block 4 is
+    zeros, so the history at the boundary is a fresh front end's.  After the boundary channel 1's filter and chan_out are, as uint32,
+    those of a front end created with the new frequency and fed blocks 5 .. 9; before it they are the never-retuned run's; channels 0
+    and 2 are the never-retuned run's throughout."""
+    fs, cf, CH, K, NALL = 48_000, 10_000_000, 1, 5, 10
+    freqs = [cf - 15_000, cf + 9_000, cf + 20_500]
+    f_new = cf + 2_300
+    fresh = list(freqs)
+    fresh[CH] = f_new
+    dec, _, d = oracle.geometry(fs)
+    n = d.input_size
+    x = M.make_signal(fs, cf, freqs + [f_new], freqs + [f_new], NALL * n, 900, dec, d.pre_decimation)
+    x[(K - 1) * n:K * n] = 0
+
+    def run(fr, first, retune_at=None):
+        fe = gpu.Frontend(fs, cf, fr)
+        assert assert_fold_path(fe.geometry, fs) and fe.input_size == n
+        fe.export_enable([0, 1, 2], ring_blocks=64)
+        for b in range(first, NALL):
+            if b == retune_at:
+                fe.retune(CH, f_new)
+            fe.push_block(x[b * n:(b + 1) * n])
+        fe.sync()
+        samples, counts, _, _, blocks, _ = fe.export_read(0, wait=True)
+        assert blocks == list(range(NALL - first))
+        filters = [u32(fe.read_tap(F.TAP_FILTER, c)).copy() for c in range(3)]
+        fe.close()
+        return u32(samples), counts, filters              # [block][channel][P]
+
+    A, A_cnt, A_fil = run(freqs, 0, retune_at=K)
+    B, B_cnt, B_fil = run(fresh, K)
+    A1, A1_cnt, A1_fil = run(freqs, 0)
+    P = d.post_input_size // d.post_decimation
+    assert np.all(A_cnt == P) and np.all(B_cnt == P) and np.all(A1_cnt == P)
+    assert np.array_equal(A_fil[CH], B_fil[CH]) and not np.array_equal(A_fil[CH], A1_fil[CH])
+    for c in (0, 2):
+        assert np.array_equal(A_fil[c], A1_fil[c]) and np.array_equal(A_fil[c], B_fil[c]), c
+        assert np.array_equal(A[:, c], A1[:, c]), c
+    assert np.array_equal(A[K:, CH], B[:, CH])
+    assert np.array_equal(A[:K, CH], A1[:K, CH])
+    assert not np.array_equal(A[K:, CH], A1[K:, CH])
+    assert np.mean(A[K:, CH, :2 * P] != 0) > 0.99 and np.mean(A[:K - 1, CH, :2 * P] != 0) > 0.99          # (the words compared are not zeros)
+
+
+def test_fold_prune_is_off_on_the_plain_layout(gpu, oracle, monkeypatch):
+    """HFDL_GPU_FOLD_PRUNE is the octet layout's (row windows per octet): on a plain geometry create reads it as off --
+    geometry.fold_rows reports every row, and chan_out is, as uint32, the unset run's."""
+    fs, cf = 48_000, 10_000_000
+    freqs = small_rate_freqs(oracle, fs, cf)
+    dec, _, d = oracle.geometry(fs)
+    n = d.input_size
+    x = M.make_signal(fs, cf, freqs, freqs, 5 * n, 950, dec, d.pre_decimation)
+    words = []
+    for prune in (None, "3e-7"):
+        if prune:
+            monkeypatch.setenv("HFDL_GPU_FOLD_PRUNE", prune)
+        else:
+            monkeypatch.delenv("HFDL_GPU_FOLD_PRUNE", raising=False)
+        fe = gpu.Frontend(fs, cf, freqs)
+        assert assert_fold_path(fe.geometry, fs) and fe.geometry.fold_rows == fe.geometry.pre_decimation
+        for b in range(5):
+            fe.push_block(x[b * n:(b + 1) * n])
+        fe.sync()
+        words.append([u32(fe.read_tap(F.TAP_CHAN_OUT, c, back=4 - b)).copy() for b in range(5) for c in range(3)])
+        fe.close()
+    assert all(len(a) and np.array_equal(a, b) for a, b in zip(*words))
+    assert np.mean(np.concatenate(words[0]) != 0) > 0.99
