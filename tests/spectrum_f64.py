@@ -137,6 +137,32 @@ class Accumulator:
         return ((self.s.astype(np.float64) - self.c.astype(np.float64)) / self.T).astype(np.float32), self.peak
 
 
+# ---------------------------------------------------------------- the stage check of the GPU tests
+
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def over(err, lim):
+    """err / lim per band for a statement err <= lim: where the bound is zero (a band whose spectrum is exact zeros: on-bin tones on
+    even bins leave such) an error of zero is 0, inside it, and any other is inf."""
+    err, lim = np.asarray(err, np.float64), np.asarray(lim, np.float64)
+    return np.divide(err, lim, out=np.where(err > 0, np.inf, 0.0), where=lim > 0)
+
+
+def check_against_model(tag, got, p64, ref, emu, G, T):
+    """got = spectrum_read dict; p64 / ref [T][bins] float64 per-block powers and gate references; emu = (mean, peak) of the fp32 emulation."""
+    g = gate(G)
+    mean64, peak64 = np.mean(p64[:T], axis=0), np.max(p64[:T], axis=0)
+    e_mean = over(np.abs(got["mean"] - mean64), g * np.mean(ref[:T], axis=0))
+    e_peak = over(np.abs(got["peak"] - peak64), g * np.max(ref[:T], axis=0))
+    same = bool(np.array_equal(u32(got["mean"]), u32(emu[0])) and np.array_equal(u32(got["peak"]), u32(emu[1])))
+    print("%s T=%d: worst |mean error| / gate %.3f, |peak error| / gate %.3f, bit-identical to the fp32 emulation: %s" % (tag, T, e_mean.max(), e_peak.max(), same))
+    assert got["blocks"] == T
+    assert e_mean.max() <= 1.0 and e_peak.max() <= 1.0, (tag, T, float(e_mean.max()), float(e_peak.max()))
+    assert same, (tag, T, int((u32(got["mean"]) != u32(emu[0])).sum()), int((u32(got["peak"]) != u32(emu[1])).sum()))
+
+
 # ---------------------------------------------------------------- the tests' input
 
 TONE_BIN = 1000.37            # the 0 dBFS tone, in FFT bins above the centre: between two bins
@@ -154,3 +180,37 @@ def make_signal(fft_size, nsamples, seed, burst=None):
     if burst is not None:
         x += burst
     return x
+
+
+# ---------------------------------------------------------------- on-bin tones: the Hann halo made visible
+
+HALO_EDGES = (0, 128, 512, 1024)      # boundaries e - 1 | e between fftshifted bins (mod N): the circular wrap, a wave boundary inside a
+                                      # tile, a tile boundary, and a tile boundary inside an owner's walk at G = 2048
+
+
+def halo_tones(N, side):
+    """fftshifted positions of the tones on one side of every edge of HALO_EDGES: "below" = e - 1 (mod N), "above" = e.  Tones of one
+    side lie more than two bins apart, so no two of them share a bin under the three-tap window."""
+    return [(e - 1) % N if side == "below" else e for e in HALO_EDGES]
+
+
+def tone_stream(N, nsamples, positions, amp):
+    """complex128 stream: a sum of exponentials of amplitude `amp` exactly on the fftshifted bins `positions` of an N-point transform, and
+    nothing else.  On a bin a tone is continuous from block to block: every [history, new] window holds whole cycles of it."""
+    m = np.arange(nsamples, dtype=np.float64)
+    x = np.zeros(nsamples, np.complex128)
+    for s in positions:
+        x += amp * np.exp(2j * np.pi * (((s - N // 2) * m) % N) / N)
+    return x
+
+
+def tone_band_powers(N, positions, amp, bins, hann=True):
+    """Band powers of a window of tone_stream from the window's weights alone, no transform: RECT, a tone is amp^2 in its bin; HANN,
+    0.5^2 / 0.375 = 2/3 of it in bin s and 0.25^2 / 0.375 = 1/6 in each of s - 1 and s + 1 (mod N)."""
+    d = np.diff(np.sort(np.concatenate([np.asarray(positions), [min(positions) + N]])))
+    assert d.min() >= 3, "tones whose three-tap footprints overlap add up coherently: not the sum of their shares"
+    pw = np.zeros(N)
+    for s in positions:
+        for k, share in ((-1, 1 / 6), (0, 2 / 3), (1, 1 / 6)) if hann else ((0, 1.0),):
+            pw[(s + k) % N] += share * amp * amp
+    return pw.reshape(bins, N // bins).sum(axis=1)

@@ -20,15 +20,12 @@ import pytest
 import hfdl_synth as synth
 import spectrum_f64 as S
 from dumphfdl_amd import frontend as F
+from spectrum_f64 import check_against_model, u32      # (tests/test_gpu_spectrum_history.py takes them from here)
 
 pytestmark = pytest.mark.gpu
 
 T_READS = (1, 5, 32, 40)       # crossing a half and a 16 + 4 cut
 NBLK = 40
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def stream_for(fe, fs, cf, freq, seed, nblk=NBLK):
@@ -38,19 +35,6 @@ def stream_for(fe, fs, cf, freq, seed, nblk=NBLK):
     rng = np.random.default_rng(seed)
     burst = synth.synth_wideband(fs, cf, ns, [dict(freq=freq, mode=2, octets=synth.make_pdu(rng, 2), t0=0.05, amp=0.003, cfo=4.0)], noise_sigma=0.0, seed=seed)
     return S.make_signal(g.fft_size, ns, seed, burst=burst).astype(np.complex64)
-
-
-def check_against_model(tag, got, p64, ref, emu, G, T):
-    """got = spectrum_read dict; p64 / ref [T][bins] float64 per-block powers and gate references; emu = (mean, peak) of the fp32 emulation."""
-    gate = S.gate(G)
-    mean64, peak64 = np.mean(p64[:T], axis=0), np.max(p64[:T], axis=0)
-    e_mean = np.abs(got["mean"] - mean64) / (gate * np.mean(ref[:T], axis=0))
-    e_peak = np.abs(got["peak"] - peak64) / (gate * np.max(ref[:T], axis=0))
-    same = bool(np.array_equal(u32(got["mean"]), u32(emu[0])) and np.array_equal(u32(got["peak"]), u32(emu[1])))
-    print("%s T=%d: worst |mean error| / gate %.3f, |peak error| / gate %.3f, bit-identical to the fp32 emulation: %s" % (tag, T, e_mean.max(), e_peak.max(), same))
-    assert got["blocks"] == T
-    assert e_mean.max() <= 1.0 and e_peak.max() <= 1.0, (tag, T, float(e_mean.max()), float(e_peak.max()))
-    assert same, (tag, T, int((u32(got["mean"]) != u32(emu[0])).sum()), int((u32(got["peak"]) != u32(emu[1])).sum()))
 
 
 def run_geometry(tag, fe, fs, centres, xs, chan_of_rx, push):
