@@ -18,6 +18,7 @@
 #include "demod.h"
 #include "spectrum.h"
 #include "export_ring.h"
+#include "blanker.h"
 
 namespace hfdl {
 
@@ -118,6 +119,22 @@ struct ChannelExport {
 	hipEvent_t newest = nullptr;        // what the newest launch carried (null: no launch yet)
 };
 
+// Impulse-noise blanker (hfdl_gpu_frontend_blanker_enable; blanker.h): never enabled = none, no launch.  Two launches per step in front of
+// the forward FFT's first pass, on that block's FFT stream: they leave the step's blocks, blanked, as cf32 in `scratch`, and the first
+// pass reads them there.  Forward FFTs run one after the other whichever stream they are on (they share d_work and the overlap
+// history: planner.h FftOrder), so one scratch buffer serves them all.  `ev` rides on the second launch's dispatch: a read of the
+// record waits for the newest launch without a packet of its own on the stream.  Turned off again (k2 = 0) the buffers stay until the
+// front end goes: the forward FFT queued last may still be reading them.
+struct Blanker {
+	float k2 = 0.f;                     // (float)10^(threshold_db / 10); 0: off
+	DevBuf scratch;                     // [nrx][input_size] float2
+	DevBuf partial;                     // [nrx][blank_chunks(input_size)] float
+	DevBuf rec;                         // [nrx] BlankRecord
+	PinnedBuf<BlankRecord> host;        // bounce buffer of a read: one record
+	Event ev;
+	uint64_t blocks = 0;                // steps blanked so far
+};
+
 // Retune (hfdl_gpu_frontend_retune_channel): what the first call allocates and later ones keep.  The new time-domain taps go through one
 // of two page-locked buffers into `pad` (N points, zeroed once: only the first taps_length are ever written), and the tap FFT has a work
 // buffer of its own -- d_work belongs to the chain of forward FFTs, which may be running on another stream.  staged[i] rides on the first
@@ -198,6 +215,7 @@ struct hfdl_gpu_frontend {
 	std::unique_ptr<hfdl::SpectrumMonitor> mon;        // null: off
 	std::unique_ptr<hfdl::ChannelExport> exp;          // null: off
 	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
+	std::unique_ptr<hfdl::Blanker> blank;              // null: never enabled
 
 	// ---- events
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)

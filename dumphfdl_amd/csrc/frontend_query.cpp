@@ -1,5 +1,5 @@
 // frontend_query.cpp -- what a caller reads from a front end: the error text, geometry, input-done queries, timers, statistics, stage
-// taps, counters, the spectrum monitor; and the page-locked allocator.
+// taps, counters, the spectrum monitor, the blanker's switch and record; and the page-locked allocator.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -462,6 +462,52 @@ extern "C" int hfdl_gpu_frontend_spectrum_rows(hfdl_gpu_frontend *fe, int32_t rx
 	}
 	*n = (int32_t)(end - from);
 	*next_row = end;
+	return 0;
+}
+
+// ---------------------------------------------------------------- impulse-noise blanker
+
+extern "C" int hfdl_gpu_frontend_blanker_enable(hfdl_gpu_frontend *fe, float threshold_db)
+{
+	if (!(threshold_db == 0.f || (threshold_db >= BLANK_DB_MIN && threshold_db <= BLANK_DB_MAX))) return fail(HFDL_GPU_EINVAL, "blanker threshold %g dB", (double)threshold_db);
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	if (!fe->blank) {
+		if (threshold_db == 0.f) return 0;
+		HIP_TRY(hipSetDevice(fe->device));
+		const size_t K = (size_t)fe->nrx, n = (size_t)fe->geo.input_size;
+		auto b = std::make_unique<Blanker>();
+		hipError_t e = b->scratch.alloc(sizeof(float2) * K * n);
+		if (e == hipSuccess) e = b->partial.alloc(sizeof(float) * K * (size_t)blank_chunks((int)n));
+		if (e == hipSuccess) e = b->rec.zeroed(sizeof(BlankRecord) * K);
+		if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the clearing runs on the null stream, which the front end's streams do not follow
+		if (e == hipSuccess) e = b->host.alloc(1);
+		if (e == hipSuccess) e = b->ev.create(EV_NO_TIMING);
+		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "blanker buffers: %s", hipGetErrorString(e));
+		fe->blank = std::move(b);
+	}
+	fe->blank->k2 = threshold_db == 0.f ? 0.f : blank_k2(threshold_db);
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_blanker_stats *out)
+{
+	if (!fe || !out) return fail(HFDL_GPU_EINVAL, "null argument");
+	Blanker *b = fe->blank.get();
+	if (!b) return fail(HFDL_GPU_EINVAL, "the blanker was never enabled");
+	if (rx < 0 || rx >= fe->nrx) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	memset(out, 0, sizeof(*out));
+	if (b->blocks == 0) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	// the collection stream waits for the newest blanker launch (its event rode on the dispatch) and copies beside the kernels in flight
+	hipStream_t st = fe->demod.st_collect;
+	hipError_t e = hipStreamWaitEvent(st, b->ev, 0);
+	if (e == hipSuccess) e = hipMemcpyAsync(b->host.p, b->rec.as<BlankRecord>() + rx, sizeof(BlankRecord), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	HIP_TRY(e);
+	out->blocks = b->blocks;
+	out->samples_blanked = b->host.p->blanked;
+	out->last_power = b->host.p->power;
+	out->last_threshold = b->host.p->threshold;
 	return 0;
 }
 

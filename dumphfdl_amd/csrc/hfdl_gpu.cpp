@@ -275,6 +275,19 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		if (int rc = fe->timers.arm(ST_FFT, 1, done, fft_start)) return rc;
 		fft_done = done.event();
 	} else if (int rc = fe->timers.arm(ST_FFT, 1, fft_start, fft_done)) return rc;
+	if (Blanker *b = fe->blank.get(); b && b->k2 > 0.f) {
+		// the blanker: two launches in front of the first pass, which then reads the blanked cf32 blocks they leave.  The timed pair and
+		// every event other streams wait for stay on the three passes; the staging buffer's input_read event still rides on pass 1,
+		// which runs behind the blanker's last read of the input
+		BlankJob j;
+		for (int r = 0; r < fe->nrx; r++) j.fresh[r] = in.fresh[r];
+		j.out = b->scratch.as<float2>(); j.out_stride = g.input_size; j.partial = b->partial.as<float>(); j.rec = b->rec.as<BlankRecord>();
+		j.n = g.input_size; j.nrx = fe->nrx; j.fmt = fmt; j.k2 = b->k2;
+		launch_blanker(j, st, b->ev);
+		for (int r = 0; r < fe->nrx; r++) in.fresh[r] = j.out + (size_t)r * (size_t)g.input_size;
+		fmt = SFMT_CF32;
+		b->blocks++;
+	}
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
 	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, st,

@@ -118,6 +118,37 @@ extern "C" int hfdl_gpu_burst_decode(int device, const float *symbols, const int
 	return 0;
 }
 
+// the blanker's two launches as enqueue_fft queues them, on one block of one receiver
+extern "C" int hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int sample_format, float threshold_db,
+		float *out, float *power, uint64_t *blanked)
+{
+	if (!raw || !out || !power || !blanked || n < 1 || n > BLANK_N_MAX || sample_format < SFMT_CF32 || sample_format > SFMT_CU8
+			|| !(threshold_db >= BLANK_DB_MIN && threshold_db <= BLANK_DB_MAX))
+		return fail(HFDL_GPU_EINVAL, "bad arguments");
+	int rc = select_device(device);
+	if (rc) return rc;
+	DevBuf d_in, d_out, d_part, d_rec;
+	hipError_t e = d_in.upload(raw, sample_bytes(sample_format) * (size_t)n);
+	if (e == hipSuccess) e = d_out.alloc(sizeof(float2) * (size_t)n);
+	if (e == hipSuccess) e = d_part.alloc(sizeof(float) * (size_t)blank_chunks(n));
+	if (e == hipSuccess) e = d_rec.zeroed(sizeof(BlankRecord));
+	HIP_TRY(e);
+	BlankJob j;
+	j.fresh[0] = d_in.p; j.out = d_out.as<float2>(); j.out_stride = n; j.partial = d_part.as<float>(); j.rec = d_rec.as<BlankRecord>();
+	j.n = n; j.nrx = 1; j.fmt = sample_format; j.k2 = blank_k2(threshold_db);
+	StageTimer tm;
+	launch_blanker(j, nullptr);
+	g_stage_ms = tm.stop();
+	if ((rc = finish_stage())) return rc;
+	BlankRecord rec;
+	e = d_rec.fetch(&rec, sizeof(rec));
+	if (e == hipSuccess) e = d_out.fetch(out, sizeof(float2) * (size_t)n);
+	HIP_TRY(e);
+	*power = rec.power;
+	*blanked = rec.blanked;
+	return 0;
+}
+
 // frame_quality_kernel as the pipeline launches it behind K5, on K5's staged frames, without a ring: frame i writes record i
 extern "C" int hfdl_gpu_frame_quality_batch(int device, const float *symbols, const int32_t *modes, int32_t nframes, hfdl_gpu_frame_quality *out)
 {

@@ -58,6 +58,10 @@ class SpectrumRow(C.Structure):
     _fields_ = [("row", C.c_uint64), ("first_block", C.c_uint64), ("blocks", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class BlankerStats(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("samples_blanked", C.c_uint64), ("last_power", C.c_float), ("last_threshold", C.c_float)]
+
+
 class FrontendCounters(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("pdus_taken", C.c_uint32), ("pdus_dropped", C.c_uint32), ("pdu_ring_capacity", C.c_uint32)]
 
@@ -90,6 +94,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_export_enable", "hfdl_gpu_frontend_export_read",
     "hfdl_gpu_frontend_retune_channel",
     "hfdl_gpu_frontend_quality_enable", "hfdl_gpu_frontend_quality_read", "hfdl_gpu_frame_quality_batch",
+    "hfdl_gpu_frontend_blanker_enable", "hfdl_gpu_frontend_blanker_stats", "hfdl_gpu_blank_block",
 ]
 
 
@@ -220,6 +225,9 @@ def _bind(L):
     L.hfdl_gpu_frontend_quality_enable.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
     L.hfdl_gpu_frontend_quality_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int]
     L.hfdl_gpu_frame_quality_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.hfdl_gpu_frontend_blanker_enable.argtypes = [C.c_void_p, C.c_float]
+    L.hfdl_gpu_frontend_blanker_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(BlankerStats)]
+    L.hfdl_gpu_blank_block.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     return L
 
 
@@ -588,6 +596,18 @@ class Frontend:
         buf, sym, n, dropped = self.quality_read_raw(max_frames, wait)
         return [quality_to_dict(buf[i]) for i in range(n)], (sym[:n] if sym is not None else None), dropped
 
+    def blanker_enable(self, threshold_db):
+        """Wideband impulse-noise blanker (include/hfdl_gpu.h): from the next pushed block on, a new sample whose power exceeds
+        10^(threshold_db / 10) times the mean power of its receiver's block enters the transform as zero.  6 .. 60 dB; 0 turns it off."""
+        _check(self._L.hfdl_gpu_frontend_blanker_enable(self._h, float(threshold_db)), self._L)
+
+    def blanker_stats(self, rx=0):
+        """dict(blocks, samples_blanked, last_power, last_threshold) of receiver rx since the first blanker_enable(); waits for the
+        forward FFTs' side of the pipeline only."""
+        st = BlankerStats()
+        _check(self._L.hfdl_gpu_frontend_blanker_stats(self._h, rx, C.byref(st)), self._L)
+        return dict(blocks=st.blocks, samples_blanked=st.samples_blanked, last_power=np.float32(st.last_power), last_threshold=np.float32(st.last_threshold))
+
     def close(self):
         if self._h:
             self._L.hfdl_gpu_frontend_destroy(self._h)
@@ -666,6 +686,31 @@ class MultiFrontend(Frontend):
         for d in out:
             d["receiver"] = self._rx_of[d["channel"]]
         return out
+
+
+BLANK_CHUNK = 4096         # samples per workgroup of the blanker's block power (dumphfdl_amd/csrc/blanker.h)
+
+
+def blank_sum_depth(n):
+    """fp32 additions on the longest path of the blanker's block power over n samples (blanker.h blank_sum_depth): 8 + 1 of a thread
+    and 6 + 2 of the tree per chunk of 4096 samples, then ceil(chunks / 256) of a thread and 6 + 2 of the tree over the chunk sums."""
+    chunks = -(-int(n) // BLANK_CHUNK)
+    return 9 + 8 + -(-chunks // 256) + 8
+
+
+def blank_block(raw, sample_format, threshold_db, device=0):
+    """The blanker alone (hfdl_gpu_blank_block) on one block: raw = float32 / int16 / uint8 numpy array of 2 n interleaved I, Q values
+    (a complex64 array for SFMT_CF32 will do).  Returns (out: n complex64 as they would enter the transform, P: float32, blanked)."""
+    dt = {SFMT_CF32: np.float32, SFMT_CS16: np.int16, SFMT_CU8: np.uint8}[sample_format]
+    r = np.asarray(raw)
+    if sample_format == SFMT_CF32 and r.dtype == np.complex64:
+        r = np.ascontiguousarray(r).view(np.float32)
+    r = np.ascontiguousarray(r, dtype=dt)
+    n = len(r) // 2
+    out = np.zeros(n, np.complex64)
+    power, blanked = C.c_float(0), C.c_uint64(0)
+    _check(load().hfdl_gpu_blank_block(device, _p(r) if n else None, n, sample_format, float(threshold_db), _p(out) if n else None, C.byref(power), C.byref(blanked)))
+    return out, np.float32(power.value), blanked.value
 
 
 def fft_forward(x, shifted=False, device=0):

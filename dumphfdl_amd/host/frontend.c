@@ -21,6 +21,9 @@
 /* ... and the frame quality records likewise: a frame log asked of such a library is refused when the front end is created */
 #pragma weak hfdl_gpu_frontend_quality_enable
 #pragma weak hfdl_gpu_frontend_quality_read
+/* ... and the impulse-noise blanker: asked of such a library, fft_create() refuses */
+#pragma weak hfdl_gpu_frontend_blanker_enable
+#pragma weak hfdl_gpu_frontend_blanker_stats
 
 /* The optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
  * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
@@ -62,6 +65,7 @@ struct gpu_fft_block {
 	struct spectrum_settings spectrum;       /* as set when fft_create() ran */
 	struct iq_export_settings iqx;
 	char *frame_log;                         /* path, NULL = off */
+	float blanker_db;                        /* 0 = off */
 };
 
 static int g_device = 0;
@@ -93,6 +97,14 @@ int hfdl_frontend_set_frame_log(const char *path)
 {
 	free(g_frame_log);
 	g_frame_log = path ? strdup(path) : NULL;
+	return 0;
+}
+
+static float g_blanker_db;
+int hfdl_frontend_set_blanker(float threshold_db)
+{
+	if (!(threshold_db == 0.f || (threshold_db >= 6.f && threshold_db <= 60.f))) return -1;
+	g_blanker_db = threshold_db;
 	return 0;
 }
 
@@ -971,6 +983,7 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 		t->stats = hfdl_xcalloc(t->nch, sizeof(*t->stats));
 		t->fs = (double)slots[0]->sample_rate;
 		t->centerfreq = (double)slots[0]->centerfreq;
+		if (fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_enable(t->fe, fb->blanker_db) != 0) fail(t, hfdl_gpu_last_error());
 	}
 	pthread_barrier_wait(down->shared_buffer.consumers_ready);
 	gettimeofday(&t->t0, NULL);
@@ -1007,6 +1020,10 @@ static void frontend_teardown(struct fe_thread *t)
 		spectrum_csv_close(t);
 		if (t->iqx.files != NULL) write_iq_export(t->fe, &t->iqx, 1);
 		if (t->flog.file != NULL && t->flog.recs != NULL) write_frame_log(t, 1);
+		hfdl_gpu_blanker_stats bs;
+		if (t->fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_stats(t->fe, 0, &bs) == 0)
+			fprintf(stderr, "blanker: receiver 0: %llu samples blanked in %llu blocks (%g dB)\n", (unsigned long long)bs.samples_blanked,
+					(unsigned long long)bs.blocks, (double)t->fb->blanker_db);
 		publish_counters(t->fe, t->stats, (int32_t)t->nch);
 		/* requests that never came due, or came in after the last push, are not the next front end's */
 		pthread_mutex_lock(&g_retune_lock);
@@ -1108,6 +1125,12 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 		free(fb);
 		return NULL;
 	}
+	if (g_blanker_db != 0.f && (hfdl_gpu_frontend_blanker_enable == NULL || hfdl_gpu_frontend_blanker_stats == NULL)) {
+		fprintf(stderr, "blanker: this GPU library has no impulse-noise blanker\n");
+		free(fb);
+		return NULL;
+	}
+	fb->blanker_db = g_blanker_db;
 	fb->frame_log = g_frame_log ? strdup(g_frame_log) : NULL;
 	fb->decimation = decimation;
 	fb->transition_bw = transition_bw;

@@ -5,7 +5,7 @@
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
  *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
- *               [--frame-log FILE] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
+ *               [--frame-log FILE] [--blanker DB] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -20,6 +20,9 @@
  *
  * --frame-log FILE      one text line per received frame to FILE (hfdl_frontend_set_frame_log, include/hfdl_host.h): the frame's time
  *               (its PDU's ts) and frequency, mode, slot, MER in dB, symbol power, gain magnitude and phase, the worst data segment.
+ *
+ * --blanker DB          wideband impulse-noise blanker (hfdl_frontend_set_blanker, include/hfdl_host.h): a raw sample more than DB
+ *               (6 .. 60) above its block's mean power enters the forward FFT as zero; one line on stderr at the end gives the count.
  *
  * --retune SECONDS:OLD_KHZ:NEW_KHZ   move the channel on OLD_KHZ to NEW_KHZ before the first block whose first sample lies at or after
  *               SECONDS of signal (hfdl_frontend_schedule_retune, include/hfdl_host.h); repeatable, at most 64.  A request that is
@@ -120,6 +123,9 @@ int main(int argc, char **argv)
 		}
 		else if (!strcmp(argv[i], "--iq-export-scale") && i + 1 < argc) iqx_scale = (float)atof(argv[++i]);
 		else if (!strcmp(argv[i], "--frame-log") && i + 1 < argc) frame_log = argv[++i];
+		else if (!strcmp(argv[i], "--blanker") && i + 1 < argc) {
+			if (hfdl_frontend_set_blanker((float)atof(argv[++i])) != 0) { fprintf(stderr, "--blanker wants a threshold of 6 to 60 dB (or 0 = off)\n"); return 1; }
+		}
 		else if (!strcmp(argv[i], "--retune") && i + 1 < argc) {
 			double at;
 			int32_t old_hz, new_hz;

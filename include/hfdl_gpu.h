@@ -462,6 +462,32 @@ int  hfdl_gpu_frontend_quality_enable(hfdl_gpu_frontend *fe, int32_t ring_frames
 int  hfdl_gpu_frontend_quality_read(hfdl_gpu_frontend *fe, hfdl_gpu_frame_quality *out, float *symbols,
 		int32_t max_frames, int32_t *n, uint32_t *dropped, int wait);
 
+/* Wideband impulse-noise blanker (off by default: nothing is allocated or launched, and the block path is the one it is without it).
+ * Lightning static, power lines and switching supplies put microsecond impulses 30 - 50 dB above everything else into the raw samples; a
+ * channel filter of up to 2^20 + 1 taps stretches each over tens of symbols of every channel at once, so the one place to fight them is
+ * in front of the forward FFT.  The rule is stateless per block and per receiver (dumphfdl_amd/csrc/blanker.h): with P the mean of
+ * |x|^2 over the input_size NEW samples of a receiver's block, after the sample-format conversion, in fp32 and in one fixed order, and
+ * T = k2 P, k2 = (float)10^(threshold_db / 10), a sample with |x|^2 > T enters the transform as (0, 0).  Every sample is judged once,
+ * when it is new (the overlap history holds blanked values); at most a fraction 1 / k2 of a block can be blanked (Markov: 4 % at 14 dB,
+ * 25 % at 6 dB), so a level jump never blanks a whole block and nothing can get stuck; a block whose P is NaN or Inf is not blanked.
+ * Results do not depend on how blocks are pushed, polled or batched.  The spectrum monitor and tap 1 see the blanked spectra; retune,
+ * export and quality records are untouched.  It works with every entry point that takes wideband input (push_block, push_block_raw,
+ * push_blocks_raw, channelize_block, prefetched blocks; host and device-resident input); push_baseband has no wideband input.
+ * Cost: two launches per step in front of the forward FFT, on its stream -- the block is read twice in its own format and written and
+ * read once more as cf32.
+ * threshold_db: 0 = off; 6 .. 60 = on from the next pushed block, for every receiver.  The first enable allocates (nrx x input_size
+ * cf32, kept until the front end is destroyed) and may take what an allocation takes; later calls change the threshold alone and wait
+ * for nothing.  HFDL_GPU_EINVAL (any other threshold_db, NaN included; null handle) is returned before any device work. */
+int  hfdl_gpu_frontend_blanker_enable(hfdl_gpu_frontend *fe, float threshold_db);
+typedef struct {
+	uint64_t blocks, samples_blanked;       /* blocks blanked and samples zeroed of this receiver since the first enable */
+	float    last_power, last_threshold;    /* P and T of its newest blanked block */
+} hfdl_gpu_blanker_stats;
+/* Receiver rx's record.  Waits as hfdl_gpu_frontend_spectrum_read() does -- for the blanker launches queued so far, on the collection
+ * stream -- and queues nothing on the kernels' streams.  No block blanked yet: all zero.  HFDL_GPU_EINVAL: null argument, rx out of
+ * range, or a front end whose blanker was never enabled. */
+int  hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_blanker_stats *out);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */
@@ -519,6 +545,11 @@ int  hfdl_gpu_viterbi27(int device, const uint8_t *soft, int32_t nbits, int32_t 
  * bitmask bit per frame; octets = nframes * HFDL_GPU_PDU_MAX_OCTETS, lens[nframes] */
 int  hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *modes, const int32_t *bitmask_lsb,
 		int32_t nframes, uint8_t *octets, int32_t *lens);
+/* the blanker (hfdl_gpu_frontend_blanker_enable above) alone, by the device functions of the front end: raw = n samples
+ * (1 .. 2^24) of sample_format; out = the n cf32 samples as they would enter the transform, *power = P, *blanked = samples zeroed.
+ * threshold_db 6 .. 60.  Every argument is checked before a device is selected. */
+int  hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int sample_format, float threshold_db,
+		float *out, float *power, uint64_t *blanked);
 /* the frame quality figures (hfdl_gpu_frame_quality above) of a batch, by the device function of the front end's records: symbols
  * and modes as for hfdl_gpu_burst_decode; out[nframes].  mode, nsym, segments and the five figures with seg_err_power are filled;
  * what only a front end knows (sample_index, channel, freq, bitmask_lsb, the training counts, the three channel fields) is 0. */

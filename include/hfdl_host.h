@@ -223,6 +223,12 @@ int           hfdl_frontend_set_iq_export(const char *dir, const int32_t *freqs,
  * device's ring dropped because the log fell behind are counted on stderr when the front end stops.  path NULL: off.  Returns 0.  With a
  * GPU library that lacks the records, fft_create() fails with a message on stderr. */
 int           hfdl_frontend_set_frame_log(const char *path);
+/* Impulse-noise blanker of the front end created by the next fft_create() (include/hfdl_gpu.h, "Wideband impulse-noise blanker"); not
+ * in the reference, whose users blank in the SDR -- a front end that ingests a recorder's raw samples is the SDR.  threshold_db 6 .. 60:
+ * a new sample more than that above its block's mean power enters the transform as zero; 0: off (the default).  When the front end
+ * stops, one line on stderr gives the samples blanked and the blocks seen.  Returns 0, or -1 for any other threshold_db (NaN included).
+ * With a GPU library that lacks the blanker, fft_create() fails with a message on stderr. */
+int           hfdl_frontend_set_blanker(float threshold_db);
 /* Retune a channel of the running front end (include/hfdl_gpu.h, hfdl_gpu_frontend_retune_channel); not in the reference, which is
  * restarted to follow the ground stations' frequency changes.  Callable from any thread: the request old_freq -> new_freq (Hz) joins a
  * list (at most 64 waiting) that the front-end thread applies between two pushes -- blocks pushed before keep old_freq in their PDUs,
