@@ -26,8 +26,11 @@ for o in $KERNEL_OBJS; do
 	$HIPCC $COMMON $contract $included -c $o.hip -o $BUILD/$o.o & pids="$pids $!"
 	objs="$objs $BUILD/$o.o"
 done
+# The shim's HOST code is compiled for size (-Xarch_host -Os: launch bookkeeping, checks and copies, nothing a block's time depends on);
+# the device pass keeps -O3, and the library's device code is byte for byte what it is without the flag.  The
+# library's size is pinned (tests/test_host_logic_cpu.py).
 for o in $SHIM_OBJS; do
-	$HIPCC $COMMON -x hip -c $o.cpp -o $BUILD/$o.o & pids="$pids $!"
+	$HIPCC $COMMON -Xarch_host -Os -x hip -c $o.cpp -o $BUILD/$o.o & pids="$pids $!"
 	objs="$objs $BUILD/$o.o"
 done
 for p in $pids; do wait $p; done          # set -e: a failed compile stops the build here instead of linking stale objects

@@ -19,6 +19,7 @@
 #include "spectrum.h"
 #include "export_ring.h"
 #include "blanker.h"
+#include "notch.h"
 
 namespace hfdl {
 
@@ -135,6 +136,29 @@ struct Blanker {
 	uint64_t blocks = 0;                // steps blanked so far
 };
 
+// Adaptive carrier canceller (hfdl_gpu_frontend_notch_enable; notch.h): never enabled = none, no launch.  One launch per closed half on
+// stream B, in the half's hand-over to the demodulator (hfdl_gpu.cpp launch_demod): it reads the half's rows of d_chan_all and leaves
+// what the demodulator reads in `out`, a second buffer of d_chan_all's shape -- the channel export and stage tap 3 keep reading the
+// channelizer's own output.  Stream order is the only ordering: the canceller of half h + 2 overwrites `out` behind the demodulators of
+// half h, and the inverse FFT into a half waits for that half's last demodulator, which is queued behind the canceller that read it.
+// `ev` rides on the launch's dispatch: a read of a record waits for the newest launch without a packet of its own on the stream.
+// Turned off again (mu = 0) the buffers stay until the front end goes.
+struct Notch {
+	float mu = 0.f;                     // 0: off
+	int nsel = 0;
+	std::vector<bool> selected;         // [nch]
+	DevBuf out;                         // [2][half_blocks][nch][outs] float2
+	DevBuf sel;                         // [nch] int32: the selected channels, nsel of them
+	DevBuf state;                       // [nch][NOTCH_STATE_FLOATS] float
+	DevBuf rec;                         // [nch] NotchRecord
+	PinnedBuf<NotchRecord> host;        // bounce buffer of a read: one record
+	PinnedBuf<int32_t> host_sel;        // [nch] where an enable's selection is uploaded from ...
+	Event staged;                       // ... recorded behind that upload: the next enable waits for it before it writes host_sel again
+	bool staging = false;
+	Event ev;
+	bool launched = false;              // since the newest enable
+};
+
 // Retune (hfdl_gpu_frontend_retune_channel): what the first call allocates and later ones keep.  The new time-domain taps go through one
 // of two page-locked buffers into `pad` (N points, zeroed once: only the first taps_length are ever written), and the tap FFT has a work
 // buffer of its own -- d_work belongs to the chain of forward FFTs, which may be running on another stream.  staged[i] rides on the first
@@ -216,6 +240,7 @@ struct hfdl_gpu_frontend {
 	std::unique_ptr<hfdl::ChannelExport> exp;          // null: off
 	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
 	std::unique_ptr<hfdl::Blanker> blank;              // null: never enabled
+	std::unique_ptr<hfdl::Notch> notch;                // null: never enabled
 
 	// ---- events
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)

@@ -254,7 +254,7 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 	const Geometry &g = fe->geo;
 	// the channelizer's own buffers hold every block of the newest half: `back` blocks before the newest one
 	if (back < 0 || back > fe->last_index) return fail(HFDL_GPU_ERANGE, "block %d back is not held any more (%d are)", back, fe->last_index);
-	if (back && what != HFDL_GPU_TAP_SPECTRUM && what != HFDL_GPU_TAP_CHAN_OUT && what != HFDL_GPU_TAP_NCO_PHASORS)
+	if (back && what != HFDL_GPU_TAP_SPECTRUM && what != HFDL_GPU_TAP_CHAN_OUT && what != HFDL_GPU_TAP_NCO_PHASORS && what != HFDL_GPU_TAP_NOTCH_OUT)
 		return fail(HFDL_GPU_EINVAL, "tap %d holds the last launch only", what);
 	const int slot = fe->last_slot - back, index = fe->last_index - back;
 	// (the spectrum tap of a one-receiver front end ignores `channel`; with several receivers it selects the channel's receiver)
@@ -276,10 +276,15 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 		HIP_TRY(hipMemcpy(dst, plain.p, sizeof(float2) * (size_t)g.n, hipMemcpyDeviceToHost));
 		*n_floats = 2 * (size_t)g.n;
 		return 0; }
-	case HFDL_GPU_TAP_CHAN_OUT: {
+	case HFDL_GPU_TAP_CHAN_OUT:
+	case HFDL_GPU_TAP_NOTCH_OUT: {
+		// the channelizer's own row, or the same row of the canceller's buffer: what the demodulator read
+		const Notch *nt = fe->notch.get();
+		if (what == HFDL_GPU_TAP_NOTCH_OUT && !(nt && nt->mu > 0.f)) return fail(HFDL_GPU_EINVAL, "tap %d: the canceller is off", what);
 		int cnt = 0;
 		HIP_TRY(hipMemcpy(&cnt, fe->cnt_slot(slot) + channel, sizeof(cnt), hipMemcpyDeviceToHost));
-		src = fe->chan_slot(slot) + (size_t)channel * g.outs; nf = 2 * (size_t)cnt; break; }
+		src = (what == HFDL_GPU_TAP_CHAN_OUT ? fe->chan_slot(slot) : nt->out.as<float2>() + (size_t)slot * (size_t)g.nch * (size_t)g.outs) + (size_t)channel * g.outs;
+		nf = 2 * (size_t)cnt; break; }
 	case HFDL_GPU_TAP_NCO_PHASORS: {
 		int cnt = 0;
 		HIP_TRY(hipMemcpy(&cnt, fe->cnt_slot(slot) + channel, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -508,6 +513,33 @@ extern "C" int hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx
 	out->samples_blanked = b->host.p->blanked;
 	out->last_power = b->host.p->power;
 	out->last_threshold = b->host.p->threshold;
+	return 0;
+}
+
+// ---------------------------------------------------------------- carrier canceller (its switch is the pipeline's: hfdl_gpu.cpp)
+
+static_assert(HFDL_GPU_NOTCH_STATE_FLOATS == NOTCH_STATE_FLOATS, "include/hfdl_gpu.h and notch.h name the same state");
+
+extern "C" int hfdl_gpu_frontend_notch_stats(hfdl_gpu_frontend *fe, int32_t channel, hfdl_gpu_notch_stats *out)
+{
+	if (!fe || !out) return fail(HFDL_GPU_EINVAL, "null argument");
+	Notch *n = fe->notch.get();
+	if (!n) return fail(HFDL_GPU_EINVAL, "the canceller was never enabled");
+	if (channel < 0 || channel >= fe->geo.nch || !n->selected[(size_t)channel]) return fail(HFDL_GPU_EINVAL, "channel %d is out of range or not selected", channel);
+	memset(out, 0, sizeof(*out));
+	if (!n->launched) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	// the collection stream waits for the newest canceller launch (its event rode on the dispatch) and copies beside the kernels in flight
+	hipStream_t st = fe->demod.st_collect;
+	hipError_t e = hipStreamWaitEvent(st, n->ev, 0);
+	if (e == hipSuccess) e = hipMemcpyAsync(n->host.p, n->rec.as<NotchRecord>() + channel, sizeof(NotchRecord), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	HIP_TRY(e);
+	out->blocks = n->host.p->blocks;
+	out->resets = n->host.p->resets;
+	out->last_in_power = n->host.p->in_power;
+	out->last_out_power = n->host.p->out_power;
+	out->tap_energy = n->host.p->tap_energy;
 	return 0;
 }
 

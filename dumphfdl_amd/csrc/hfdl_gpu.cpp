@@ -1,5 +1,5 @@
 // hfdl_gpu.cpp -- C-ABI shim of libhfdl_gpu.so, the pipeline: input staging, the forward FFT of a pushed block, the fold / inverse FFT
-// of a closed half, the demodulator launches, sync and poll.  (frontend.h names the other translation units of the shim.)
+// of a closed half, the carrier canceller's switch, the demodulator launches, sync and poll.  (frontend.h names the other translation units of the shim.)
 // The only C++ a C host ever sees is through include/hfdl_gpu.h (extern "C", plain pointers).
 #include <algorithm>
 #include "frontend.h"
@@ -213,6 +213,22 @@ extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, hipEvent_t ready)
 {
 	const int slot0 = buf * fe->half_blocks;
+	if (Notch *n = fe->notch.get(); n && n->mu > 0.f) {
+		// the carrier canceller: stream B waits for the half here, the canceller leaves the half's rows in its own buffer -- the selected
+		// channels' cancelled, the others' word for word -- and the demodulators read that buffer, behind it on the stream
+		const Geometry &g = fe->geo;
+		const size_t at = (size_t)slot0 * (size_t)g.nch * (size_t)g.outs;
+		float2 *out = n->out.as<float2>() + at;
+		if (ready) HIP_TRY(hipStreamWaitEvent(fe->stream_b, ready, 0));
+		if (n->nsel < g.nch) HIP_TRY(hipMemcpyAsync(out, fe->chan_slot(slot0), sizeof(float2) * (size_t)nblk * (size_t)g.nch * (size_t)g.outs, hipMemcpyDeviceToDevice, fe->stream_b));
+		NotchJob j;
+		j.in = fe->chan_slot(slot0); j.out = out; j.cnt = fe->cnt_slot(slot0); j.sel = n->sel.as<int32_t>();
+		j.state = n->state.as<float>(); j.rec = n->rec.as<NotchRecord>();
+		j.nch = g.nch; j.outs = g.outs; j.nblk = nblk; j.nsel = n->nsel; j.mu = n->mu;
+		launch_notch(j, fe->stream_b, n->ev);
+		n->launched = true;
+		return fe->demod.launch_half(out, fe->cnt_slot(slot0), nblk, buf, nullptr, fe->stream_b, fe->stream_d, fe->timers);
+	}
 	return fe->demod.launch_half(fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, buf, ready, fe->stream_b, fe->stream_d, fe->timers);
 }
 
@@ -525,11 +541,66 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), dst, true, fe->stream, lay, nullptr, NcoJob(), r.staged[sb]);
 	launch_retune_channelizer(fe->d_cc, fe->d_nco, fe->d_ph_cont, channel, k, fe->stream, r.done.signal());
 	fe->demod.enqueue_retune(channel, new_freq_hz, fe->stream_b, fe->stream_d);
+	// the retuned channel meets a fresh canceller: its taps and delay line go where its demodulator state goes, behind the closed half on B
+	if (Notch *n = fe->notch.get()) HIP_TRY(hipMemsetAsync(n->state.as<float>() + (size_t)channel * NOTCH_STATE_FLOATS, 0, sizeof(float) * NOTCH_STATE_FLOATS, fe->stream_b));
 	HIP_TRY(hipGetLastError());
 	fe->order.retune();
 	fe->freqs[(size_t)channel] = new_freq_hz;
 	fe->cc[(size_t)channel] = k;
 	r.calls++;
+	return 0;
+}
+
+// ---------------------------------------------------------------- carrier canceller
+
+// From this call on the selected channels are cancelled with step `mu`, each from zero state; blocks pushed before it are handed over
+// as they would have been.  The half being filled is closed as a retune closes it; the new selection and the cleared state follow the
+// closed half's canceller and demodulators on stream B.  Everything is checked and allocated before the first launch.
+extern "C" int hfdl_gpu_frontend_notch_enable(hfdl_gpu_frontend *fe, const int32_t *channels, int32_t nsel, float mu)
+{
+	if (!(mu == 0.f || notch_mu_valid(mu))) return fail(HFDL_GPU_EINVAL, "canceller step %g: 0 (off) or %g .. %g", (double)mu, (double)NOTCH_MU_MIN, (double)NOTCH_MU_MAX);
+	if (!fe || nsel < 0 || (nsel > 0 && !channels)) return fail(HFDL_GPU_EINVAL, "null argument");
+	const int nch = fe->geo.nch;
+	std::vector<int32_t> sel;
+	std::vector<bool> seen((size_t)nch, channels == nullptr || nsel == 0);
+	if (channels && nsel > 0) {
+		for (int i = 0; i < nsel; i++) {
+			if (channels[i] < 0 || channels[i] >= nch || seen[(size_t)channels[i]]) return fail(HFDL_GPU_EINVAL, "canceller: channel %d out of range or listed twice", channels[i]);
+			seen[(size_t)channels[i]] = true;
+		}
+		sel.assign(channels, channels + nsel);
+	} else for (int c = 0; c < nch; c++) sel.push_back(c);
+	if (!fe->notch && mu == 0.f) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	if (!fe->notch) {
+		auto n = std::make_unique<Notch>();
+		hipError_t e = n->out.alloc(sizeof(float2) * 2 * (size_t)fe->half_blocks * (size_t)nch * (size_t)fe->geo.outs);
+		if (e == hipSuccess) e = n->sel.alloc(sizeof(int32_t) * (size_t)nch);
+		if (e == hipSuccess) e = n->state.alloc(sizeof(float) * NOTCH_STATE_FLOATS * (size_t)nch);
+		if (e == hipSuccess) e = n->rec.alloc(sizeof(NotchRecord) * (size_t)nch);
+		if (e == hipSuccess) e = n->host.alloc(1);
+		if (e == hipSuccess) e = n->host_sel.alloc((size_t)nch);
+		if (e == hipSuccess) e = n->staged.create(EV_NO_TIMING);
+		if (e == hipSuccess) e = n->ev.create(EV_NO_TIMING);
+		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "canceller buffers: %s", hipGetErrorString(e));
+		fe->notch = std::move(n);
+	}
+	// the boundary: what was pushed so far goes to the demodulator under the old setting (a held-back half first, as a retune does)
+	if (int rc = flush_pending_demod(fe, false)) return rc;
+	if (int rc = close_half(fe, true)) return rc;
+	Notch &n = *fe->notch;
+	n.mu = mu;
+	if (mu == 0.f) return 0;
+	if (n.staging) HIP_TRY(hipEventSynchronize(n.staged));       // the upload of the enable before this one has read the page-locked list
+	std::copy(sel.begin(), sel.end(), n.host_sel.p);
+	HIP_TRY(hipMemcpyAsync(n.sel.p, n.host_sel.p, sizeof(int32_t) * sel.size(), hipMemcpyHostToDevice, fe->stream_b));
+	HIP_TRY(hipEventRecord(n.staged, fe->stream_b));
+	n.staging = true;
+	HIP_TRY(hipMemsetAsync(n.state.p, 0, sizeof(float) * NOTCH_STATE_FLOATS * (size_t)nch, fe->stream_b));
+	HIP_TRY(hipMemsetAsync(n.rec.p, 0, sizeof(NotchRecord) * (size_t)nch, fe->stream_b));
+	n.nsel = (int)sel.size();
+	n.selected = seen;
+	n.launched = false;
 	return 0;
 }
 

@@ -149,6 +149,32 @@ extern "C" int hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int 
 	return 0;
 }
 
+// the carrier canceller as the pipeline launches it in a half's hand-over: one "block" of nch rows of n samples each, every channel selected
+extern "C" int hfdl_gpu_notch_rows(int device, const float *x, int32_t nch, int32_t n, float mu, float *state, float *y)
+{
+	if (!x || !y || nch < 1 || n < 1 || (int64_t)nch * n > ((int64_t)1 << 27) || !notch_mu_valid(mu)) return fail(HFDL_GPU_EINVAL, "bad arguments");
+	int rc = select_device(device);
+	if (rc) return rc;
+	const size_t row_bytes = sizeof(float2) * (size_t)nch * (size_t)n, state_bytes = sizeof(float) * NOTCH_STATE_FLOATS * (size_t)nch;
+	DevBuf d_in, d_out, d_state, d_rec;
+	hipError_t e = d_in.upload(x, row_bytes);
+	if (e == hipSuccess) e = d_out.alloc(row_bytes);
+	if (e == hipSuccess) e = state ? d_state.upload(state, state_bytes) : d_state.zeroed(state_bytes);
+	if (e == hipSuccess) e = d_rec.zeroed(sizeof(NotchRecord) * (size_t)nch);
+	HIP_TRY(e);
+	NotchJob j;
+	j.in = d_in.as<const float2>(); j.out = d_out.as<float2>(); j.state = d_state.as<float>(); j.rec = d_rec.as<NotchRecord>();
+	j.nch = nch; j.outs = n; j.nblk = 1; j.nsel = nch; j.mu = mu;
+	StageTimer tm;
+	launch_notch(j, nullptr);
+	g_stage_ms = tm.stop();
+	if ((rc = finish_stage())) return rc;
+	e = d_out.fetch(y, row_bytes);
+	if (e == hipSuccess && state) e = d_state.fetch(state, state_bytes);
+	HIP_TRY(e);
+	return 0;
+}
+
 // frame_quality_kernel as the pipeline launches it behind K5, on K5's staged frames, without a ring: frame i writes record i
 extern "C" int hfdl_gpu_frame_quality_batch(int device, const float *symbols, const int32_t *modes, int32_t nframes, hfdl_gpu_frame_quality *out)
 {

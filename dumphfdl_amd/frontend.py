@@ -7,7 +7,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PDU_MAX_OCTETS = 960
 
-TAP_SPECTRUM, TAP_FILTER, TAP_CHAN_OUT, TAP_RESAMPLED, TAP_MF_OUT, TAP_SYMBOLS, TAP_AGC_LEVEL, TAP_PHASE_CYCLES, TAP_NCO_PHASORS = range(1, 10)
+TAP_SPECTRUM, TAP_FILTER, TAP_CHAN_OUT, TAP_RESAMPLED, TAP_MF_OUT, TAP_SYMBOLS, TAP_AGC_LEVEL, TAP_PHASE_CYCLES, TAP_NCO_PHASORS, TAP_NOTCH_OUT = range(1, 11)
 
 
 SFMT_CF32, SFMT_CS16, SFMT_CU8 = 0, 1, 2
@@ -62,6 +62,10 @@ class BlankerStats(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("samples_blanked", C.c_uint64), ("last_power", C.c_float), ("last_threshold", C.c_float)]
 
 
+class NotchStats(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("resets", C.c_uint64), ("last_in_power", C.c_float), ("last_out_power", C.c_float), ("tap_energy", C.c_float)]
+
+
 class FrontendCounters(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("pdus_taken", C.c_uint32), ("pdus_dropped", C.c_uint32), ("pdu_ring_capacity", C.c_uint32)]
 
@@ -95,6 +99,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_retune_channel",
     "hfdl_gpu_frontend_quality_enable", "hfdl_gpu_frontend_quality_read", "hfdl_gpu_frame_quality_batch",
     "hfdl_gpu_frontend_blanker_enable", "hfdl_gpu_frontend_blanker_stats", "hfdl_gpu_blank_block",
+    "hfdl_gpu_frontend_notch_enable", "hfdl_gpu_frontend_notch_stats", "hfdl_gpu_notch_rows",
 ]
 
 
@@ -228,6 +233,9 @@ def _bind(L):
     L.hfdl_gpu_frontend_blanker_enable.argtypes = [C.c_void_p, C.c_float]
     L.hfdl_gpu_frontend_blanker_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(BlankerStats)]
     L.hfdl_gpu_blank_block.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.hfdl_gpu_frontend_notch_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]
+    L.hfdl_gpu_frontend_notch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(NotchStats)]
+    L.hfdl_gpu_notch_rows.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -608,6 +616,25 @@ class Frontend:
         _check(self._L.hfdl_gpu_frontend_blanker_stats(self._h, rx, C.byref(st)), self._L)
         return dict(blocks=st.blocks, samples_blanked=st.samples_blanked, last_power=np.float32(st.last_power), last_threshold=np.float32(st.last_threshold))
 
+    def notch_enable(self, mu, channels=None):
+        """Adaptive carrier canceller (include/hfdl_gpu.h) in front of the demodulator of `channels` (None: every channel), each from
+        zero state, for the blocks pushed from now on.  mu 1e-5 .. 0.05; 0 turns it off."""
+        sel = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        _check(self._L.hfdl_gpu_frontend_notch_enable(self._h, _p(sel) if sel is not None and len(sel) else None, 0 if sel is None else len(sel), float(mu)), self._L)
+
+    def notch_stats(self, channel):
+        """dict(blocks, resets, last_in_power, last_out_power, tap_energy) of a selected channel since notch_enable(); waits for the
+        canceller launches queued so far only."""
+        st = NotchStats()
+        _check(self._L.hfdl_gpu_frontend_notch_stats(self._h, channel, C.byref(st)), self._L)
+        return dict(blocks=st.blocks, resets=st.resets, last_in_power=np.float32(st.last_in_power), last_out_power=np.float32(st.last_out_power),
+                    tap_energy=np.float32(st.tap_energy))
+
+    @staticmethod
+    def notch_rows(x, mu, state=None, device=0):
+        """The canceller alone (module-level notch_rows)."""
+        return notch_rows(x, mu, state, device)
+
     def close(self):
         if self._h:
             self._L.hfdl_gpu_frontend_destroy(self._h)
@@ -711,6 +738,23 @@ def blank_block(raw, sample_format, threshold_db, device=0):
     power, blanked = C.c_float(0), C.c_uint64(0)
     _check(load().hfdl_gpu_blank_block(device, _p(r) if n else None, n, sample_format, float(threshold_db), _p(out) if n else None, C.byref(power), C.byref(blanked)))
     return out, np.float32(power.value), blanked.value
+
+
+NOTCH_STATE_FLOATS = 174   # HFDL_GPU_NOTCH_STATE_FLOATS: 32 taps (re, im), then the last 55 inputs (re, im), newest first
+
+
+def notch_rows(x, mu, state=None, device=0):
+    """The carrier canceller alone (hfdl_gpu_notch_rows): x = [nch][n] complex64, every row a channel's next n samples; state =
+    [nch][NOTCH_STATE_FLOATS] float32 carried from an earlier call, or None for fresh channels.  Returns (y [nch][n] complex64, the
+    state after the rows)."""
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    if x.ndim == 1:
+        x = x[None, :]
+    nch, n = x.shape
+    st = np.zeros((nch, NOTCH_STATE_FLOATS), np.float32) if state is None else np.array(state, dtype=np.float32, order="C").reshape(nch, NOTCH_STATE_FLOATS)
+    y = np.zeros((nch, n), np.complex64)
+    _check(load().hfdl_gpu_notch_rows(device, _p(x) if x.size else None, nch, n, float(mu), _p(st), _p(y) if y.size else None))
+    return y, st
 
 
 def fft_forward(x, shifted=False, device=0):

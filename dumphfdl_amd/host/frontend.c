@@ -24,6 +24,9 @@
 /* ... and the impulse-noise blanker: asked of such a library, fft_create() refuses */
 #pragma weak hfdl_gpu_frontend_blanker_enable
 #pragma weak hfdl_gpu_frontend_blanker_stats
+/* ... and the adaptive carrier canceller likewise */
+#pragma weak hfdl_gpu_frontend_notch_enable
+#pragma weak hfdl_gpu_frontend_notch_stats
 
 /* The optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
  * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
@@ -56,6 +59,16 @@ static void iq_export_settings_free(struct iq_export_settings *s)
 	free((int32_t *)s->freqs);
 }
 
+struct notch_settings { float mu; int32_t *freqs_khz; int32_t nfreqs; };                                   /* nfreqs 0 = every channel */
+
+static struct notch_settings notch_settings_copy(const struct notch_settings *s)
+{
+	struct notch_settings c = *s;
+	c.freqs_khz = s->nfreqs > 0 ? hfdl_xcalloc((size_t)s->nfreqs, sizeof(int32_t)) : NULL;
+	if (s->nfreqs > 0) memcpy(c.freqs_khz, s->freqs_khz, (size_t)s->nfreqs * sizeof(int32_t));
+	return c;
+}
+
 struct gpu_fft_block {
 	struct block block;
 	int32_t decimation;
@@ -66,6 +79,7 @@ struct gpu_fft_block {
 	struct iq_export_settings iqx;
 	char *frame_log;                         /* path, NULL = off */
 	float blanker_db;                        /* 0 = off */
+	struct notch_settings notch;             /* mu 0 = off */
 };
 
 static int g_device = 0;
@@ -106,6 +120,41 @@ int hfdl_frontend_set_blanker(float threshold_db)
 	if (!(threshold_db == 0.f || (threshold_db >= 6.f && threshold_db <= 60.f))) return -1;
 	g_blanker_db = threshold_db;
 	return 0;
+}
+
+static struct notch_settings g_notch;
+int hfdl_frontend_set_notch(float mu, const int32_t *freqs_khz, int n)
+{
+	if (!(mu == 0.f || (mu >= 1e-5f && mu <= 0.05f)) || n < 0 || n > 4096 || (n > 0 && freqs_khz == NULL)) return -1;
+	const struct notch_settings given = { mu, (int32_t *)freqs_khz, n };
+	const struct notch_settings copy = notch_settings_copy(&given);
+	free(g_notch.freqs_khz);
+	g_notch = copy;
+	return 0;
+}
+
+/* the canceller of a new front end: the listed frequencies become channel indices.  0, or -1 with the reason in *why */
+static int notch_start(hfdl_gpu_frontend *fe, const struct notch_settings *s, const int32_t *freqs, size_t nch, const char **why)
+{
+	static char text[96];
+	int32_t *sel = hfdl_xcalloc(s->nfreqs > 0 ? (size_t)s->nfreqs : 1, sizeof(int32_t));
+	int rc = 0;
+	for (int32_t i = 0; i < s->nfreqs && rc == 0; i++) {
+		size_t c = 0;
+		while (c < nch && freqs[c] != s->freqs_khz[i] * 1000) c++;
+		if (c == nch) {
+			snprintf(text, sizeof(text), "notch: %d kHz is not a channel of this front end", s->freqs_khz[i]);
+			*why = text;
+			rc = -1;
+		}
+		sel[i] = (int32_t)c;
+	}
+	if (rc == 0 && hfdl_gpu_frontend_notch_enable(fe, s->nfreqs > 0 ? sel : NULL, s->nfreqs, s->mu) != 0) {
+		*why = hfdl_gpu_last_error();
+		rc = -1;
+	}
+	free(sel);
+	return rc;
 }
 
 /* ---- spectrum monitor: one rtl_power-compatible CSV line from a row of band powers (plain C, no device call; kept in this file
@@ -984,6 +1033,8 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 		t->fs = (double)slots[0]->sample_rate;
 		t->centerfreq = (double)slots[0]->centerfreq;
 		if (fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_enable(t->fe, fb->blanker_db) != 0) fail(t, hfdl_gpu_last_error());
+		const char *why = NULL;
+		if (t->ok && fb->notch.mu != 0.f && notch_start(t->fe, &fb->notch, t->freqs, t->nch, &why) != 0) fail(t, why);
 	}
 	pthread_barrier_wait(down->shared_buffer.consumers_ready);
 	gettimeofday(&t->t0, NULL);
@@ -1024,6 +1075,14 @@ static void frontend_teardown(struct fe_thread *t)
 		if (t->fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_stats(t->fe, 0, &bs) == 0)
 			fprintf(stderr, "blanker: receiver 0: %llu samples blanked in %llu blocks (%g dB)\n", (unsigned long long)bs.samples_blanked,
 					(unsigned long long)bs.blocks, (double)t->fb->blanker_db);
+		/* one line per cancelled channel (a channel that was not selected has no record: its call fails and prints nothing) */
+		for (size_t c = 0; t->fb->notch.mu != 0.f && c < t->nch; c++) {
+			hfdl_gpu_notch_stats ns;
+			if (hfdl_gpu_frontend_notch_stats(t->fe, (int32_t)c, &ns) == 0)
+				fprintf(stderr, "notch: %d Hz: %llu blocks, %llu tap resets, last block %.4g -> %.4g, tap energy %.4g (mu %g)\n", t->freqs[c],
+						(unsigned long long)ns.blocks, (unsigned long long)ns.resets, (double)ns.last_in_power, (double)ns.last_out_power,
+						(double)ns.tap_energy, (double)t->fb->notch.mu);
+		}
 		publish_counters(t->fe, t->stats, (int32_t)t->nch);
 		/* requests that never came due, or came in after the last push, are not the next front end's */
 		pthread_mutex_lock(&g_retune_lock);
@@ -1130,7 +1189,13 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 		free(fb);
 		return NULL;
 	}
+	if (g_notch.mu != 0.f && (hfdl_gpu_frontend_notch_enable == NULL || hfdl_gpu_frontend_notch_stats == NULL)) {
+		fprintf(stderr, "notch: this GPU library has no carrier canceller\n");
+		free(fb);
+		return NULL;
+	}
 	fb->blanker_db = g_blanker_db;
+	fb->notch = notch_settings_copy(&g_notch);
 	fb->frame_log = g_frame_log ? strdup(g_frame_log) : NULL;
 	fb->decimation = decimation;
 	fb->transition_bw = transition_bw;
@@ -1152,5 +1217,6 @@ void fft_destroy(struct block *fft_block)
 	spectrum_settings_free(&fb->spectrum);
 	iq_export_settings_free(&fb->iqx);
 	free(fb->frame_log);
+	free(fb->notch.freqs_khz);
 	free(fb);
 }

@@ -5,7 +5,7 @@
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
  *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
- *               [--frame-log FILE] [--blanker DB] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
+ *               [--frame-log FILE] [--blanker DB] [--notch MU[:KHZ,...]] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -23,6 +23,10 @@
  *
  * --blanker DB          wideband impulse-noise blanker (hfdl_frontend_set_blanker, include/hfdl_host.h): a raw sample more than DB
  *               (6 .. 60) above its block's mean power enters the forward FFT as zero; one line on stderr at the end gives the count.
+ *
+ * --notch MU[:KHZ,KHZ,...]   adaptive carrier canceller (hfdl_frontend_set_notch, include/hfdl_host.h) with step MU (1e-5 .. 0.05; 0.002
+ *               is the tested one) in front of the demodulator of the listed channels, or of every channel; one line per cancelled
+ *               channel on stderr at the end.
  *
  * --retune SECONDS:OLD_KHZ:NEW_KHZ   move the channel on OLD_KHZ to NEW_KHZ before the first block whose first sample lies at or after
  *               SECONDS of signal (hfdl_frontend_schedule_retune, include/hfdl_host.h); repeatable, at most 64.  A request that is
@@ -125,6 +129,21 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--frame-log") && i + 1 < argc) frame_log = argv[++i];
 		else if (!strcmp(argv[i], "--blanker") && i + 1 < argc) {
 			if (hfdl_frontend_set_blanker((float)atof(argv[++i])) != 0) { fprintf(stderr, "--blanker wants a threshold of 6 to 60 dB (or 0 = off)\n"); return 1; }
+		}
+		else if (!strcmp(argv[i], "--notch") && i + 1 < argc) {
+			/* MU[:KHZ,KHZ,...] */
+			static int32_t khz[4096];
+			int n = 0;
+			char *end = NULL;
+			const float mu = strtof(argv[++i], &end);
+			int bad = end == argv[i] || (*end != '\0' && *end != ':');
+			while (!bad && *end != '\0') {
+				const char *at = end + 1;
+				const double f = strtod(at, &end);
+				bad = end == at || (*end != '\0' && *end != ',') || n == 4096;
+				if (!bad) khz[n++] = (int32_t)lround(f);
+			}
+			if (bad || hfdl_frontend_set_notch(mu, khz, n) != 0) { fprintf(stderr, "--notch wants MU[:KHZ,KHZ,...] with a step MU of 1e-5 to 0.05 (or 0 = off)\n"); return 1; }
 		}
 		else if (!strcmp(argv[i], "--retune") && i + 1 < argc) {
 			double at;

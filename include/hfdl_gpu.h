@@ -488,6 +488,37 @@ typedef struct {
  * range, or a front end whose blanker was never enabled. */
 int  hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_blanker_stats *out);
 
+/* Adaptive carrier canceller per channel (off by default: nothing is allocated or launched, and the block path differs by one host
+ * branch).  Steady carriers inside a channel's 2.4 kHz passband -- broadcast and utility carriers, CW, receiver birdies -- pass the
+ * channel filter, and a tone a few dB above the burst defeats the preamble search and the slicer.  Between the channelizer's output and
+ * the demodulator, a selected channel runs a normalised-LMS line canceller (dumphfdl_amd/csrc/notch.h): 32 complex taps predict the
+ * sample from the channel's own past 24 samples back, the prediction is taken away, and the taps follow with step mu / (power in the
+ * delay line).  fp32 in one fixed order; the state is carried sample by sample across blocks, so results do not depend on how blocks
+ * are pushed, polled or batched.  A sample that is not finite never reaches the taps; taps whose energy is not finite or exceeds 4 at
+ * the end of a block are set to zero and the event is counted: nothing can stay stuck.  One such reset is to be expected where a
+ * channel's samples begin out of nothing: enabled before a front end's first block, the canceller meets the channel filter's start-up
+ * ramp (some 60 samples rising from 1e-9 to the signal's level), the normalised step runs away on it, that block's row is spoilt and
+ * the reset at its end puts the channel right.
+ * What sees what: the channel export and HFDL_GPU_TAP_CHAN_OUT read the raw channel (the canceller writes a buffer of its own, of
+ * the channelizer output's size: 224 MiB at 40 Msps / 256 channels); the spectrum monitor sees nothing of it; demodulator, burst decoder,
+ * HFDL_GPU_TAP_NOTCH_OUT and the frame quality records see the cancelled samples.  An unselected channel's samples reach the demodulator
+ * word for word.  It applies to every half that goes to the demodulator, hfdl_gpu_frontend_push_baseband()'s included.  A retuned channel
+ * meets a fresh canceller.  Cost: one launch per half on the demodulator's stream.
+ * mu: 0 = off; 1e-5 .. 0.05 = on.  channels NULL / nsel 0 = every channel.  Every call replaces the selection and restarts every selected
+ * channel from zero state; like a retune it closes the half being filled: blocks pushed before the call are untouched, blocks pushed
+ * after it meet the new setting.  The first enable allocates.  HFDL_GPU_EINVAL (any other mu, NaN included; a null handle; a channel out
+ * of range or listed twice) is returned before any device work. */
+#define HFDL_GPU_NOTCH_STATE_FLOATS 174      /* 32 taps (re, im), then the last 55 inputs (re, im), newest first */
+int  hfdl_gpu_frontend_notch_enable(hfdl_gpu_frontend *fe, const int32_t *channels, int32_t nsel, float mu);
+typedef struct {
+	uint64_t blocks, resets;                                  /* rows cancelled, tap resets, since the enable */
+	float    last_in_power, last_out_power, tap_energy;       /* sum |x|^2, sum |y|^2 (sample order, fp32) and sum |w|^2 of the newest row */
+} hfdl_gpu_notch_stats;
+/* A selected channel's record.  Waits as hfdl_gpu_frontend_blanker_stats() does -- for the canceller launches queued so far, on the
+ * collection stream -- and queues nothing on the kernels' streams.  Nothing cancelled since the enable: all zero.  HFDL_GPU_EINVAL: null
+ * argument, channel out of range or not selected, or a front end whose canceller was never enabled. */
+int  hfdl_gpu_frontend_notch_stats(hfdl_gpu_frontend *fe, int32_t channel, hfdl_gpu_notch_stats *out);
+
 /* stage taps -- the DATADUMPS analogue (src/hfdl.c:616-644): copy an intermediate buffer to host */
 enum {
 	HFDL_GPU_TAP_SPECTRUM = 1,       /* cf32[fft_size], fftshifted forward FFT (shared.buf after src/fft.c:59) */
@@ -499,6 +530,8 @@ enum {
 	HFDL_GPU_TAP_AGC_LEVEL = 7,      /* f32[n], agc signal level per 5400-sps sample */
 	HFDL_GPU_TAP_NCO_PHASORS = 9,    /* cf32[n]: the NCO phasors (cos phi_k, sin phi_k) that multiplied the last block's outputs of `channel`
 	                                    (decimating_shift_addition_cc's recurrence, src/libcsdr_gpl.c:48-66; bit-exact vs the reference) */
+	HFDL_GPU_TAP_NOTCH_OUT = 10,     /* cf32[<= max_outputs_per_block]: the row of `channel` the demodulator read with the carrier canceller on (a selected
+	                                    channel: cancelled; another: tap 3's words); `back` as for tap 3.  HFDL_GPU_EINVAL while the canceller is off */
 	HFDL_GPU_TAP_PHASE_CYCLES = 8    /* f32[4]: shader cycles of the last demod launch: resampler phase, the whole four-wave pipelined phase (wall),
 	                                    busy cycles of the timing-recovery wave, busy cycles of the carrier / equaliser / framer wave */
 };
@@ -550,6 +583,10 @@ int  hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *mode
  * threshold_db 6 .. 60.  Every argument is checked before a device is selected. */
 int  hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int sample_format, float threshold_db,
 		float *out, float *power, uint64_t *blanked);
+/* the carrier canceller (hfdl_gpu_frontend_notch_enable above) alone, by the kernel of the front end: x, y = [nch][n] cf32, every row a
+ * channel's next n samples; state = [nch][HFDL_GPU_NOTCH_STATE_FLOATS], in and out, NULL = fresh and discarded.  mu 1e-5 .. 0.05.
+ * Every argument is checked before a device is selected. */
+int  hfdl_gpu_notch_rows(int device, const float *x, int32_t nch, int32_t n, float mu, float *state, float *y);
 /* the frame quality figures (hfdl_gpu_frame_quality above) of a batch, by the device function of the front end's records: symbols
  * and modes as for hfdl_gpu_burst_decode; out[nframes].  mode, nsym, segments and the five figures with seg_err_power are filled;
  * what only a front end knows (sample_index, channel, freq, bitmask_lsb, the training counts, the three channel fields) is 0. */

@@ -229,6 +229,13 @@ int           hfdl_frontend_set_frame_log(const char *path);
  * stops, one line on stderr gives the samples blanked and the blocks seen.  Returns 0, or -1 for any other threshold_db (NaN included).
  * With a GPU library that lacks the blanker, fft_create() fails with a message on stderr. */
 int           hfdl_frontend_set_blanker(float threshold_db);
+/* Adaptive carrier canceller of the front end created by the next fft_create() (include/hfdl_gpu.h, "Adaptive carrier canceller"); not
+ * in the reference, whose users notch in the SDR.  mu 1e-5 .. 0.05: the channels on freqs_khz[0 .. n - 1] (n = 0: every channel) run a
+ * 32-tap normalised-LMS line canceller with that step in front of their demodulator; 0: off (the default).  When the front end stops,
+ * one line per cancelled channel on stderr gives its blocks, tap resets, the last block's power in and out, and the tap energy.
+ * Returns 0, or -1 for any other mu (NaN included), n < 0 or above 4096, or a null list with n > 0.  A frequency that is no channel of
+ * the front end stops it with a message when it starts; with a GPU library that lacks the canceller, fft_create() fails with one. */
+int           hfdl_frontend_set_notch(float mu, const int32_t *freqs_khz, int n);
 /* Retune a channel of the running front end (include/hfdl_gpu.h, hfdl_gpu_frontend_retune_channel); not in the reference, which is
  * restarted to follow the ground stations' frequency changes.  Callable from any thread: the request old_freq -> new_freq (Hz) joins a
  * list (at most 64 waiting) that the front-end thread applies between two pushes -- blocks pushed before keep old_freq in their PDUs,
