@@ -124,12 +124,20 @@ __device__ __forceinline__ void nco_table_segment(const NcoJob &job, int c)
 	if (job.seg == 0) job.snap[c] = st;
 	const int cnt = nco_output_count(st, job.post_input_size, job.post);
 	const int per = (job.outs + job.nseg - 1) / job.nseg;
-	const int i0 = job.seg * per, i1 = (job.seg + 1) * per < cnt ? (job.seg + 1) * per : cnt;
+	// The chain is serial -- a step waits for the step before -- and with two segments instead of three (the fold in the mixed domain:
+	// no third pass) a segment took longer than the pass it rides on: the pass ended when its rider did (profiles/r23_experiments.md).
+	// So the loop runs to a bound every lane shares -- the segment's end or the table's last row (`outs` rows, every one inside the
+	// block's table): a scalar counter and branch, no lane mask carried from step to step through the scalar unit.  A channel with
+	// fewer outputs than that (cnt: the ragged last row, an empty block) gets rows it never reads; every row below cnt, the hand-over
+	// to the next segment of a channel whose rows go on, and the carried state (closed form, below) are the same 32 bits as before.
+	const int i0 = job.seg * per, i1 = (job.seg + 1) * per < job.outs ? (job.seg + 1) * per : job.outs;
 	float2 p = job.seg == 0 ? nco_phasor_seed(st.starting_phase) : job.cont[c];
 	float2 *dst = job.ph + (size_t)i0 * job.nch + c;
-	for (int i = i0; i < i1; i++, dst += job.nch) {
+	const float cd = k.nco_cosdelta, sd = k.nco_sindelta;
+	const size_t row = (size_t)job.nch;
+	for (int i = i0; i < i1; i++, dst += row) {
 		*dst = p;
-		nco_phasor_step(p.x, p.y, k.nco_cosdelta, k.nco_sindelta);
+		nco_phasor_step(p.x, p.y, cd, sd);
 	}
 	job.cont[c] = p;
 	if (job.seg == job.nseg - 1) {

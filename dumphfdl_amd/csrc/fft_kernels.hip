@@ -7,6 +7,8 @@
 // LDS, runs an in-place radix-4 DIF (result bit-reversed, undone on the way out) and applies the
 // inter-pass twiddle while storing.  Global accesses are 128-byte runs (16 adjacent columns of cf32);
 // the overlap history and the fftshift are index remaps on the first load / last store, never a pass.
+// Where the front end folds in the mixed domain (fold_domain.h) a block's transform ends with pass 2, which then stores the fold's operand
+// (fft_rpass2, mix_out); pass 3 runs on demand alone: for the spectrum monitor and for the stage taps that read a spectrum or a filter.
 #include <hip/hip_ext.h>
 #include "kernels.h"
 #include "retune_launch.h"
@@ -226,18 +228,26 @@ __global__ __launch_bounds__(16 * B) void fft_rpass1(const float2 *__restrict__ 
 	}
 }
 
-// pass 2, fast form: in place on buf; for each (k1, n3): R2-point FFT over n2 (stride R3), twiddle W_{R2 R3}^{k2 n3}
+// pass 2, fast form: in place on buf; for each (k1, n3): R2-point FFT over n2 (stride R3), twiddle W_{R2 R3}^{k2 n3}.
+// mix_out (a runtime argument: no second instantiation): the fold's operand instead (fold_domain.h) -- element (k1, k2, n3) goes to
+// [g][rho][k2 & 15] of the block's slot.  A workgroup holds one k1, 16 adjacent n3 and every k2: per k2 >> 4 it writes 16 rows x 16 bins
+// = 2 KiB contiguous.  The last stage's lanes then run over k2 & 15 first (a wave's store: 512 contiguous bytes) and the exchange planes
+// are laid out [col][k1] for it (fft_regs.h stage_a).  keep: the in-place store as well (pass 3 follows for the spectrum monitor).
 template <int B, bool AHEAD>
-__global__ __launch_bounds__(16 * B) void fft_rpass2(float2 *__restrict__ buf, FftPlan p, NcoJob job, int riders, int tpw)
+__global__ __launch_bounds__(16 * B) void fft_rpass2(float2 *__restrict__ buf, FftPlan p, NcoJob job, int riders, int tpw,
+		float2 *__restrict__ mix_out, int mix_q, int keep, int64_t mix_rx_stride)
 {
 	constexpr int NT = 16 * B;
 	if ((int)blockIdx.x < riders) { if (blockIdx.y == 0) nco_table_segment(job, (int)blockIdx.x * NT + (int)threadIdx.x); return; }
 	buf += (size_t)blockIdx.y * (size_t)p.n;       // receiver
+	const bool mix = mix_out != nullptr;
+	if (mix) mix_out += blockIdx.y * mix_rx_stride;
 	__shared__ float2 ex[B * FR_PITCH];
 	__shared__ float2 ltw[16 * B];
 	const int bid = ((int)blockIdx.x - riders) * tpw, tid = (int)threadIdx.x;
 	const int r23 = p.n >> p.l1;
 	const int col = tid & 15, n2 = tid >> 4;
+	const int kp = mix ? 1 : 16, cp = mix ? FR_TPITCH : 1;
 	auto base_of = [&](int tile) {                            // 16 adjacent n3 of one k1 (R3 is a multiple of 16)
 		const int cc0 = tile * 16;
 		return buf + (size_t)(cc0 >> p.l3) * r23 + (cc0 & (p.r3 - 1));
@@ -256,16 +266,32 @@ __global__ __launch_bounds__(16 * B) void fft_rpass2(float2 *__restrict__ buf, F
 		float2 *base = base_of(tile);
 		const int n30 = (tile * 16) & (p.r3 - 1);
 		__syncthreads();
-		stage_a(x, ex, ltw, n2, col);
+		stage_a(x, ex, ltw, n2, col, kp, cp);
 		__syncthreads();
 #pragma unroll
 		for (int i = 0; i < 256 / NT; i++) {
-			const int tt = tid + i * NT, tcol = tt & 15, k1 = tt >> 4, n3 = n30 + tcol;
+			const int tt = tid + i * NT, tlo = tt & 15, thi = tt >> 4;
+			const int tcol = mix ? thi : tlo, k1 = mix ? tlo : thi, n3 = n30 + tcol;      // k1: here the low four bits of k2
 			float2 z[B], w[B];
-			stage_b<B>(z, ex, k1, tcol);
+			stage_b<B>(z, ex, k1, tcol, kp, cp);
 			twiddle_run<B>(w, (unsigned)k1 * (unsigned)n3, 16u * (unsigned)n3, p.l2 + p.l3);
+			// One store loop for both forms, offsets in 32 bits (below N <= 2^24 elements).  k2 = k1 + 16 kb goes, in place, to row k2 of R3
+			// points; mixed, to bin k1 of group g = K1 + R1 (kb mod 2^(q - 4)), row rho = (kb >> (q - 4)) R3 + n3, a group being
+			// pre = 2^(l2 - q + l3) rows of 16 bins.  Both are (kb & lo) * s_lo + (kb >> hs) * s_hi from a base
+			const int K1 = (tile * 16) >> p.l3, qh = mix_q - 4, rows_log = p.l2 - mix_q + p.l3;
+			const unsigned lo = mix ? (1u << qh) - 1u : ~0u, hs = mix ? (unsigned)qh : 31u;
+			const unsigned s_lo = mix ? 1u << (p.l1 + rows_log + 4) : 16u << p.l3, s_hi = mix ? 1u << (p.l3 + 4) : 0u;
+			float2 *here = base + (size_t)k1 * p.r3 + tcol;
+			float2 *dst = mix ? mix_out + ((size_t)K1 << (rows_log + 4)) + (size_t)n3 * 16 + k1 : here;
 #pragma unroll
-			for (int k2 = 0; k2 < B; k2++) base[(size_t)(k1 + 16 * k2) * p.r3 + tcol] = cmul(z[slot_small<B>(k2)], w[k2]);
+			for (int kb = 0; kb < B; kb++) {
+				w[kb] = cmul(z[slot_small<B>(kb)], w[kb]);
+				dst[((unsigned)kb & lo) * s_lo + ((unsigned)kb >> hs) * s_hi] = w[kb];
+			}
+			if (keep) {                                       // (one branch, not one per store)
+#pragma unroll
+				for (int kb = 0; kb < B; kb++) here[(unsigned)kb * (16u << p.l3)] = w[kb];
+			}
 		}
 		if (AHEAD) {
 #pragma unroll
@@ -341,14 +367,15 @@ __global__ __launch_bounds__(16 * B) void fft_rpass3(const float2 *__restrict__ 
 	}
 }
 
-template <int B>
-static void launch_rpass1(int fmt, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t input_read, const float2 *hist, const FftInputs &in, int split, float2 *hist_next,
-		float2 *work, const FftPlan &p, const NcoJob &nco, int riders, int tpw)
+// One launch call for every register-resident pass (the kernel by address, its arguments by pointer): a templated launch per
+// instantiation costs the library a kilobyte of host code each, and its size is pinned (tests/test_host_logic_cpu.py)
+static void launch_rpass(const void *kernel, dim3 grid, int logr, hipStream_t st, hipEvent_t start, hipEvent_t stop, void **args)
 {
-	const dim3 blk(16 * B);
-	if (fmt == SFMT_CS16) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CS16, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
-	else if (fmt == SFMT_CU8) hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CU8, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
-	else hipExtLaunchKernelGGL((fft_rpass1<B, SFMT_CF32, false>), grid, blk, 0, st, start, input_read, 0, hist, in, split, hist_next, work, p, nco, riders, tpw);
+	(void)hipExtLaunchKernel(kernel, grid, dim3(1u << logr), args, 0, st, start, stop, 0);       // (a failure is found by the caller's hipGetLastError, as with the launch macros)
+}
+template <int B> static const void *rpass1_of(int fmt)
+{
+	return fmt == SFMT_CS16 ? (const void *)fft_rpass1<B, SFMT_CS16, false> : fmt == SFMT_CU8 ? (const void *)fft_rpass1<B, SFMT_CU8, false> : (const void *)fft_rpass1<B, SFMT_CF32, false>;
 }
 
 // Retune (hfdl_gpu_frontend_retune_channel): channel c becomes a freshly created channel as far as the riders' arrays go -- its
@@ -370,9 +397,38 @@ void launch_retune_channelizer(ChanConst *cc, NcoState *chain, float2 *cont, int
 // the register-resident passes take radices 64 / 128 / 256 (N = 2^18 .. 2^24); smaller transforms keep the LDS radix-4 passes
 static bool fast_plan(const FftPlan &p) { return p.l1 >= 6 && p.l1 <= 8 && p.l2 >= 6 && p.l2 <= 8 && p.l3 >= 6 && p.l3 <= 8; }
 
+// ---- the mixed domain's copies (kernels.h): one thread per element, lanes over k2 & 15, then n3 ----
+// dir 0: taps[slot](rho of -n3, j') = R3 plain[k1][k2][n3];  1: plain = taps / R3 (exact: a power of two);  2: plain = block[g][rho][k2 & 15]
+__global__ __launch_bounds__(256) void mixed_copy_kernel(float2 *__restrict__ plain, float *__restrict__ taps, const float2 *__restrict__ block,
+		int dir, int l1, int l2, int l3, int q, int m, size_t rs_f, int slot)
+{
+	const size_t n = (size_t)1 << (l1 + l2 + l3);
+	for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+		const int ka = (int)(e & 15), n3 = (int)(e >> 4) & ((1 << l3) - 1), kb = (int)(e >> (4 + l3)) & ((1 << (l2 - 4)) - 1), k1 = (int)(e >> (l2 + l3));
+		const int k2 = ka + 16 * kb, jp = mixed_bin(natural_bin_of(k1, k2, q, l1), l1);
+		float2 *pl = plain + ((size_t)k1 << (l2 + l3)) + ((size_t)k2 << l3) + n3;
+		if (dir == 2) {
+			*pl = block[((size_t)(jp >> 4) << (l2 - q + l3 + 4)) + (size_t)mixed_row(k2, n3, q, l3) * 16 + (jp & 15)];
+			continue;
+		}
+		float *t = taps + tap_index_f(TAPL_OCTET, m, rs_f, slot, mixed_tap_row(k2, n3, q, l3), jp, 0);
+		const float r3 = (float)(1 << l3), ir3 = 1.0f / r3;       // powers of two: both products are exact
+		if (dir == 0) { const float2 v = *pl; t[0] = v.x * r3; t[4] = v.y * r3; }
+		else *pl = make_float2(t[0] * ir3, t[4] * ir3);
+	}
+}
+
+static void launch_mixed_copy(const FftPlan &p, const Geometry &g, float2 *plain, float *taps, const float2 *block, int dir, int slot, hipStream_t st)
+{
+	hipLaunchKernelGGL(mixed_copy_kernel, dim3(2048), dim3(256), 0, st, plain, taps, block, dir, p.l1, p.l2, p.l3, g.mix_q, g.m, (size_t)g.tap_row_stride * 2, slot);
+}
+void launch_mixed_tap_pack(const FftPlan &p, const Geometry &g, const float2 *plain, float2 *taps, int slot, hipStream_t st) { launch_mixed_copy(p, g, (float2 *)plain, (float *)taps, nullptr, 0, slot, st); }
+void launch_mixed_tap_unpack(const FftPlan &p, const Geometry &g, const float2 *taps, int slot, float2 *plain, hipStream_t st) { launch_mixed_copy(p, g, plain, (float *)taps, nullptr, 1, slot, st); }
+void launch_mixed_block_unpack(const FftPlan &p, const Geometry &g, const float2 *slot, float2 *plain, hipStream_t st) { launch_mixed_copy(p, g, plain, nullptr, slot, 2, 0, st); }
+
 // one three-pass sequence for all in.nrx receivers: grid dimension y = receiver (work holds nrx transforms, n apart)
 void launch_fft_forward(const FftPlan &p, const float2 *hist, const FftInputs &in, int fmt, int split, float2 *hist_next,
-		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay, hipEvent_t done, NcoJob nco, hipEvent_t input_read, hipEvent_t start)
+		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay, hipEvent_t done, NcoJob nco, hipEvent_t input_read, hipEvent_t start, FftVariant var)
 {
 	const unsigned nrx = (unsigned)in.nrx;
 	const int64_t ors = in.out_stride;
@@ -380,31 +436,37 @@ void launch_fft_forward(const FftPlan &p, const float2 *hist, const FftInputs &i
 	const int g1 = (c1 + FFT_TILE - 1) / FFT_TILE, g2 = (c2 + FFT_TILE - 1) / FFT_TILE, g3 = (c3 + FFT_TILE - 1) / FFT_TILE;
 	nco.nseg = 3;
 	if (fast_plan(p)) {
+		// the fold's operand comes out of pass 2: the riders' two segments, the done event and the timed stop ride on passes 1 and 2
+		const bool mix = var.mix_out != nullptr, run1 = var.passes & 1, run2 = var.passes & 2, run3 = var.passes & 4;
+		if (mix) nco.nseg = 2;
 		// one rider workgroup per 16 B channels in front of each pass (a third of the NCO phasor table each)
 		auto riders_of = [&](int l) { const int nt = 1 << l; return nco.cc ? (nco.nch + nt - 1) / nt : 0; };
-		const int rd1 = riders_of(p.l1), rd2 = riders_of(p.l2), rd3 = riders_of(p.l3);
+		const int rd1 = riders_of(p.l1), rd2 = riders_of(p.l2), rd3 = mix ? 0 : riders_of(p.l3);
 		// tiles per workgroup: 4 where that still leaves four workgroups per CU to hand out, else 2, else 1
 		auto tpw_of = [](int tiles) { return tiles % 4 == 0 && tiles >= 4096 ? 4 : tiles % 2 == 0 && tiles >= 1024 ? 2 : 1; };
 		// (passes 1 and 2 keep one tile per workgroup: their sixteen loads per thread go straight into the transform's registers, a second
 		// set costs 90 - 140 VGPRs with the index arithmetic of the overlap assembly, and they lose little beside the demodulators)
-		const int t1 = 1, t2 = 1, t3 = tpw_of(g3);
+		const int t3 = tpw_of(g3);
+		FftPlan plan = p;
+		FftInputs inputs = in;
+		int tpw = 1, shift = shifted ? 1 : 0, keep = mix && run3 ? 1 : 0;
+		int64_t out_stride = ors;
 		nco.seg = 0;
-		switch (p.l1) {
-		case 6: launch_rpass1<4>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
-		case 7: launch_rpass1<8>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
-		default: launch_rpass1<16>(fmt, dim3(g1 / t1 + rd1, nrx), st, start, input_read, hist, in, split, hist_next, work, p, nco, rd1, t1); break;
+		if (run1) {
+			void *args[] = { &hist, &inputs, &split, &hist_next, &work, &plan, &nco, (void *)&rd1, &tpw };
+			launch_rpass(p.l1 == 6 ? rpass1_of<4>(fmt) : p.l1 == 7 ? rpass1_of<8>(fmt) : rpass1_of<16>(fmt), dim3(g1 + rd1, nrx), p.l1, st, start, input_read, args);
 		}
 		nco.seg = 1;
-		switch (p.l2) {
-		case 6: hipLaunchKernelGGL((fft_rpass2<4, false>), dim3(g2 / t2 + rd2, nrx), dim3(64), 0, st, work, p, nco, rd2, t2); break;
-		case 7: hipLaunchKernelGGL((fft_rpass2<8, false>), dim3(g2 / t2 + rd2, nrx), dim3(128), 0, st, work, p, nco, rd2, t2); break;
-		default: hipLaunchKernelGGL((fft_rpass2<16, false>), dim3(g2 / t2 + rd2, nrx), dim3(256), 0, st, work, p, nco, rd2, t2); break;
+		if (run2) {
+			void *args[] = { &work, &plan, &nco, (void *)&rd2, &tpw, &var.mix_out, &var.mix_q, &keep, &var.mix_rx_stride };
+			launch_rpass(p.l2 == 6 ? (const void *)fft_rpass2<4, false> : p.l2 == 7 ? (const void *)fft_rpass2<8, false> : (const void *)fft_rpass2<16, false>,
+					dim3(g2 + rd2, nrx), p.l2, st, nullptr, mix || !run3 ? done : nullptr, args);
 		}
 		nco.seg = 2;
-		switch (p.l3) {
-		case 6: hipExtLaunchKernelGGL(fft_rpass3<4>, dim3(g3 / t3 + rd3, nrx), dim3(64), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
-		case 7: hipExtLaunchKernelGGL(fft_rpass3<8>, dim3(g3 / t3 + rd3, nrx), dim3(128), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
-		default: hipExtLaunchKernelGGL(fft_rpass3<16>, dim3(g3 / t3 + rd3, nrx), dim3(256), 0, st, nullptr, done, 0, (const float2 *)work, out, p, shifted ? 1 : 0, lay, nco, rd3, t3, ors); break;
+		if (run3) {
+			void *args[] = { &work, &out, &plan, &shift, &lay, &nco, (void *)&rd3, (void *)&t3, &out_stride };
+			launch_rpass(p.l3 == 6 ? (const void *)fft_rpass3<4> : p.l3 == 7 ? (const void *)fft_rpass3<8> : (const void *)fft_rpass3<16>,
+					dim3(g3 / t3 + rd3, nrx), p.l3, st, nullptr, mix ? nullptr : done, args);
 		}
 		return;
 	}

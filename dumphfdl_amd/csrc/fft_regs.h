@@ -64,20 +64,24 @@ template <int B> __device__ __forceinline__ void dft_small(float2 (&z)[B])
 }
 template <int B> __device__ __forceinline__ constexpr int slot_small(int k) { return B == 16 ? slot16(k) : B == 8 ? slot8(k) : k; }
 
-// stage A + exchange: x[n1] (n1 = 0..15) of column `col`, sub-transform n2 -> LDS plane n2, row k1, column col, times W_R^(n2 k1)
-__device__ __forceinline__ void stage_a(float2 (&x)[16], float2 *ex, const float2 *ltw, int n2, int col)
+// stage A + exchange: x[n1] (n1 = 0..15) of column `col`, sub-transform n2 -> LDS plane n2, row k1, column col, times W_R^(n2 k1).
+// A plane is [k1][col] (kp = 16, cp = 1: stage B's lanes run over col) or, where stage B's lanes must run over k1 (pass 2 storing the
+// fold's operand, fft_kernels.hip), [col][k1] with 17 cf32 per column (kp = 1, cp = FR_TPITCH; 16 x 17 = FR_PITCH: the same plane): the
+// sixteen columns a 64-bit write covers then start 34 dwords apart -- sixteen disjoint bank pairs, as with cp = 1.
+constexpr int FR_TPITCH = 17;
+__device__ __forceinline__ void stage_a(float2 (&x)[16], float2 *ex, const float2 *ltw, int n2, int col, int kp = 16, int cp = 1)
 {
 	dft16(x);
-	float2 *dst = ex + n2 * FR_PITCH + col;
+	float2 *dst = ex + n2 * FR_PITCH + col * cp;
 	dst[0] = x[0];
 #pragma unroll
-	for (int k1 = 1; k1 < 16; k1++) dst[k1 * 16] = cmul(x[slot16(k1)], ltw[n2 * k1]);
+	for (int k1 = 1; k1 < 16; k1++) dst[k1 * kp] = cmul(x[slot16(k1)], ltw[n2 * k1]);
 }
 
 // stage B of task (k1, col): B points from the exchange buffer, B-point DFT; X[k1 + 16 k2] is z[slot_small<B>(k2)]
-template <int B> __device__ __forceinline__ void stage_b(float2 (&z)[B], const float2 *ex, int k1, int col)
+template <int B> __device__ __forceinline__ void stage_b(float2 (&z)[B], const float2 *ex, int k1, int col, int kp = 16, int cp = 1)
 {
-	const float2 *src = ex + k1 * 16 + col;
+	const float2 *src = ex + k1 * kp + col * cp;
 #pragma unroll
 	for (int n2 = 0; n2 < B; n2++) z[n2] = src[n2 * FR_PITCH];
 	dft_small<B>(z);

@@ -55,7 +55,7 @@ __device__ __forceinline__ int rx_of_channel(const int4 *__restrict__ rx_tab, in
 // taps of channel c sit in its padded slot, the spectrum is its receiver's
 __global__ __launch_bounds__(FOLD_THREADS) void fold_ref_kernel(const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
 		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int layout, int nb,
-		const int4 *__restrict__ rx_tab, int nrx, size_t spec_rx_stride)
+		const int4 *__restrict__ rx_tab, int nrx, size_t spec_rx_stride, size_t row_stride, size_t group_stride)
 {
 	const int s = blockIdx.x % slices, c = blockIdx.x / slices;
 	const int rxi = rx_of_channel(rx_tab, nrx, c);
@@ -64,7 +64,8 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_ref_kernel(const float *__r
 	spec += (size_t)rxi * spec_rx_stride;
 	for (int b0 = 0; b0 < nb; b0 += 4)              // four blocks per pass over the taps
 		for (int j = threadIdx.x; j < m; j += FOLD_THREADS) {
-			const float2 *sp = spec + (size_t)b0 * spec_stride + (size_t)s * rows * (size_t)m + j;
+			// row r of bin j: r * row_stride + (j / 16) * group_stride + j % 16 (kernels.h Geometry: M and 16 where the fold reads spectra)
+			const float2 *sp = spec + (size_t)b0 * spec_stride + (size_t)s * rows * row_stride + (size_t)(j >> 4) * group_stride + (j & 15);
 			float2 acc[4] = { make_float2(0.f, 0.f), make_float2(0.f, 0.f), make_float2(0.f, 0.f), make_float2(0.f, 0.f) };
 			for (int r = 0; r < rows; r += 4) {
 				const int n = rows - r < 4 ? rows - r : 4;
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_ref_kernel(const float *__r
 #pragma unroll
 				for (int b = 0; b < 4; b++)
 					if (b0 + b < nb) {
-						for (int k = 0; k < n; k++) x[k] = sp[(size_t)b * spec_stride + (size_t)(r + k) * m];
+						for (int k = 0; k < n; k++) x[k] = sp[(size_t)b * spec_stride + (size_t)(r + k) * row_stride];
 						cmac_quad(acc[b], h, x, n);
 					}
 			}
@@ -145,7 +146,7 @@ template <int P, int W, int D, bool WIN = false, bool SMALL = false, int CG = 1>
 __device__ __forceinline__ void fold_mfma16_body(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
 		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
-		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride, size_t row_stride, size_t group_stride)
 {
 	static_assert(!WIN || W == 1, "windows are per wave: no spectrum tile is shared");
 	static_assert(D == 2 || D == 4, "the LDS stage of a trip is a compile-time constant for even D");
@@ -204,7 +205,7 @@ __device__ __forceinline__ void fold_mfma16_body(
 	}
 	// wave-uniform bases stepped by scalar adds + one byte offset per lane
 	const char *tb = (const char *)(taps + (size_t)s * rows * row_stride_f + (size_t)octet0 * 64 * m + (size_t)g * 1024) + lane * 16;
-	const size_t qs_b = row_stride_f * 16, os_b = (size_t)m * 256, xquad_b = (size_t)m * 32;       // bytes per quad of rows / per octet / per quad of spectrum rows
+	const size_t qs_b = row_stride_f * 16, os_b = (size_t)m * 256, xquad_b = row_stride * 32;       // bytes per quad of rows / per octet / per quad of spectrum rows
 	const char *xp[MINE], *xp0[MINE];                         // item (wave * MINE + i) * 64 + lane = (segment, 16-byte part)
 	int xseg[MINE];
 #pragma unroll
@@ -212,7 +213,7 @@ __device__ __forceinline__ void fold_mfma16_body(
 		const int item = (((wave * MINE) % NLOADS) + i) * 64 + lane, seg = item >> 3, part = item & 7;
 		const int sn = (seg & 15) + 16 * (seg >> 6), sk = (seg >> 4) & 3;
 		const int bi = sn < nb ? sn : nb - 1;                 // columns past the last block repeat it; they are never stored
-		xp[i] = xp0[i] = (const char *)(spec + (size_t)bi * spec_stride + ((size_t)s * rows + sk) * (size_t)m + g * 16 + 2 * part);
+		xp[i] = xp0[i] = (const char *)(spec + (size_t)bi * spec_stride + ((size_t)s * rows + sk) * row_stride + (size_t)g * group_stride + 2 * part);
 		xseg[i] = part * XPITCH + seg;
 	}
 	const char *const tb0 = tb;
@@ -382,9 +383,9 @@ template <int P, int W, int D, bool WIN = false, bool SMALL = false, int CG = 1>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(fold16_waves(P, W, D, SMALL, CG), fold16_waves(P, W, D, SMALL, CG)))) void fold_mfma16_kernel(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
 		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
-		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride, size_t row_stride, size_t group_stride)
 {
-	fold_mfma16_body<P, W, D, WIN, SMALL, CG>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride);
+	fold_mfma16_body<P, W, D, WIN, SMALL, CG>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride, row_stride, group_stride);
 }
 
 #ifdef HFDL_LAB
@@ -394,9 +395,9 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(fold16_w
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) __attribute__((amdgpu_num_vgpr(104))) void fold32_two_waves_kernel(
 		const float *__restrict__ taps, const float2 *__restrict__ spec, float2 *__restrict__ partial,
 		size_t row_stride_f, size_t spec_stride, size_t partial_stride, int m, int slices, int rows, int nb,
-		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride)
+		const int2 *__restrict__ win, const int4 *__restrict__ grp_tab, size_t spec_rx_stride, size_t row_stride, size_t group_stride)
 {
-	fold_mfma16_body<1, 8, 2, false, false, 2>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride);
+	fold_mfma16_body<1, 8, 2, false, false, 2>(taps, spec, partial, row_stride_f, spec_stride, partial_stride, m, slices, rows, nb, win, grp_tab, spec_rx_stride, row_stride, group_stride);
 }
 #endif
 
@@ -451,6 +452,7 @@ struct FoldArgs {
 	const int4 *grp_tab, *rx_host;                    // receivers (kernels.h Geometry::grp_tab / rx_host): each pads its channels to whole groups
 	int nrx;
 	size_t spec_rx_stride;
+	size_t row_stride, group_stride;                  // of a block's fold operand (kernels.h Geometry)
 	// workgroups of `pw` octets over all receivers, and the octets left over (no workgroup straddles two receivers); the table of their
 	// FoldGroup entries: the full groups, then the left-over octets
 	void split(int pw, int &groups, int &rest) const
@@ -463,6 +465,13 @@ struct FoldArgs {
 	hipEvent_t start, stop;
 };
 
+// one launch call for every tiling (the kernel by address): a templated launch per instantiation is a kilobyte of host code each
+static void fold_launch(const void *kernel, unsigned blocks, unsigned threads, FoldArgs a, int slices, const int2 *win, const int4 *table, hipEvent_t start, hipEvent_t stop)
+{
+	void *args[] = { &a.taps, &a.spec, &a.partial, &a.rs_f, &a.ss, &a.ps, &a.m, &slices, &a.rows, &a.nb, &win, &table, &a.spec_rx_stride, &a.row_stride, &a.group_stride };
+	(void)hipExtLaunchKernel(kernel, dim3(blocks), dim3(threads), args, 0, a.st, start, stop, 0);      // (a failure is found by the caller's hipGetLastError, as with the launch macros)
+}
+
 // workgroups of 8 P W channels first; the octets left over get single-wave workgroups in a launch of their own
 template <int P, int W, int D, bool SMALL = false, int CG = 1>
 static int fold16_go(const FoldArgs &a)
@@ -473,15 +482,13 @@ static int fold16_go(const FoldArgs &a)
 	a.split(P * W, groups, rest);
 	int launches = 0;
 	if (groups > 0) {
-		hipExtLaunchKernelGGL((fold_mfma16_kernel<P, W, D, false, SMALL, CG>), dim3((unsigned)(groups * ntile)), dim3(64 * W), 0, a.st, a.start, rest ? nullptr : a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(P * W), a.spec_rx_stride);
+		fold_launch((const void *)fold_mfma16_kernel<P, W, D, false, SMALL, CG>, (unsigned)(groups * ntile), 64 * W, a, a.slices, (const int2 *)nullptr, a.table(P * W), a.start, rest ? nullptr : a.stop);
 		launches++;
 	}
 	if (rest > 0) {
 		// (a single wave fetches the whole spectrum tile itself: two quads in flight keep that within its registers when the tile is 32 blocks wide)
 		constexpr int DR = CG > 1 ? 2 : D;
-		hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, DR, false, SMALL, CG>), dim3((unsigned)(rest * ntile)), dim3(64), 0, a.st, groups > 0 ? nullptr : a.start, a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(P * W) + groups, a.spec_rx_stride);
+		fold_launch((const void *)fold_mfma16_kernel<1, 1, DR, false, SMALL, CG>, (unsigned)(rest * ntile), 64, a, a.slices, (const int2 *)nullptr, a.table(P * W) + groups, groups > 0 ? nullptr : a.start, a.stop);
 		launches++;
 	}
 	return launches;
@@ -495,13 +502,11 @@ static int fold32_two_waves_go(const FoldArgs &a)
 	a.split(8, groups, rest);
 	int launches = 0;
 	if (groups > 0) {
-		hipExtLaunchKernelGGL(fold32_two_waves_kernel, dim3((unsigned)(groups * ntile)), dim3(512), 0, a.st, a.start, rest ? nullptr : a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(8), a.spec_rx_stride);
+		fold_launch((const void *)fold32_two_waves_kernel, (unsigned)(groups * ntile), 512, a, a.slices, (const int2 *)nullptr, a.table(8), a.start, rest ? nullptr : a.stop);
 		launches++;
 	}
 	if (rest > 0) {
-		hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, 2, false, false, 2>), dim3((unsigned)(rest * ntile)), dim3(64), 0, a.st, groups > 0 ? nullptr : a.start, a.stop, 0,
-			a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, a.slices, a.rows, a.nb, (const int2 *)nullptr, a.table(8) + groups, a.spec_rx_stride);
+		fold_launch((const void *)fold_mfma16_kernel<1, 1, 2, false, false, 2>, (unsigned)(rest * ntile), 64, a, a.slices, (const int2 *)nullptr, a.table(8) + groups, groups > 0 ? nullptr : a.start, a.stop);
 		launches++;
 	}
 	return launches;
@@ -513,8 +518,7 @@ template <int D>
 static int fold16_go_win(const FoldArgs &a, const int2 *win)
 {
 	const int ntile = a.m >> 4;
-	hipExtLaunchKernelGGL((fold_mfma16_kernel<1, 1, D, true>), dim3((unsigned)(a.ngroups * ntile)), dim3(64), 0, a.st, a.start, a.stop, 0,
-		a.taps, a.spec, a.partial, a.rs_f, a.ss, a.ps, a.m, 1, a.rows, a.nb, win, a.table(1), a.spec_rx_stride);
+	fold_launch((const void *)fold_mfma16_kernel<1, 1, D, true>, (unsigned)(a.ngroups * ntile), 64, a, 1, win, a.table(1), a.start, a.stop);
 	return 1;
 }
 
@@ -586,6 +590,8 @@ int fold_launch_blocks(const Geometry &g, int remaining, int nb_max)
 	return take;
 }
 
+static size_t fold_row_stride(const Geometry &g) { return g.spec_row_stride ? (size_t)g.spec_row_stride : (size_t)g.m; }
+
 static FoldArgs fold_args(const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial, size_t partial_stride,
 		int nb, hipStream_t st, hipEvent_t start, hipEvent_t stop)
 {
@@ -594,6 +600,7 @@ static FoldArgs fold_args(const Geometry &g, const float2 *taps, const float2 *s
 	a.rs_f = (size_t)g.tap_row_stride * 2; a.ss = spec_stride; a.ps = partial_stride;
 	a.m = g.m; a.slices = g.slices; a.rows = g.rows_per_slice; a.nch = g.nch; a.ngroups = g.nch_pad / tap_layout_group(g.tap_layout); a.nb = nb;
 	a.grp_tab = g.grp_tab; a.rx_host = g.rx_host; a.nrx = g.nrx; a.spec_rx_stride = (size_t)g.spec_rx_stride;
+	a.row_stride = fold_row_stride(g); a.group_stride = (size_t)g.spec_group_stride;
 	a.st = st; a.start = start; a.stop = stop;
 	return a;
 }
@@ -603,7 +610,7 @@ static void launch_fold_ref(const Geometry &g, const float2 *taps, const float2 
 {
 	hipExtLaunchKernelGGL(fold_ref_kernel, dim3((unsigned)(g.nch * g.slices)), dim3(FOLD_THREADS), 0, st, start, stop, 0,
 		(const float *)taps, spectrum, partial, (size_t)g.tap_row_stride * 2, spec_stride, partial_stride, g.m, g.slices, g.rows_per_slice, g.tap_layout, nb,
-		g.rx_tab, g.nrx, (size_t)g.spec_rx_stride);
+		g.rx_tab, g.nrx, (size_t)g.spec_rx_stride, fold_row_stride(g), (size_t)g.spec_group_stride);
 }
 
 int launch_fold_variant(int v, const Geometry &g, const float2 *taps, const float2 *spectrum, size_t spec_stride, float2 *partial,
@@ -704,9 +711,10 @@ __global__ __launch_bounds__(IFFT_THREADS) void ifft_nco_kernel(const float2 *__
 		const float2 *pc = partial + (size_t)b * partial_stride + (size_t)c * g.slices * (size_t)m;
 		for (int u = threadIdx.x; u < m; u += IFFT_THREADS) {
 			const int j = (u - h0 - m / 2) & mask;
+			const int jp = mixed_bin(j, g.mix_l1);            // the partial sums of a mixed-domain fold lie in group order (fold_domain.h)
 			float2 acc = make_float2(0.f, 0.f);
 			for (int s = 0; s < g.slices; s++) {
-				float2 v = pc[(size_t)s * m + j];
+				float2 v = pc[(size_t)s * m + jp];
 				acc.x += v.x; acc.y += v.y;
 			}
 			sm[u] = acc;

@@ -95,6 +95,7 @@ struct SpectrumMonitor {
 	DevBuf acc;                         // [nrx][bins] float2 { sum, compensation } of the band powers
 	DevBuf peak;                        // [nrx][bins] float with MAXHOLD
 	PinnedBuf<float> host;              // bounce buffer of a read: [bins] float2 + [bins] float
+	DevBuf scratch;                     // [nrx][N] float2 where the fold runs in the mixed domain: the one block's spectrum pass 3 makes for the monitor alone
 	Event ev;
 	hipEvent_t last = nullptr;          // null: no launch yet, or everything launched has been waited for
 	hipEvent_t newest() const { return last ? last : ev.e; }

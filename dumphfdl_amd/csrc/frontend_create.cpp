@@ -158,7 +158,13 @@ static int build_taps(hfdl_gpu_frontend *fe)
 		FftOutLayout lay = fe->tap_layout;
 		lay.chan = slot;
 		float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
-		launch_fft_forward(fe->fft.p, nullptr, d_pad, SFMT_CF32, 0, nullptr, fe->d_work, dst, true, fe->stream, lay);
+		if (fe->geo.mix_l1) {
+			// the mixed domain: passes 1 and 2, then R3 T[k1, k2, -n3] into the same layout at (row rho, bin j')
+			FftVariant v;
+			v.passes = FFT_PASSES_12;
+			launch_fft_forward(fe->fft.p, nullptr, d_pad, SFMT_CF32, 0, nullptr, fe->d_work, nullptr, true, fe->stream, FftOutLayout(), nullptr, NcoJob(), nullptr, nullptr, v);
+			launch_mixed_tap_pack(fe->fft.p, fe->geo, fe->d_work, fe->d_taps, slot, fe->stream);
+		} else launch_fft_forward(fe->fft.p, nullptr, d_pad, SFMT_CF32, 0, nullptr, fe->d_work, dst, true, fe->stream, lay);
 	}
 	HIP_TRY(hipStreamSynchronize(fe->stream));
 	HIP_TRY(hipGetLastError());
@@ -305,6 +311,18 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	CREATE_TRY(fe->fft_done.own.create(EV_NO_TIMING));
 	CREATE_TRY(fe->ev_switch.create(EV_NO_TIMING));
 	if (int rc = fe->fft.build(pl.n)) return rc;
+	{
+		// HFDL_GPU_FOLD_SPECTRUM=0: the fold in the mixed domain (fold_domain.h) wherever the geometry allows it -- the
+		// forward FFT stops after pass 2.  Unset or 1, the fold reads spectra: all three passes, the taps' full transform.  Opt-in, because
+		// under out-of-band signals 60 dB above the channel the mixed-domain sums cancel in the accumulator and the channelizer output
+		// lands 2.8 x further from the float64 model (2.4 Msps x 130 channels: 1.57e-4 against 5.6e-5 relative RMS at worst) -- past the
+		// gate of tests/test_gpu_channelizer_f64.py at one (block, channel) of 1392.
+		const FftPlan &fp = fe->fft.p;
+		if (g.tap_layout == TAPL_OCTET && mixed_fold_fits(fp.l1, fp.l2, fp.l3, ilog2(pl.m), fe->prune_tol > 0) && env_long("HFDL_GPU_FOLD_SPECTRUM", 0, 1, 1) == 0) {
+			g.mix_l1 = fp.l1; g.mix_q = ilog2(pl.m) - fp.l1;
+			g.spec_row_stride = 16; g.spec_group_stride = 16 * (int64_t)pl.pre;
+		}
+	}
 	const size_t n = (size_t)pl.n;
 	const size_t K = (size_t)nrx;
 	for (int i = 0; i < 2; i++) {      // overlap history, ping-pong: block k reads [k&1] and leaves the next one in [(k+1)&1]; one per receiver

@@ -265,13 +265,22 @@ extern "C" int hfdl_gpu_frontend_read_tap_block(hfdl_gpu_frontend *fe, int what,
 	case HFDL_GPU_TAP_SPECTRUM:
 		src = fe->spec_slot(fe->last_set, index) + (fe->nrx > 1 ? (size_t)fe->rx_of[(size_t)channel] * (size_t)g.n : 0);
 		nf = 2 * (size_t)g.n;
-		break;
+		if (!g.mix_l1) break;
+		[[fallthrough]];                       // the mixed domain: the slot holds pass 2's output -- the spectrum is made here, by the pass 3 the pipeline left out
 	case HFDL_GPU_TAP_FILTER: {
-		// the taps lie in matrix-operand order (kernels.h tap_index_f): a kernel gathers the channel into plain cf32[N]
+		// the taps lie in matrix-operand order (kernels.h tap_index_f): a kernel gathers the channel into plain cf32[N].  In the mixed
+		// domain both taps go back to pass 2's own order and through pass 3: the words the three-pass transform leaves
 		if (2 * (size_t)g.n > cap) return fail(HFDL_GPU_ERANGE, "tap needs %zu floats, buffer holds %zu", 2 * (size_t)g.n, cap);
-		DevBuf plain;
+		DevBuf plain, mid;
 		HIP_TRY(plain.alloc(sizeof(float2) * (size_t)g.n));
-		launch_tap_extract(fe->d_taps, g, fe->slot_of(channel), plain.as<float2>(), fe->stream);
+		if (g.mix_l1) {
+			HIP_TRY(mid.alloc(sizeof(float2) * (size_t)g.n));
+			if (what == HFDL_GPU_TAP_SPECTRUM) launch_mixed_block_unpack(fe->fft.p, g, (const float2 *)src, mid.as<float2>(), fe->stream);
+			else launch_mixed_tap_unpack(fe->fft.p, g, fe->d_taps, fe->slot_of(channel), mid.as<float2>(), fe->stream);
+			FftVariant v;
+			v.passes = FFT_PASS_3;
+			launch_fft_forward(fe->fft.p, nullptr, (const void *)nullptr, SFMT_CF32, 0, nullptr, mid.as<float2>(), plain.as<float2>(), true, fe->stream, FftOutLayout(), nullptr, NcoJob(), nullptr, nullptr, v);
+		} else launch_tap_extract(fe->d_taps, g, fe->slot_of(channel), plain.as<float2>(), fe->stream);
 		HIP_TRY(hipStreamSynchronize(fe->stream));
 		HIP_TRY(hipMemcpy(dst, plain.p, sizeof(float2) * (size_t)g.n, hipMemcpyDeviceToHost));
 		*n_floats = 2 * (size_t)g.n;
@@ -329,6 +338,7 @@ extern "C" int hfdl_gpu_frontend_spectrum_enable(hfdl_gpu_frontend *fe, int32_t 
 	hipError_t e = mon->acc.alloc(sizeof(float2) * nb * K);
 	if (e == hipSuccess && (flags & HFDL_GPU_SPECTRUM_MAXHOLD)) e = mon->peak.alloc(sizeof(float) * nb * K);
 	if (e == hipSuccess) e = mon->host.alloc(3 * nb);
+	if (e == hipSuccess && fe->geo.mix_l1) e = mon->scratch.alloc(sizeof(float2) * K * (size_t)fe->geo.n);
 	if (e == hipSuccess) e = mon->ev.create(EV_NO_TIMING);
 	if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "spectrum monitor buffers: %s", hipGetErrorString(e));
 	mon->bins = bins;

@@ -306,14 +306,24 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 	}
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
-	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, fe->spec_slot(set, i), true, st,
+	// The mixed domain: pass 2 leaves the fold's operand in the block's slot and carries fft_done; pass 3 runs for the spectrum monitor
+	// alone, behind it, into the monitor's one-block scratch (forward FFTs run one after the other: one scratch serves them all)
+	SpectrumMonitor *mon = fe->mon.get();
+	FftVariant var;
+	float2 *spectrum = fe->spec_slot(set, i);
+	if (g.mix_l1) {
+		var.mix_out = spectrum; var.mix_q = g.mix_q; var.mix_rx_stride = g.n;
+		var.passes = mon ? FFT_PASSES_ALL : FFT_PASSES_12;
+		spectrum = mon ? mon->scratch.as<float2>() : nullptr;
+	}
+	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, spectrum, true, st,
 			FftOutLayout(), fft_done, job,
 			stage_idx >= 0 ? fe->ev_stage_free[stage_idx].e : nullptr,      // input consumed once pass 1 is done: the copy stream may refill the buffer
-			fft_start);
-	if (SpectrumMonitor *mon = fe->mon.get()) {
+			fft_start, var);
+	if (mon) {
 		// the spectrum monitor: one launch behind the last pass; the timed pair and the events other streams wait for stay on that pass
 		SpecmonJob m;
-		m.spec = fe->spec_slot(set, i); m.rx_stride = g.n; m.n = g.n; m.bins = mon->bins; m.nrx = fe->nrx; m.flags = mon->flags;
+		m.spec = spectrum; m.rx_stride = g.n; m.n = g.n; m.bins = mon->bins; m.nrx = fe->nrx; m.flags = mon->flags;
 		m.scale = (float)(1.0 / ((double)g.n * (double)g.n * ((mon->flags & SPECMON_HANN) ? 0.375 : 1.0)));
 		m.fresh = mon->fresh; m.acc = mon->acc.as<float2>(); m.peak = mon->peak.as<float>();
 		SpectrumHistory *h = mon->hist.get();
@@ -538,7 +548,12 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	FftOutLayout lay = fe->tap_layout;
 	lay.chan = slot;
 	float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
-	launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), dst, true, fe->stream, lay, nullptr, NcoJob(), r.staged[sb]);
+	if (fe->geo.mix_l1) {
+		FftVariant v;
+		v.passes = FFT_PASSES_12;
+		launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), nullptr, true, fe->stream, FftOutLayout(), nullptr, NcoJob(), r.staged[sb], nullptr, v);
+		launch_mixed_tap_pack(fe->fft.p, fe->geo, r.work.as<float2>(), fe->d_taps, slot, fe->stream);
+	} else launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), dst, true, fe->stream, lay, nullptr, NcoJob(), r.staged[sb]);
 	launch_retune_channelizer(fe->d_cc, fe->d_nco, fe->d_ph_cont, channel, k, fe->stream, r.done.signal());
 	fe->demod.enqueue_retune(channel, new_freq_hz, fe->stream_b, fe->stream_d);
 	// the retuned channel meets a fresh canceller: its taps and delay line go where its demodulator state goes, behind the closed half on B

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fold_domain.h"
 
 namespace hfdl {
 
@@ -55,6 +56,12 @@ struct Geometry {
 	// TAPL_OCTET: the fold workgroups' FoldGroup entries, one table per workgroup width pw = 1 .. FOLD_GROUP_MAX octets at
 	// grp_tab + (pw - 1) * (nch_pad / 8): per receiver its nch_r / pw full groups, receiver after receiver, then the octets left over
 	const int4 *grp_tab = nullptr;
+	// The fold in the mixed domain (fold_domain.h): mix_l1 = l1 of the forward FFT's plan (0: the fold reads spectra, rows of M bins), mix_q =
+	// log2(M) - l1.  A block's slot then holds pass 2's output as [bin group g][row rho][16 bins]: row rho of group g lies at
+	// rho * spec_row_stride + g * spec_group_stride cf32 (16 and 16 * pre; the spectrum domain: M and 16), the taps at (row rho, bin j'),
+	// and the partial sums come out in group order j'.
+	int32_t mix_l1 = 0, mix_q = 0;
+	int64_t spec_row_stride = 0, spec_group_stride = 16;
 };
 // an entry (planner.h FoldGroup, read as an int4): first octet of the group, its receiver, the end of that receiver's channel slots, channel - slot
 constexpr int FOLD_GROUP_MAX = 16;          // octets one fold workgroup takes at most (P x W of the widest compiled tiling)
@@ -130,19 +137,31 @@ enum { SFMT_CF32 = 0, SFMT_CS16 = 1, SFMT_CU8 = 2 };
 // kind != TAPL_PLAIN: the transform is the filter of channel `chan`, `out` is the tap buffer, and element (row i >> row_log, bin) goes
 // to tap_index_f(kind, 2^row_log, 2 * row_stride, chan, row, bin, comp) floats
 struct FftOutLayout { int row_log = 0; int64_t row_stride = 0; int kind = 0; int chan = 0; };
+// Which passes run (register-resident plans only, when not all three) and where pass 2 stores.  mix_out: pass 2 stores out of place, in
+// the fold's operand order (Geometry::mix_l1): receiver r's transform at mix_out + r * mix_rx_stride; `done`, the timed stop and the last
+// rider segment then ride on pass 2.  With pass 3 asked for as well (the spectrum monitor is on) pass 2 ALSO stores in place and pass 3
+// follows, without an event, into `out`.  passes = FFT_PASSES_12 leaves pass 2's output in `work`; FFT_PASS_3 transforms what lies there.
+enum { FFT_PASSES_ALL = 7, FFT_PASSES_12 = 3, FFT_PASS_3 = 4 };
+struct FftVariant { int passes = FFT_PASSES_ALL; float2 *mix_out = nullptr; int mix_q = 0; int64_t mix_rx_stride = 0; };
 void launch_fft_forward(const FftPlan &p, const float2 *hist, const FftInputs &in, int fmt, int split, float2 *hist_next,
 		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay = FftOutLayout(), hipEvent_t done = nullptr,
-		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr);
+		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr, FftVariant var = FftVariant());
 		// input_read: signalled when the first pass has consumed the inputs; start: rides on the first pass' dispatch (timing)
 // one transform (one receiver)
 inline void launch_fft_forward(const FftPlan &p, const float2 *hist, const void *fresh, int fmt, int split, float2 *hist_next,
 		float2 *work, float2 *out, bool shifted, hipStream_t st, FftOutLayout lay = FftOutLayout(), hipEvent_t done = nullptr,
-		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr)
+		NcoJob nco = NcoJob(), hipEvent_t input_read = nullptr, hipEvent_t start = nullptr, FftVariant var = FftVariant())
 {
 	FftInputs in;
 	in.fresh[0] = fresh;
-	launch_fft_forward(p, hist, in, fmt, split, hist_next, work, out, shifted, st, lay, done, nco, input_read, start);
+	launch_fft_forward(p, hist, in, fmt, split, hist_next, work, out, shifted, st, lay, done, nco, input_read, start, var);
 }
+// The mixed domain's two copies (fft_kernels.hip), one transform of p.n points each, `plain` in pass 2's own order [k1][k2][n3]:
+// pack: the taps of padded slot `slot`, R3 T[k1, k2, -n3], into the tap buffer at (row rho, bin j'); unpack: back, the words pass 2 left;
+// unpack_block: a block's slot [g][rho][16] back into pass 2's order
+void launch_mixed_tap_pack(const FftPlan &p, const Geometry &g, const float2 *plain, float2 *taps, int slot, hipStream_t st);
+void launch_mixed_tap_unpack(const FftPlan &p, const Geometry &g, const float2 *taps, int slot, float2 *plain, hipStream_t st);
+void launch_mixed_block_unpack(const FftPlan &p, const Geometry &g, const float2 *slot, float2 *plain, hipStream_t st);
 // Blocks the next fold launch takes of the `remaining` ones, at most `nb_max`: the one rule for the size of a fold launch.
 int fold_launch_blocks(const Geometry &g, int remaining, int nb_max);
 // optional events ride on the kernel dispatches themselves (hipExtLaunchKernelGGL): no separate barrier packets in the queue

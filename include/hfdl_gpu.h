@@ -106,6 +106,16 @@ typedef struct {
  *                                as an amplitude ratio at N = 2^23) in EVERY row: a tolerance below that keeps every row.  Off, every row is
  *                                folded -- the reference's sum, term for term.  Ignored by a front end of several receivers
  *                                (hfdl_gpu_frontend_create_multi with nrx > 1): there geometry.fold_rows = pre_decimation
+ *   HFDL_GPU_FOLD_SPECTRUM 0 / 1 (default 1) 1: the fold reads full spectra -- all three passes of the forward FFT -- on every geometry.
+ *                                0: a geometry whose forward FFT runs the register-resident passes (fft_size >= 2^18) with at least
+ *                                sixteen bins of fft_inv_size per first-pass index and no pruned fold stops the transform after its second
+ *                                pass and folds there: the third pass is a plain DFT, and the fold's sum over its outputs equals the sum
+ *                                over its inputs against the taps' second-pass transform, index-reversed and scaled by the radix
+ *                                (DESIGN.md section 4.2): 5 % more samples per second at 40 Msps x 256 channels.  Every tap still meets
+ *                                every sample in fp32, but what the filter rejects is then rejected by cancellation inside the fp32
+ *                                accumulator, not by small taps: out-of-band signals 60 dB above a channel leave its output up to 1.6e-4
+ *                                (relative RMS) from the exact convolution instead of 0.6e-4, in proportion to their level.  Hence opt-in.
+ *                                HFDL_GPU_TAP_SPECTRUM and HFDL_GPU_TAP_FILTER read the same words either way
  * The A/B switches of the measurement scripts (stream placement, tiling sweeps, probes) are in the laboratory build only:
  * include/hfdl_gpu_lab.h, libhfdl_gpu_lab.so. */
 
