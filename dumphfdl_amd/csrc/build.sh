@@ -15,7 +15,11 @@ else
 	BUILD=${HFDL_BUILD_DIR:-../build}
 fi
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function ${HFDL_EXTRA_FLAGS:-}"
+# The HOST half of every object is compiled without exception and unwind tables: the shim has no try, catch or throw, an uncaught C++
+# exception ends the process at the C ABI either way, and the tables were 25 KB of a library whose size is pinned
+# (tests/test_host_logic_cpu.py).  The device pass never sees the flags.
+NO_UNWIND="-Xarch_host -fno-exceptions -Xarch_host -fno-asynchronous-unwind-tables -Xarch_host -fno-unwind-tables"
+COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $NO_UNWIND ${HFDL_EXTRA_FLAGS:-}"
 mkdir -p $BUILD
 pids=""
 objs=""

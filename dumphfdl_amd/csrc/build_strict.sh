@@ -19,7 +19,7 @@ for F in ${@:-0 1 2 4 8 15}; do
 	for o in $KERNEL_OBJS $SHIM_OBJS; do
 		if [ $o = demod_kernels ]; then objs="$objs $OUTDIR/demod_kernels_$F.o"; else objs="$objs ../build/$o.o"; fi
 	done
-	( $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off -DHFDL_DM_STRICT_FAST=$F -I. -c ../../tests/hostsim/strict_demod_kernels.hip -o $OUTDIR/demod_kernels_$F.o &&
+	( $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Xarch_host -fno-exceptions -Xarch_host -fno-asynchronous-unwind-tables -Xarch_host -fno-unwind-tables -ffp-contract=off -DHFDL_DM_STRICT_FAST=$F -I. -c ../../tests/hostsim/strict_demod_kernels.hip -o $OUTDIR/demod_kernels_$F.o &&
 	  $HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o $OUTDIR/libhfdl_gpu_strict_$F.so $objs ) & pids="$pids $!"
 done
 for p in $pids; do wait $p; done

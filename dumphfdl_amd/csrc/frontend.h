@@ -19,6 +19,7 @@
 #include "spectrum.h"
 #include "export_ring.h"
 #include "blanker.h"
+#include "iqbal.h"
 #include "notch.h"
 
 namespace hfdl {
@@ -137,6 +138,26 @@ struct Blanker {
 	uint64_t blocks = 0;                // steps blanked so far
 };
 
+// I/Q imbalance and DC corrector (hfdl_gpu_frontend_iqbal_enable; iqbal.h): never enabled = none, no launch.  One launch per step behind
+// the blanker's and in front of the forward FFT's first pass, on that block's FFT stream: it leaves the step's blocks, corrected, as cf32
+// in `scratch` -- or where the blanker left them, in place -- and the first pass reads them there.  One scratch serves every forward FFT,
+// as the blanker's does.  State and chunk sums live in two slots, written in turn (`step` counts the launches).  `ev` rides on the
+// launch's dispatch: a read of the record, and a seed, wait for the newest launch without a packet of their own on the stream.  Turned
+// off again the buffers stay until the front end goes.
+struct Iqbal {
+	std::vector<float> alpha;           // [nrx] 0: off
+	bool any_on = false;
+	uint64_t restart = 0;               // receivers whose next block is the first after an enable
+	DevBuf scratch;                     // [nrx][input_size] float2
+	DevBuf partial;                     // [2][nrx][5][blank_chunks(input_size)] float
+	DevBuf state;                       // [2][nrx] IqbalState
+	DevBuf seed;                        // [nrx] IqbalSeed
+	PinnedBuf<IqbalState> host;         // bounce buffer of a read: one record
+	Event ev;
+	uint64_t step = 0;                  // launches so far: launch i writes slot i & 1
+	uint32_t seeds = 0;                 // generation of the newest seed
+};
+
 // Adaptive carrier canceller (hfdl_gpu_frontend_notch_enable; notch.h): never enabled = none, no launch.  One launch per closed half on
 // stream B, in the half's hand-over to the demodulator (hfdl_gpu.cpp launch_demod): it reads the half's rows of d_chan_all and leaves
 // what the demodulator reads in `out`, a second buffer of d_chan_all's shape -- the channel export and stage tap 3 keep reading the
@@ -242,6 +263,7 @@ struct hfdl_gpu_frontend {
 	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
 	std::unique_ptr<hfdl::Blanker> blank;              // null: never enabled
 	std::unique_ptr<hfdl::Notch> notch;                // null: never enabled
+	std::unique_ptr<hfdl::Iqbal> iqbal;                // null: never enabled
 
 	// ---- events
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)

@@ -1,5 +1,5 @@
 // frontend_query.cpp -- what a caller reads from a front end: the error text, geometry, input-done queries, timers, statistics, stage
-// taps, counters, the spectrum monitor, the blanker's switch and record; and the page-locked allocator.
+// taps, counters, the spectrum monitor, the blanker's and the I/Q corrector's switches and records; and the page-locked allocator.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -523,6 +523,95 @@ extern "C" int hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx
 	out->samples_blanked = b->host.p->blanked;
 	out->last_power = b->host.p->power;
 	out->last_threshold = b->host.p->threshold;
+	return 0;
+}
+
+// ---------------------------------------------------------------- I/Q imbalance and DC corrector
+
+// rx = -1: every receiver
+static bool iqbal_targets(const hfdl_gpu_frontend *fe, int32_t rx, int &r0, int &r1)
+{
+	if (rx < -1 || rx >= fe->nrx) return false;
+	r0 = rx < 0 ? 0 : rx;
+	r1 = rx < 0 ? fe->nrx : rx + 1;
+	return true;
+}
+
+extern "C" int hfdl_gpu_frontend_iqbal_enable(hfdl_gpu_frontend *fe, int32_t rx, float alpha)
+{
+	if (!iqbal_alpha_valid(alpha)) return fail(HFDL_GPU_EINVAL, "I/Q corrector alpha %g", (double)alpha);
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	int r0, r1;
+	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	if (!fe->iqbal) {
+		if (alpha == 0.f) return 0;
+		HIP_TRY(hipSetDevice(fe->device));
+		const size_t K = (size_t)fe->nrx, n = (size_t)fe->geo.input_size;
+		auto q = std::make_unique<Iqbal>();
+		q->alpha.assign(K, 0.f);
+		hipError_t e = q->scratch.alloc(sizeof(float2) * K * n);
+		if (e == hipSuccess) e = q->partial.alloc(sizeof(float) * 2 * K * 5 * (size_t)blank_chunks((int)n));
+		if (e == hipSuccess) e = q->state.zeroed(sizeof(IqbalState) * 2 * K);
+		if (e == hipSuccess) e = q->seed.zeroed(sizeof(IqbalSeed) * K);
+		if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the clearing runs on the null stream, which the front end's streams do not follow
+		if (e == hipSuccess) e = q->host.alloc(1);
+		if (e == hipSuccess) e = q->ev.create(EV_NO_TIMING);
+		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "I/Q corrector buffers: %s", hipGetErrorString(e));
+		fe->iqbal = std::move(q);
+	}
+	Iqbal *q = fe->iqbal.get();
+	for (int r = r0; r < r1; r++) {
+		if (alpha > 0.f && q->alpha[(size_t)r] == 0.f) {
+			// on again: the estimate starts afresh with the next block, and a seed from before the switch is forgotten (the one wait of
+			// this call, and only where a seed was ever given: for the launch that may still be reading it)
+			q->restart |= (uint64_t)1 << r;
+			if (q->seeds) {
+				HIP_TRY(hipSetDevice(fe->device));
+				if (q->step) HIP_TRY(hipEventSynchronize(q->ev));
+				const IqbalSeed none = {};
+				HIP_TRY(hipMemcpy(q->seed.as<IqbalSeed>() + r, &none, sizeof(none), hipMemcpyHostToDevice));
+			}
+		}
+		q->alpha[(size_t)r] = alpha;
+	}
+	q->any_on = false;
+	for (float a : q->alpha) q->any_on = q->any_on || a > 0.f;
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_iqbal_seed(hfdl_gpu_frontend *fe, int32_t rx, float kappa_re, float kappa_im, float dc_re, float dc_im, int hold)
+{
+	if (!iqbal_seed_valid(kappa_re, kappa_im, dc_re, dc_im) || (hold != 0 && hold != 1)) return fail(HFDL_GPU_EINVAL, "I/Q corrector seed: |kappa| above 0.25, a value that is not finite, or hold %d", hold);
+	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
+	Iqbal *q = fe->iqbal.get();
+	int r0, r1;
+	if (!q) return fail(HFDL_GPU_EINVAL, "the I/Q corrector was never enabled");
+	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	for (int r = r0; r < r1; r++) if (q->alpha[(size_t)r] == 0.f) return fail(HFDL_GPU_EINVAL, "the I/Q corrector of receiver %d is off", r);
+	HIP_TRY(hipSetDevice(fe->device));
+	if (q->step) HIP_TRY(hipEventSynchronize(q->ev));       // the newest launch may still be reading the slot
+	IqbalSeed sd = {};
+	sd.k_re = kappa_re; sd.k_im = kappa_im; sd.m_re = dc_re; sd.m_im = dc_im; sd.gen = ++q->seeds; sd.hold = (uint32_t)hold;
+	for (int r = r0; r < r1; r++) HIP_TRY(hipMemcpy(q->seed.as<IqbalSeed>() + r, &sd, sizeof(sd), hipMemcpyHostToDevice));
+	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_iqbal_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_iqbal_stats *out)
+{
+	if (!fe || !out) return fail(HFDL_GPU_EINVAL, "null argument");
+	Iqbal *q = fe->iqbal.get();
+	if (!q) return fail(HFDL_GPU_EINVAL, "the I/Q corrector was never enabled");
+	if (rx < 0 || rx >= fe->nrx) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	memset(out, 0, sizeof(*out));
+	if (q->step == 0) return 0;
+	HIP_TRY(hipSetDevice(fe->device));
+	// the collection stream waits for the newest corrector launch (its event rode on the dispatch) and copies beside the kernels in flight
+	hipStream_t st = fe->demod.st_collect;
+	hipError_t e = hipStreamWaitEvent(st, q->ev, 0);
+	if (e == hipSuccess) e = hipMemcpyAsync(q->host.p, q->state.as<IqbalState>() + ((q->step - 1) & 1) * (size_t)fe->nrx + (size_t)rx, sizeof(IqbalState), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	HIP_TRY(e);
+	iqbal_stats_of(*q->host.p, out);
 	return 0;
 }
 

@@ -304,6 +304,22 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		fmt = SFMT_CF32;
 		b->blocks++;
 	}
+	if (Iqbal *q = fe->iqbal.get(); q && q->any_on) {
+		// the I/Q corrector: one launch behind the blanker's and in front of the first pass, which then reads the cf32 blocks it leaves --
+		// in the blanker's scratch, in place, where the blanker ran, in its own otherwise.  The timed pair and every event other streams
+		// wait for stay on the passes, as with the blanker
+		IqbalJob j;
+		const bool in_place = fmt == SFMT_CF32 && fe->blank && in.fresh[0] == fe->blank->scratch.p;
+		for (int r = 0; r < fe->nrx; r++) { j.fresh[r] = in.fresh[r]; j.alpha[r] = q->alpha[(size_t)r]; }
+		j.out = in_place ? fe->blank->scratch.as<float2>() : q->scratch.as<float2>(); j.out_stride = g.input_size;
+		j.partial = q->partial.as<float>(); j.state = q->state.as<IqbalState>(); j.seed = q->seed.as<IqbalSeed>();
+		j.restart = q->restart; j.n = g.input_size; j.nrx = fe->nrx; j.fmt = fmt; j.slot = (int)(q->step & 1);
+		launch_iqbal(j, st, q->ev);
+		for (int r = 0; r < fe->nrx; r++) in.fresh[r] = j.out + (size_t)r * (size_t)g.input_size;
+		fmt = SFMT_CF32;
+		q->restart = 0;
+		q->step++;
+	}
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
 	// The mixed domain: pass 2 leaves the fold's operand in the block's slot and carries fft_done; pass 3 runs for the spectrum monitor

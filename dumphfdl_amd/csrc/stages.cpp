@@ -149,6 +149,45 @@ extern "C" int hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int 
 	return 0;
 }
 
+// the I/Q corrector's launch as enqueue_fft queues it, on nblocks consecutive blocks of one receiver from a fresh enable (and a seed)
+extern "C" int hfdl_gpu_iqbal_blocks(int device, const void *raw, int32_t n, int32_t nblocks, int sample_format, float alpha,
+		const float *seed, int hold, float *out, hfdl_gpu_iqbal_stats *records)
+{
+	if (!raw || !out || !records || n < 1 || n > BLANK_N_MAX || nblocks < 1 || nblocks > IQBAL_BLOCKS_MAX || sample_format < SFMT_CF32 || sample_format > SFMT_CU8
+			|| !iqbal_alpha_valid(alpha) || alpha == 0.f || (hold != 0 && hold != 1) || (!seed && hold) || (seed && !iqbal_seed_valid(seed[0], seed[1], seed[2], seed[3])))
+		return fail(HFDL_GPU_EINVAL, "bad arguments");
+	int rc = select_device(device);
+	if (rc) return rc;
+	const size_t N = (size_t)n, B = (size_t)nblocks, G = (size_t)blank_chunks(n);
+	IqbalSeed sd = {};
+	if (seed) { sd.k_re = seed[0]; sd.k_im = seed[1]; sd.m_re = seed[2]; sd.m_im = seed[3]; sd.gen = 1; sd.hold = (uint32_t)hold; }
+	// block b reads state and chunk sums b and writes b + 1: the two slots of the pipeline, laid out as a row so every record is kept
+	DevBuf d_in, d_out, d_part, d_state, d_seed;
+	hipError_t e = d_in.upload(raw, sample_bytes(sample_format) * N * B);
+	if (e == hipSuccess) e = d_out.alloc(sizeof(float2) * N * B);
+	if (e == hipSuccess) e = d_part.alloc(sizeof(float) * (B + 1) * 5 * G);
+	if (e == hipSuccess) e = d_state.zeroed(sizeof(IqbalState) * (B + 1));
+	if (e == hipSuccess) e = d_seed.upload(&sd, sizeof(sd));
+	HIP_TRY(e);
+	StageTimer tm;
+	for (size_t b = 0; b < B; b++) {
+		IqbalJob j;
+		j.fresh[0] = d_in.as<char>() + sample_bytes(sample_format) * N * b; j.alpha[0] = alpha;
+		j.out = d_out.as<float2>() + N * b; j.out_stride = n;
+		j.partial = d_part.as<float>() + b * 5 * G; j.state = d_state.as<IqbalState>() + b; j.seed = d_seed.as<IqbalSeed>();
+		j.restart = b == 0; j.n = n; j.nrx = 1; j.fmt = sample_format; j.slot = 1;
+		launch_iqbal(j, nullptr);
+	}
+	g_stage_ms = tm.stop();
+	if ((rc = finish_stage())) return rc;
+	std::vector<IqbalState> rec(B + 1);
+	e = d_state.fetch(rec.data(), sizeof(IqbalState) * (B + 1));
+	if (e == hipSuccess) e = d_out.fetch(out, sizeof(float2) * N * B);
+	HIP_TRY(e);
+	for (size_t b = 0; b < B; b++) iqbal_stats_of(rec[b + 1], records + b);
+	return 0;
+}
+
 // the carrier canceller as the pipeline launches it in a half's hand-over: one "block" of nch rows of n samples each, every channel selected
 extern "C" int hfdl_gpu_notch_rows(int device, const float *x, int32_t nch, int32_t n, float mu, float *state, float *y)
 {

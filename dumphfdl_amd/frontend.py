@@ -62,6 +62,11 @@ class BlankerStats(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("samples_blanked", C.c_uint64), ("last_power", C.c_float), ("last_threshold", C.c_float)]
 
 
+class IqbalStats(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("refused", C.c_uint64), ("kappa_re", C.c_float), ("kappa_im", C.c_float), ("dc_re", C.c_float), ("dc_im", C.c_float),
+                ("power", C.c_float), ("image_rejection_db", C.c_float), ("valid", C.c_uint32), ("hold", C.c_uint32)]
+
+
 class NotchStats(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("resets", C.c_uint64), ("last_in_power", C.c_float), ("last_out_power", C.c_float), ("tap_energy", C.c_float)]
 
@@ -100,6 +105,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_quality_enable", "hfdl_gpu_frontend_quality_read", "hfdl_gpu_frame_quality_batch",
     "hfdl_gpu_frontend_blanker_enable", "hfdl_gpu_frontend_blanker_stats", "hfdl_gpu_blank_block",
     "hfdl_gpu_frontend_notch_enable", "hfdl_gpu_frontend_notch_stats", "hfdl_gpu_notch_rows",
+    "hfdl_gpu_frontend_iqbal_enable", "hfdl_gpu_frontend_iqbal_seed", "hfdl_gpu_frontend_iqbal_stats", "hfdl_gpu_iqbal_blocks",
 ]
 
 
@@ -233,6 +239,10 @@ def _bind(L):
     L.hfdl_gpu_frontend_blanker_enable.argtypes = [C.c_void_p, C.c_float]
     L.hfdl_gpu_frontend_blanker_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(BlankerStats)]
     L.hfdl_gpu_blank_block.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.hfdl_gpu_frontend_iqbal_enable.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+    L.hfdl_gpu_frontend_iqbal_seed.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]
+    L.hfdl_gpu_frontend_iqbal_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(IqbalStats)]
+    L.hfdl_gpu_iqbal_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.hfdl_gpu_frontend_notch_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]
     L.hfdl_gpu_frontend_notch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(NotchStats)]
     L.hfdl_gpu_notch_rows.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
@@ -616,6 +626,24 @@ class Frontend:
         _check(self._L.hfdl_gpu_frontend_blanker_stats(self._h, rx, C.byref(st)), self._L)
         return dict(blocks=st.blocks, samples_blanked=st.samples_blanked, last_power=np.float32(st.last_power), last_threshold=np.float32(st.last_threshold))
 
+    def iqbal_enable(self, alpha, rx=-1):
+        """Wideband I/Q imbalance and DC corrector (include/hfdl_gpu.h) of receiver rx (-1: every receiver): from the next pushed block on,
+        a block enters the transform as d - kappa conj(d), d = x - m, with (kappa, m) estimated from the blocks before it; alpha 2^-10 .. 1
+        is the weight of a block in the running averages, 0 turns it off."""
+        _check(self._L.hfdl_gpu_frontend_iqbal_enable(self._h, rx, float(alpha)), self._L)
+
+    def iqbal_seed(self, kappa, dc=0j, hold=False, rx=-1):
+        """Presets (kappa, dc) of receiver rx (-1: every receiver) from its next pushed block; hold: keep them, estimate nothing."""
+        kappa, dc = complex(kappa), complex(dc)
+        _check(self._L.hfdl_gpu_frontend_iqbal_seed(self._h, rx, kappa.real, kappa.imag, dc.real, dc.imag, int(bool(hold))), self._L)
+
+    def iqbal_stats(self, rx=0):
+        """dict(blocks, refused, kappa, dc, power, image_rejection_db, valid, hold) of receiver rx's newest block; waits for the forward
+        FFTs' side of the pipeline only."""
+        st = IqbalStats()
+        _check(self._L.hfdl_gpu_frontend_iqbal_stats(self._h, rx, C.byref(st)), self._L)
+        return iqbal_stats_to_dict(st)
+
     def notch_enable(self, mu, channels=None):
         """Adaptive carrier canceller (include/hfdl_gpu.h) in front of the demodulator of `channels` (None: every channel), each from
         zero state, for the blocks pushed from now on.  mu 1e-5 .. 0.05; 0 turns it off."""
@@ -738,6 +766,33 @@ def blank_block(raw, sample_format, threshold_db, device=0):
     power, blanked = C.c_float(0), C.c_uint64(0)
     _check(load().hfdl_gpu_blank_block(device, _p(r) if n else None, n, sample_format, float(threshold_db), _p(out) if n else None, C.byref(power), C.byref(blanked)))
     return out, np.float32(power.value), blanked.value
+
+
+IQBAL_BLOCKS_MAX = 64      # blocks of one iqbal_blocks() call (dumphfdl_amd/csrc/iqbal.h)
+
+
+def iqbal_stats_to_dict(st):
+    return dict(blocks=st.blocks, refused=st.refused, kappa=np.complex64(complex(st.kappa_re, st.kappa_im)), dc=np.complex64(complex(st.dc_re, st.dc_im)),
+                power=np.float32(st.power), image_rejection_db=np.float32(st.image_rejection_db), valid=bool(st.valid), hold=bool(st.hold))
+
+
+def iqbal_blocks(raw, n, sample_format, alpha, seed=None, hold=False, device=0):
+    """The I/Q corrector alone (hfdl_gpu_iqbal_blocks) on consecutive blocks of n samples of one receiver, from a fresh enable: raw =
+    float32 / int16 / uint8 numpy array of 2 n nblocks interleaved I, Q values (a complex64 array for SFMT_CF32 will do); seed = None or
+    (kappa, dc).  Returns (out: nblocks * n complex64 as they would enter the transform, records: the IqbalStats array, one per block)."""
+    dt = {SFMT_CF32: np.float32, SFMT_CS16: np.int16, SFMT_CU8: np.uint8}[sample_format]
+    r = np.asarray(raw)
+    if sample_format == SFMT_CF32 and r.dtype == np.complex64:
+        r = np.ascontiguousarray(r).view(np.float32)
+    r = np.ascontiguousarray(r, dtype=dt)
+    n = int(n)
+    nblocks = len(r) // (2 * n) if n > 0 else 0
+    out = np.zeros(max(nblocks, 0) * max(n, 0), np.complex64)
+    recs = (IqbalStats * max(nblocks, 1))()
+    sd = None if seed is None else np.array([complex(seed[0]).real, complex(seed[0]).imag, complex(seed[1]).real, complex(seed[1]).imag], np.float32)
+    _check(load().hfdl_gpu_iqbal_blocks(device, _p(r) if r.size else None, n, nblocks, sample_format, float(alpha), _p(sd) if sd is not None else None,
+                                        int(bool(hold)), _p(out) if out.size else None, C.cast(recs, C.c_void_p)))
+    return out, recs
 
 
 NOTCH_STATE_FLOATS = 174   # HFDL_GPU_NOTCH_STATE_FLOATS: 32 taps (re, im), then the last 55 inputs (re, im), newest first

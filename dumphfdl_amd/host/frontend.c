@@ -24,6 +24,9 @@
 /* ... and the impulse-noise blanker: asked of such a library, fft_create() refuses */
 #pragma weak hfdl_gpu_frontend_blanker_enable
 #pragma weak hfdl_gpu_frontend_blanker_stats
+/* ... and the I/Q imbalance and DC corrector likewise */
+#pragma weak hfdl_gpu_frontend_iqbal_enable
+#pragma weak hfdl_gpu_frontend_iqbal_stats
 /* ... and the adaptive carrier canceller likewise */
 #pragma weak hfdl_gpu_frontend_notch_enable
 #pragma weak hfdl_gpu_frontend_notch_stats
@@ -79,6 +82,7 @@ struct gpu_fft_block {
 	struct iq_export_settings iqx;
 	char *frame_log;                         /* path, NULL = off */
 	float blanker_db;                        /* 0 = off */
+	float iq_alpha;                          /* 0 = off */
 	struct notch_settings notch;             /* mu 0 = off */
 };
 
@@ -119,6 +123,14 @@ int hfdl_frontend_set_blanker(float threshold_db)
 {
 	if (!(threshold_db == 0.f || (threshold_db >= 6.f && threshold_db <= 60.f))) return -1;
 	g_blanker_db = threshold_db;
+	return 0;
+}
+
+static float g_iq_alpha;
+int hfdl_frontend_set_iq_correction(float alpha)
+{
+	if (!(alpha == 0.f || (alpha >= 1.f / 1024.f && alpha <= 1.f))) return -1;
+	g_iq_alpha = alpha;
 	return 0;
 }
 
@@ -1033,6 +1045,7 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 		t->fs = (double)slots[0]->sample_rate;
 		t->centerfreq = (double)slots[0]->centerfreq;
 		if (fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_enable(t->fe, fb->blanker_db) != 0) fail(t, hfdl_gpu_last_error());
+		if (t->ok && fb->iq_alpha != 0.f && hfdl_gpu_frontend_iqbal_enable(t->fe, -1, fb->iq_alpha) != 0) fail(t, hfdl_gpu_last_error());
 		const char *why = NULL;
 		if (t->ok && fb->notch.mu != 0.f && notch_start(t->fe, &fb->notch, t->freqs, t->nch, &why) != 0) fail(t, why);
 	}
@@ -1075,6 +1088,14 @@ static void frontend_teardown(struct fe_thread *t)
 		if (t->fb->blanker_db != 0.f && hfdl_gpu_frontend_blanker_stats(t->fe, 0, &bs) == 0)
 			fprintf(stderr, "blanker: receiver 0: %llu samples blanked in %llu blocks (%g dB)\n", (unsigned long long)bs.samples_blanked,
 					(unsigned long long)bs.blocks, (double)t->fb->blanker_db);
+		/* one line per receiver (a receiver the front end does not have has no record: its call fails and ends the list) */
+		for (int32_t r = 0; t->fb->iq_alpha != 0.f && r < 64; r++) {
+			hfdl_gpu_iqbal_stats is;
+			if (hfdl_gpu_frontend_iqbal_stats(t->fe, r, &is) != 0) break;
+			fprintf(stderr, "iq-correct: receiver %d: kappa %+.6f%+.6fj (image %.1f dB down), dc %+.6f%+.6fj, %llu of %llu blocks refused (alpha %g)\n", (int)r,
+					(double)is.kappa_re, (double)is.kappa_im, (double)is.image_rejection_db, (double)is.dc_re, (double)is.dc_im,
+					(unsigned long long)is.refused, (unsigned long long)is.blocks, (double)t->fb->iq_alpha);
+		}
 		/* one line per cancelled channel (a channel that was not selected has no record: its call fails and prints nothing) */
 		for (size_t c = 0; t->fb->notch.mu != 0.f && c < t->nch; c++) {
 			hfdl_gpu_notch_stats ns;
@@ -1189,12 +1210,18 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 		free(fb);
 		return NULL;
 	}
+	if (g_iq_alpha != 0.f && (hfdl_gpu_frontend_iqbal_enable == NULL || hfdl_gpu_frontend_iqbal_stats == NULL)) {
+		fprintf(stderr, "iq-correct: this GPU library has no I/Q imbalance corrector\n");
+		free(fb);
+		return NULL;
+	}
 	if (g_notch.mu != 0.f && (hfdl_gpu_frontend_notch_enable == NULL || hfdl_gpu_frontend_notch_stats == NULL)) {
 		fprintf(stderr, "notch: this GPU library has no carrier canceller\n");
 		free(fb);
 		return NULL;
 	}
 	fb->blanker_db = g_blanker_db;
+	fb->iq_alpha = g_iq_alpha;
 	fb->notch = notch_settings_copy(&g_notch);
 	fb->frame_log = g_frame_log ? strdup(g_frame_log) : NULL;
 	fb->decimation = decimation;

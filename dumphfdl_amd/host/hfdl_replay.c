@@ -5,7 +5,7 @@
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
  *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
- *               [--frame-log FILE] [--blanker DB] [--notch MU[:KHZ,...]] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
+ *               [--frame-log FILE] [--blanker DB] [--iq-correct ALPHA] [--notch MU[:KHZ,...]] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -23,6 +23,10 @@
  *
  * --blanker DB          wideband impulse-noise blanker (hfdl_frontend_set_blanker, include/hfdl_host.h): a raw sample more than DB
  *               (6 .. 60) above its block's mean power enters the forward FFT as zero; one line on stderr at the end gives the count.
+ *
+ * --iq-correct ALPHA    wideband I/Q imbalance and DC corrector (hfdl_frontend_set_iq_correction, include/hfdl_host.h): every block
+ *               enters the forward FFT with the image and DC offset estimated from the blocks before it removed; ALPHA (2^-10 .. 1;
+ *               0.125 is the tested one) is a block's weight in the estimate; one line per receiver on stderr at the end.
  *
  * --notch MU[:KHZ,KHZ,...]   adaptive carrier canceller (hfdl_frontend_set_notch, include/hfdl_host.h) with step MU (1e-5 .. 0.05; 0.002
  *               is the tested one) in front of the demodulator of the listed channels, or of every channel; one line per cancelled
@@ -129,6 +133,9 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--frame-log") && i + 1 < argc) frame_log = argv[++i];
 		else if (!strcmp(argv[i], "--blanker") && i + 1 < argc) {
 			if (hfdl_frontend_set_blanker((float)atof(argv[++i])) != 0) { fprintf(stderr, "--blanker wants a threshold of 6 to 60 dB (or 0 = off)\n"); return 1; }
+		}
+		else if (!strcmp(argv[i], "--iq-correct") && i + 1 < argc) {
+			if (hfdl_frontend_set_iq_correction((float)atof(argv[++i])) != 0) { fprintf(stderr, "--iq-correct wants an alpha of 1/1024 to 1 (or 0 = off)\n"); return 1; }
 		}
 		else if (!strcmp(argv[i], "--notch") && i + 1 < argc) {
 			/* MU[:KHZ,KHZ,...] */

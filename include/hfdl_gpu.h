@@ -498,6 +498,44 @@ typedef struct {
  * range, or a front end whose blanker was never enabled. */
 int  hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_blanker_stats *out);
 
+/* Wideband I/Q imbalance and DC corrector (off by default: nothing is allocated or launched, and the block path differs by one host
+ * branch).  A zero-IF receiver whose I and Q arms differ in gain and phase delivers x = s + kappa conj(s) + m: every signal at +f leaves
+ * an image at -f, 25 to 40 dB down, and a spike at 0 Hz.  Behind a channel filter the image of a broadcast station is in-band signal on
+ * an HFDL channel; in front of the forward FFT, removing it is one complex multiply per sample.  The rule (dumphfdl_amd/csrc/iqbal.h)
+ * is per receiver and feed-forward: running averages, with weight alpha per block (the cumulative mean before that), of the means of x,
+ * x^2 and |x|^2 over the input_size NEW samples of each block -- after the sample-format conversion and after the blanker -- give
+ * m, C = E (x - m)^2 and P = E |x - m|^2; kappa = C / (P + sqrt(P^2 - |C|^2)), exact for a proper s; block b enters the transform as
+ * d - kappa conj(d), d = x - m, with the estimate from the blocks BEFORE b.  A block without an estimate -- the first after an enable,
+ * P not positive or not finite, or |C| > 0.5 P: a real-valued stream, which the rule must never cancel against itself -- is copied word for
+ * word and counted as refused.  A block whose sums are not all finite leaves the estimate as it was.  fp32, in one fixed order: results do
+ * not depend on how blocks are pushed, polled or batched.  The spectrum monitor and tap 1 see the corrected spectra; retune, export,
+ * quality records and the carrier canceller are untouched.  It works with every entry point that takes wideband input.
+ * One complex kappa per receiver corrects the part of the imbalance that is flat over the band.
+ *
+ * alpha 2^-10 .. 1 turns receiver rx (-1: every receiver) on from the next pushed block, 0 off; turned on again, the estimate starts
+ * afresh.  1/8 is the tested value: kappa within 1 % after one block of the tested scenario.  The first enabling call allocates (one
+ * block of cf32 per receiver, kept until the front end is destroyed); later calls wait for nothing, except that turning a receiver on
+ * again after a seed waits for the corrector launches queued so far.  HFDL_GPU_EINVAL (any other alpha, NaN included; null handle; rx out
+ * of range) is returned before any device work. */
+int  hfdl_gpu_frontend_iqbal_enable(hfdl_gpu_frontend *fe, int32_t rx, float alpha);
+/* Presets (kappa, DC) of receiver rx (-1: every receiver) from its next pushed block.  hold = 1: a fixed, calibrated correction that no
+ * block changes; hold = 0: the estimator starts from them as if one block had been seen.  Waits for the corrector launches queued so far.
+ * HFDL_GPU_EINVAL, before any device work: |kappa| > 0.25, a value that is not finite, hold not 0 or 1, null handle, rx out of range, a
+ * corrector that was never enabled or is off for the receiver. */
+int  hfdl_gpu_frontend_iqbal_seed(hfdl_gpu_frontend *fe, int32_t rx, float kappa_re, float kappa_im, float dc_re, float dc_im, int hold);
+typedef struct {
+	uint64_t blocks, refused;               /* blocks of this receiver that went through the corrector since the first enable; those copied */
+	float    kappa_re, kappa_im;            /* what its newest block was corrected with (valid), else 0 */
+	float    dc_re, dc_im;
+	float    power;                         /* P of that estimate (0 under a seed or a hold) */
+	float    image_rejection_db;            /* -20 log10 |kappa|: how far below its signal the uncorrected image lies (valid; kappa = 0: +Inf) */
+	uint32_t valid, hold;                   /* the newest block was corrected; with a held preset */
+} hfdl_gpu_iqbal_stats;
+/* Receiver rx's record.  Waits as hfdl_gpu_frontend_blanker_stats() does -- for the corrector launches queued so far, on the collection
+ * stream -- and queues nothing on the kernels' streams.  No block yet: all zero.  HFDL_GPU_EINVAL: null argument, rx out of range, or a
+ * front end whose corrector was never enabled. */
+int  hfdl_gpu_frontend_iqbal_stats(hfdl_gpu_frontend *fe, int32_t rx, hfdl_gpu_iqbal_stats *out);
+
 /* Adaptive carrier canceller per channel (off by default: nothing is allocated or launched, and the block path differs by one host
  * branch).  Steady carriers inside a channel's 2.4 kHz passband -- broadcast and utility carriers, CW, receiver birdies -- pass the
  * channel filter, and a tone a few dB above the burst defeats the preamble search and the slicer.  Between the channelizer's output and
@@ -593,6 +631,13 @@ int  hfdl_gpu_burst_decode(int device, const float *symbols, const int32_t *mode
  * threshold_db 6 .. 60.  Every argument is checked before a device is selected. */
 int  hfdl_gpu_blank_block(int device, const void *raw, int32_t n, int sample_format, float threshold_db,
 		float *out, float *power, uint64_t *blanked);
+/* the I/Q corrector (hfdl_gpu_frontend_iqbal_enable above) alone, by the kernel of the front end, on nblocks (1 .. 64) consecutive
+ * blocks of n samples (1 .. 2^24) of one receiver from a fresh enable: raw = nblocks * n samples of sample_format; alpha 2^-10 .. 1;
+ * seed = NULL, or kappa_re, kappa_im, dc_re, dc_im given before the first block (hold as above; 0 without a seed).  out = the
+ * nblocks * n cf32 samples as they would enter the transform, records[b] = the record after block b.  Every argument is checked before a
+ * device is selected. */
+int  hfdl_gpu_iqbal_blocks(int device, const void *raw, int32_t n, int32_t nblocks, int sample_format, float alpha,
+		const float *seed, int hold, float *out, hfdl_gpu_iqbal_stats *records);
 /* the carrier canceller (hfdl_gpu_frontend_notch_enable above) alone, by the kernel of the front end: x, y = [nch][n] cf32, every row a
  * channel's next n samples; state = [nch][HFDL_GPU_NOTCH_STATE_FLOATS], in and out, NULL = fresh and discarded.  mu 1e-5 .. 0.05.
  * Every argument is checked before a device is selected. */

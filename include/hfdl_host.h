@@ -229,6 +229,13 @@ int           hfdl_frontend_set_frame_log(const char *path);
  * stops, one line on stderr gives the samples blanked and the blocks seen.  Returns 0, or -1 for any other threshold_db (NaN included).
  * With a GPU library that lacks the blanker, fft_create() fails with a message on stderr. */
 int           hfdl_frontend_set_blanker(float threshold_db);
+/* I/Q imbalance and DC corrector of the front end created by the next fft_create() (include/hfdl_gpu.h, "Wideband I/Q imbalance and DC
+ * corrector"); not in the reference, which leaves it to the SDR's driver -- a file, a pipe or a multi-receiver push has no driver.
+ * alpha 2^-10 .. 1: every receiver's blocks enter the transform with the image and the DC offset estimated from the blocks before them
+ * removed, alpha the weight of a block in the estimate (1/8 is the tested value); 0: off (the default).  When the front end stops, one
+ * line per receiver on stderr gives kappa, the DC offset and the blocks refused.  Returns 0, or -1 for any other alpha (NaN included).
+ * With a GPU library that lacks the corrector, fft_create() fails with a message on stderr. */
+int           hfdl_frontend_set_iq_correction(float alpha);
 /* Adaptive carrier canceller of the front end created by the next fft_create() (include/hfdl_gpu.h, "Adaptive carrier canceller"); not
  * in the reference, whose users notch in the SDR.  mu 1e-5 .. 0.05: the channels on freqs_khz[0 .. n - 1] (n = 0: every channel) run a
  * 32-tap normalised-LMS line canceller with that step in front of their demodulator; 0: off (the default).  When the front end stops,
