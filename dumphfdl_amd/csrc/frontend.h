@@ -21,6 +21,7 @@
 #include "blanker.h"
 #include "iqbal.h"
 #include "notch.h"
+#include "real_input.h"
 
 namespace hfdl {
 
@@ -187,6 +188,7 @@ struct Notch {
 // pass of the tap FFT behind the copy out of stage[i]: the call's only host wait.  `done` rides on retune_channelizer_kernel.
 struct Retune {
 	DevBuf pad, work;
+	DevBuf eo;                          // a real front end: the transforms of the even and the odd taps, 2 N' words (queue_real_taps)
 	PinnedBuf<float2> stage[2];
 	Event staged[2];
 	DoneEvent done;
@@ -202,6 +204,11 @@ struct Retune {
 // lp / lp_cut: the caller's cache of the low-pass prototype (planner.h design_bandpass); taps == nullptr: the constants alone.  False: the
 // planner refuses the shift.
 bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, hfdl::ChanConst &k, std::complex<float> *taps, std::vector<float> &lp, float &lp_cut);
+// A real front end (real_input.h): design_channel leaves taps_host_len() words, the even taps and then the odd ones, each a zero-padded
+// input of the N'-point plan.  queue_real_taps queues, on `st`, their two transforms -- through `pad` (N' words, zero past taps_length)
+// and `work` into eo[0 .. N') and eo[N' .. 2N') -- and the combine into padded slot `slot` of the tap buffer.  `host` is read by the two
+// copies; `staged` (may be null) rides on the pass that reads `pad` last.  build_taps() and a retune both call it.
+int queue_real_taps(hfdl_gpu_frontend *fe, const float2 *host, float2 *pad, float2 *work, float2 *eo, int slot, hipStream_t st, hipEvent_t staged);
 
 // Members are destroyed in reverse order of declaration: events first, then memory, then the streams (the destructor has synchronised
 // them).  So: streams, then memory, then events.
@@ -288,6 +295,13 @@ struct hfdl_gpu_frontend {
 		return ev_stage_ready[(newest - host_block <= span ? host_block : newest - span) % (uint64_t)n_stage];
 	}
 	int32_t sample_rate = 0, decimation = 0;
+	// Real-sampled input (hfdl_gpu_frontend_create_real; real_input.h): real_rate = fs_r, 0 for a complex front end.  sample_rate and
+	// rx_center then describe the equivalent complex stream (fs_r / 2, base + fs_r / 4), which is what everything else is planned for;
+	// d_real [nrx][N'] takes pass 3's unshifted output, and the untangle launch behind it fills the block's spectrum slot.
+	int32_t real_rate = 0;
+	std::vector<int32_t> rx_base;       // [nrx] the RF frequency at 0 Hz of each receiver's samples
+	float2 *d_real = nullptr;
+	size_t taps_host_len() const { return real_rate ? 2 * (size_t)plan.taps_length : (size_t)plan.taps_length; }
 	float tbw = 0;
 	hfdl::Plan plan{};                  // shift = 0 geometry (src/fft.c:70-86)
 	hfdl::Geometry geo{};

@@ -103,6 +103,7 @@ bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, ChanConst
 {
 	// src/hfdl.c:476: shift relative to the SSB carrier 1440 Hz above the channel frequency -- from the centre of ITS receiver
 	float shift = (float)(fe->rx_center[(size_t)rx] - (freq + 1440)) / (float)fe->sample_rate;
+	if (fe->real_rate) shift = real_shift(fe->real_rate, fe->rx_base[(size_t)rx], freq);      // the equivalent stream's, its centre taken exactly
 	Plan cp;
 	if (!plan_block(cp, fe->tbw, fe->decimation, shift)) return false;
 	k = ChanConst{};
@@ -110,9 +111,30 @@ bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, ChanConst
 	k.nco_sindelta = cp.sindelta; k.nco_cosdelta = cp.cosdelta; k.nco_rate = cp.rate;
 	k.frequency = freq;
 	if (taps == nullptr) return true;          // the constants alone
+	if (fe->real_rate) {
+		// designed at the REAL rate, 2 overlap' + 1 taps, then split into the even and the odd ones (real_input.h)
+		// -- the one function the host build calls too, so the words are that build's by construction
+		std::vector<std::complex<float>> h((size_t)real_taps_length(fe->plan.taps_length));
+		real_design_taps(fe->real_rate, fe->rx_base[(size_t)rx], freq, fe->decimation, fe->plan.taps_length, h.data(), taps, lp, lp_cut);
+		return true;
+	}
 	float half_bw = 0.5f / fe->decimation;
 	design_bandpass(taps, fe->plan.taps_length, (-shift) - half_bw, (-shift) + half_bw, lp, lp_cut);
 	return true;
+}
+
+int queue_real_taps(hfdl_gpu_frontend *fe, const float2 *host, float2 *pad, float2 *work, float2 *eo, int slot, hipStream_t st, hipEvent_t staged)
+{
+	const size_t T = (size_t)fe->plan.taps_length, n = (size_t)fe->plan.n;
+	for (int half = 0; half < 2; half++) {
+		HIP_TRY(hipMemcpyAsync(pad, host + (size_t)half * T, sizeof(float2) * T, hipMemcpyHostToDevice, st));
+		launch_fft_forward(fe->fft.p, nullptr, pad, SFMT_CF32, 0, nullptr, work, eo + (size_t)half * n, false, st, FftOutLayout(), nullptr, NcoJob(), half ? staged : nullptr);
+	}
+	RealTapJob j;
+	j.e = eo; j.o = eo + n; j.taps = (float *)fe->d_taps; j.rs_f = (size_t)fe->geo.tap_row_stride * 2;
+	j.n = fe->plan.n; j.logn = ilog2(fe->plan.n); j.m_log = ilog2(fe->plan.m); j.kind = fe->geo.tap_layout; j.slot = slot;
+	launch_real_tap_combine(j, st);
+	return 0;
 }
 
 static int build_taps(hfdl_gpu_frontend *fe)
@@ -121,7 +143,8 @@ static int build_taps(hfdl_gpu_frontend *fe)
 	const int nch = (int)fe->freqs.size();
 	const size_t n = (size_t)pl.n;
 	// time-domain taps on the host (exact reference arithmetic), one worker per hardware thread
-	std::vector<std::complex<float>> host((size_t)nch * (size_t)pl.taps_length);
+	const size_t per = fe->taps_host_len();
+	std::vector<std::complex<float>> host((size_t)nch * per);
 	fe->cc.resize((size_t)nch);
 	unsigned nthreads = std::max(1u, std::min((unsigned)nch, std::thread::hardware_concurrency()));
 	// several front ends created at once on one host (one process per GPU): share the cores
@@ -134,7 +157,7 @@ static int build_taps(hfdl_gpu_frontend *fe)
 		for (;;) {
 			int c = next.fetch_add(1);
 			if (c >= nch) break;
-			if (!design_channel(fe, fe->rx_of[(size_t)c], fe->freqs[c], fe->cc[c], host.data() + (size_t)c * pl.taps_length, lp, lp_cut)) bad++;
+			if (!design_channel(fe, fe->rx_of[(size_t)c], fe->freqs[c], fe->cc[c], host.data() + (size_t)c * per, lp, lp_cut)) bad++;
 		}
 	};
 	std::vector<std::thread> pool;
@@ -150,7 +173,14 @@ static int build_taps(hfdl_gpu_frontend *fe)
 	HIP_TRY(hipMemsetAsync(d_pad, 0, sizeof(float2) * n, fe->stream));
 	if (fe->geo.nch_pad > nch)          // the slots that fill each receiver's last group of the interleaved layout up: all-zero taps
 		HIP_TRY(hipMemsetAsync(fe->d_taps, 0, sizeof(float2) * n * (size_t)fe->geo.nch_pad, fe->stream));
+	DevBuf eo;
+	if (fe->real_rate) HIP_TRY(eo.alloc(sizeof(float2) * 2 * n));
 	for (int c = 0; c < nch; c++) {
+		if (fe->real_rate) {
+			// real input: the transforms of the even and the odd taps, combined into the slot
+			if (int rc = queue_real_taps(fe, (const float2 *)(host.data() + (size_t)c * per), d_pad, fe->d_work, eo.as<float2>(), fe->slot_of(c), fe->stream, nullptr)) return rc;
+			continue;
+		}
 		HIP_TRY(hipMemcpyAsync(d_pad, host.data() + (size_t)c * pl.taps_length, sizeof(float2) * (size_t)pl.taps_length,
 				hipMemcpyHostToDevice, fe->stream));
 		// the last pass writes the channel's filter straight into the matrix-operand layout (kernels.h tap_index_f), at its padded slot
@@ -286,7 +316,8 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	// HFDL_GPU_FOLD_PRUNE=tol (0 < tol <= 1e-3; unset: every alias row is folded, the reference's sum term for term): fold only the
 	// rows around each channel's pass band (build_fold_windows) -- one slice, the windows are the parallelism
 	// (the pruned fold's windows are per octet of ONE receiver's taps: off with several receivers)
-	fe->prune_tol = g.tap_layout == TAPL_OCTET && nrx == 1 ? env_double("HFDL_GPU_FOLD_PRUNE", 1e-12, 1e-3, 0.0) : 0.0;
+	// (and per octet of taps whose spectrum is stored: a real front end ignores it, and HFDL_GPU_FOLD_SPECTRUM=0 below, as well)
+	fe->prune_tol = g.tap_layout == TAPL_OCTET && nrx == 1 && !fe->real_rate ? env_double("HFDL_GPU_FOLD_PRUNE", 1e-12, 1e-3, 0.0) : 0.0;
 	// fold_bound: with many channels the fold bounds the block; the demodulator launches of a half are then held back until the next
 	// half's forward FFTs are queued (launch_demod) instead of starting at once.
 	fe->fold_bound = lab.fold_bound < 0 ? nch >= 128 : lab.fold_bound != 0;
@@ -318,7 +349,7 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 		// lands 2.8 x further from the float64 model (2.4 Msps x 130 channels: 1.57e-4 against 5.6e-5 relative RMS at worst) -- past the
 		// gate of tests/test_gpu_channelizer_f64.py at one (block, channel) of 1392.
 		const FftPlan &fp = fe->fft.p;
-		if (g.tap_layout == TAPL_OCTET && mixed_fold_fits(fp.l1, fp.l2, fp.l3, ilog2(pl.m), fe->prune_tol > 0) && env_long("HFDL_GPU_FOLD_SPECTRUM", 0, 1, 1) == 0) {
+		if (!fe->real_rate && g.tap_layout == TAPL_OCTET && mixed_fold_fits(fp.l1, fp.l2, fp.l3, ilog2(pl.m), fe->prune_tol > 0) && env_long("HFDL_GPU_FOLD_SPECTRUM", 0, 1, 1) == 0) {
 			g.mix_l1 = fp.l1; g.mix_q = ilog2(pl.m) - fp.l1;
 			g.spec_row_stride = 16; g.spec_group_stride = 16 * (int64_t)pl.pre;
 		}
@@ -330,6 +361,7 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 		CREATE_TRY(hipMemsetAsync(fe->d_hist[i], 0, sizeof(float2) * (size_t)pl.overlap * K, fe->stream));   // calloc'ed history, src/fft.c:79
 	}
 	CREATE_TRY(fe->alloc(fe->d_work, n * K));
+	if (fe->real_rate) CREATE_TRY(fe->alloc(fe->d_real, n * K));
 	CREATE_TRY(fe->alloc(fe->d_rx, K));
 	CREATE_TRY(hipMemcpy(fe->d_rx, fe->rx_host.data(), sizeof(int4) * K, hipMemcpyHostToDevice));
 	g.rx_tab = fe->d_rx;
@@ -377,8 +409,9 @@ static int create_frontend(hfdl_gpu_frontend *fe, int32_t nrx, const int32_t *nc
 	return 0;
 }
 
-extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx,
-		const int32_t *centerfreqs, const int32_t *freqs, const int32_t *nch_per_rx)
+// real_rate / bases: a real front end (hfdl_gpu_frontend_create_real), whose sample_rate and centerfreqs are the equivalent stream's
+static int create_any(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx, const int32_t *centerfreqs, const int32_t *freqs,
+		const int32_t *nch_per_rx, int32_t real_rate, const int32_t *bases)
 {
 	int rc = check_create_args(out, sample_rate, nrx, centerfreqs, freqs, nch_per_rx);
 	if (rc || (rc = select_device(device))) return rc;
@@ -392,10 +425,33 @@ extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int devic
 	fe->freqs.assign(freqs, freqs + nch);
 	fe->nrx = nrx;
 	fe->rx_center.assign(centerfreqs, centerfreqs + nrx);
+	fe->real_rate = real_rate;
+	if (real_rate) fe->rx_base.assign(bases, bases + nrx);
 	for (int r = 0; r < nrx; r++) fe->rx_of.insert(fe->rx_of.end(), (size_t)nch_per_rx[r], r);
 	if ((rc = create_frontend(fe.get(), nrx, nch_per_rx))) return rc;       // (the destructor releases what a failed create got as far as)
 	*out = fe.release();
 	return 0;
+}
+
+extern "C" int hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t sample_rate, int32_t nrx,
+		const int32_t *centerfreqs, const int32_t *freqs, const int32_t *nch_per_rx)
+{
+	return create_any(out, device, sample_rate, nrx, centerfreqs, freqs, nch_per_rx, 0, nullptr);
+}
+
+// Real-sampled receivers: planned as the equivalent complex streams (real_input.h), checked like them
+extern "C" int hfdl_gpu_frontend_create_real(hfdl_gpu_frontend **out, int device, int32_t sample_rate_real, int32_t nrx,
+		const int32_t *base_freqs, const int32_t *freqs, const int32_t *nch_per_rx)
+{
+	if (out) *out = nullptr;
+	if (!base_freqs || !freqs || !nch_per_rx || nrx < 1 || nrx > HFDL_GPU_RECEIVERS_MAX) return fail(HFDL_GPU_EINVAL, "bad arguments: null pointer, or %d receivers", nrx);
+	if (sample_rate_real < REAL_RATE_MIN || (sample_rate_real & 1)) return fail(HFDL_GPU_EINVAL, "real sample rate %d: even and >= %d", sample_rate_real, REAL_RATE_MIN);
+	int32_t centres[HFDL_GPU_RECEIVERS_MAX];
+	for (int r = 0; r < nrx; r++) {
+		if (!real_base_valid(sample_rate_real, base_freqs[r])) return fail(HFDL_GPU_EINVAL, "receiver %d: base %d Hz out of range", r, base_freqs[r]);
+		centres[r] = real_equiv_centre(sample_rate_real, base_freqs[r]);
+	}
+	return create_any(out, device, real_equiv_rate(sample_rate_real), nrx, centres, freqs, nch_per_rx, sample_rate_real, base_freqs);
 }
 
 // The order, explicitly: every owned stream (the demodulator's collection stream too) and the monitor's event are synchronised; then

@@ -76,6 +76,14 @@ extern "C" int hfdl_gpu_frontend_channel_receiver(const hfdl_gpu_frontend *fe, i
 	return 0;
 }
 
+extern "C" int hfdl_gpu_frontend_real_input(const hfdl_gpu_frontend *fe, int32_t *is_real, int32_t *real_rate)
+{
+	if (!fe || !is_real || !real_rate) return fail(HFDL_GPU_EINVAL, "null argument");
+	*is_real = fe->real_rate != 0;
+	*real_rate = fe->real_rate;
+	return 0;
+}
+
 // ---------------------------------------------------------------- page-locked host memory
 
 // page-locked ranges handed out by hfdl_gpu_host_alloc(): only these are left to the DMA engine after push_block returns
@@ -531,7 +539,7 @@ extern "C" int hfdl_gpu_frontend_blanker_stats(hfdl_gpu_frontend *fe, int32_t rx
 // rx = -1: every receiver
 static bool iqbal_targets(const hfdl_gpu_frontend *fe, int32_t rx, int &r0, int &r1)
 {
-	if (rx < -1 || rx >= fe->nrx) return false;
+	if (rx < -1 || rx >= fe->nrx || fe->real_rate) return false;       // (real samples: there is no I/Q to balance)
 	r0 = rx < 0 ? 0 : rx;
 	r1 = rx < 0 ? fe->nrx : rx + 1;
 	return true;
@@ -542,7 +550,7 @@ extern "C" int hfdl_gpu_frontend_iqbal_enable(hfdl_gpu_frontend *fe, int32_t rx,
 	if (!iqbal_alpha_valid(alpha)) return fail(HFDL_GPU_EINVAL, "I/Q corrector alpha %g", (double)alpha);
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	int r0, r1;
-	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
+	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers), or a front end for real input", rx, fe->nrx);
 	if (!fe->iqbal) {
 		if (alpha == 0.f) return 0;
 		HIP_TRY(hipSetDevice(fe->device));
@@ -585,8 +593,9 @@ extern "C" int hfdl_gpu_frontend_iqbal_seed(hfdl_gpu_frontend *fe, int32_t rx, f
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	Iqbal *q = fe->iqbal.get();
 	int r0, r1;
+	// (the receiver and the kind of front end first: a real front end says so, whatever else is wrong -- its corrector can never have been enabled)
+	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers), or a front end for real input", rx, fe->nrx);
 	if (!q) return fail(HFDL_GPU_EINVAL, "the I/Q corrector was never enabled");
-	if (!iqbal_targets(fe, rx, r0, r1)) return fail(HFDL_GPU_EINVAL, "receiver %d out of range (%d receivers)", rx, fe->nrx);
 	for (int r = r0; r < r1; r++) if (q->alpha[(size_t)r] == 0.f) return fail(HFDL_GPU_EINVAL, "the I/Q corrector of receiver %d is off", r);
 	HIP_TRY(hipSetDevice(fe->device));
 	if (q->step) HIP_TRY(hipEventSynchronize(q->ev));       // the newest launch may still be reading the slot

@@ -84,9 +84,19 @@ int hfdl_gpu_frontend::settle_events()
 
 extern "C" void *hfdl_gpu_frontend_stream(hfdl_gpu_frontend *fe) { return fe ? (void *)fe->fft_stream(fe->side_of(true)) : nullptr; }      // the stream that reads device input
 
-// a block of input: a known sample format, exactly input_size samples
-static int check_block(const hfdl_gpu_frontend *fe, size_t nsamples, int fmt)
+// a block of input: a known sample format, exactly input_size samples.  A real front end takes the real formats alone, 2 input_size
+// samples a block, and from here on they are what they are to the forward FFT's loads: input_size pairs of the complex format of that
+// width (real_input.h)
+static int check_block(const hfdl_gpu_frontend *fe, size_t &nsamples, int &fmt)
 {
+	const bool real_fmt = fmt == HFDL_GPU_SFMT_RS16 || fmt == HFDL_GPU_SFMT_RF32;
+	if (real_fmt != (fe->real_rate != 0)) return fail(HFDL_GPU_EINVAL, "sample format %d on a front end for %s input", fmt, fe->real_rate ? "real" : "complex");
+	if (real_fmt) {
+		if (nsamples != 2 * (size_t)fe->plan.input_size)
+			return fail(HFDL_GPU_EINVAL, "a block is exactly %d real samples (got %zu)", 2 * fe->plan.input_size, nsamples);
+		fmt = fmt == HFDL_GPU_SFMT_RS16 ? SFMT_CS16 : SFMT_CF32;
+		nsamples /= 2;
+	}
 	if (fmt != SFMT_CF32 && fmt != SFMT_CS16 && fmt != SFMT_CU8) return fail(HFDL_GPU_EINVAL, "unknown sample format %d", fmt);
 	if (nsamples != (size_t)fe->plan.input_size)
 		return fail(HFDL_GPU_EINVAL, "a block is exactly %d samples (got %zu)", fe->plan.input_size, nsamples);
@@ -132,7 +142,7 @@ static int queue_input_copy(hfdl_gpu_frontend *fe, const void *const *iq, size_t
 // input is read where it lies, by a forward FFT on stream C itself (enqueue_fft).
 // iq[0 .. nrx - 1]: one block of every receiver; in.fresh[] receives where the forward FFT reads them.
 // *stage_idx = staging buffer used (-1 for device input): the forward FFT's first pass signals ev_stage_free when it has read it.
-static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int fmt, int on_device, FftInputs &in, int *stage_idx)
+static int stage_input(hfdl_gpu_frontend *fe, const void *const *iq, size_t nsamples, int &fmt, int on_device, FftInputs &in, int *stage_idx)
 {
 	*stage_idx = -1;
 	if (!fe || !iq) return fail(HFDL_GPU_EINVAL, "null argument");
@@ -332,10 +342,19 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		var.passes = mon ? FFT_PASSES_ALL : FFT_PASSES_12;
 		spectrum = mon ? mon->scratch.as<float2>() : nullptr;
 	}
-	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, spectrum, true, st,
-			FftOutLayout(), fft_done, job,
+	// Real input: the block's pairs are transformed as they are, pass 3 stores unshifted into the scratch, and one more launch untangles
+	// that into the slot, in natural order -- the equivalent stream's shifted order (real_input.h).  `done` and the timed stop ride on
+	// that launch, as they moved to pass 2 for the mixed domain; input_read, the timed start and the riders stay on the passes.
+	const bool real = fe->real_rate != 0;
+	launch_fft_forward(fe->fft.p, fe->d_hist[fe->blocks & 1], in, fmt, g.overlap, fe->d_hist[(fe->blocks + 1) & 1], fe->d_work, real ? fe->d_real : spectrum, !real, st,
+			FftOutLayout(), real ? nullptr : fft_done, job,
 			stage_idx >= 0 ? fe->ev_stage_free[stage_idx].e : nullptr,      // input consumed once pass 1 is done: the copy stream may refill the buffer
 			fft_start, var);
+	if (real) {
+		RealUntangleJob u;
+		u.in = fe->d_real; u.out = spectrum; u.in_stride = u.out_stride = g.n; u.n = g.n; u.logn = fe->fft.p.logn; u.nrx = fe->nrx;
+		launch_real_untangle(u, st, fft_done);
+	}
 	if (mon) {
 		// the spectrum monitor: one launch behind the last pass; the timed pair and the events other streams wait for stay on that pass
 		SpecmonJob m;
@@ -445,7 +464,8 @@ extern "C" int hfdl_gpu_frontend_channelize_block(hfdl_gpu_frontend *fe, const f
 	int rc = single_receiver_only(fe, "hfdl_gpu_frontend_channelize_block");
 	if (rc) return rc;
 	const void *one[1] = { iq };
-	if ((rc = stage_input(fe, one, nsamples, SFMT_CF32, on_device, in, &sidx))) return rc;
+	int fmt = SFMT_CF32;                                    // (cf32 I/Q: a real front end refuses it)
+	if ((rc = stage_input(fe, one, nsamples, fmt, on_device, in, &sidx))) return rc;
 	if ((rc = flush_pending_demod(fe, false))) return rc;
 	if ((rc = close_half(fe, true))) return rc;             // blocks pushed for the demodulator and not yet handed to it
 	if ((rc = enqueue_fft(fe, in, SFMT_CF32, sidx, on_device))) return rc;
@@ -529,7 +549,7 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	for (int c = 0; c < nch; c++)
 		if (c != channel && fe->rx_of[(size_t)c] == rx && fe->freqs[(size_t)c] == new_freq_hz)
 			return fail(HFDL_GPU_EINVAL, "channel %d of receiver %d already listens on %d Hz", c, rx, new_freq_hz);
-	const size_t ntaps = (size_t)fe->plan.taps_length, n = (size_t)fe->plan.n;
+	const size_t ntaps = fe->taps_host_len(), n = (size_t)fe->plan.n;
 	ChanConst k;
 	{
 		std::vector<float> none;
@@ -541,6 +561,7 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 		auto r = std::make_unique<Retune>();
 		CREATE_TRY(r->pad.alloc(sizeof(float2) * n));
 		CREATE_TRY(r->work.alloc(sizeof(float2) * n));
+		if (fe->real_rate) CREATE_TRY(r->eo.alloc(sizeof(float2) * 2 * n));
 		for (int i = 0; i < 2; i++) {
 			CREATE_TRY(r->stage[i].alloc(ntaps));
 			CREATE_TRY(r->staged[i].create(EV_NO_TIMING));
@@ -559,12 +580,15 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	// the boundary: what was pushed so far is folded and demodulated on the old frequency (a held-back half first, as a device push does)
 	if (int rc = flush_pending_demod(fe, false)) return rc;
 	if (int rc = close_half(fe, true)) return rc;
-	HIP_TRY(hipMemcpyAsync(r.pad.p, r.stage[sb].p, sizeof(float2) * ntaps, hipMemcpyHostToDevice, fe->stream));
 	const int slot = fe->slot_of(channel);
+	if (!fe->real_rate) HIP_TRY(hipMemcpyAsync(r.pad.p, r.stage[sb].p, sizeof(float2) * ntaps, hipMemcpyHostToDevice, fe->stream));
 	FftOutLayout lay = fe->tap_layout;
 	lay.chan = slot;
 	float2 *dst = lay.kind == TAPL_PLAIN ? fe->d_taps + (size_t)slot * (size_t)fe->geo.tap_chan_stride : fe->d_taps;
-	if (fe->geo.mix_l1) {
+	if (fe->real_rate) {
+		// real input: the function build_taps() went through, so the words are a fresh create's
+		if (int rc = queue_real_taps(fe, r.stage[sb].p, r.pad.as<float2>(), r.work.as<float2>(), r.eo.as<float2>(), slot, fe->stream, r.staged[sb])) return rc;
+	} else if (fe->geo.mix_l1) {
 		FftVariant v;
 		v.passes = FFT_PASSES_12;
 		launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), nullptr, true, fe->stream, FftOutLayout(), nullptr, NcoJob(), r.staged[sb], nullptr, v);

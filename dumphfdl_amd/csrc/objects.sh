@@ -8,6 +8,9 @@ SHIM_OBJS="hfdl_gpu frontend_create frontend_query frontend_quality demod_host s
 # -- the library's count of code objects and its size are pinned (tests/test_retune_device_cpu.py, tests/test_host_logic_cpu.py), and a
 # code object of its own costs 14 KB of headers and padding around 6 KB of code.  INCLUDED_<object>="<names>".
 INCLUDED_spectrum_kernels="quality_kernels blanker_kernels iqbal_kernels notch_kernels"
+# real-sampled input's two kernels ride with the forward FFT they sit behind; that object is compiled WITH contraction, so real_kernels
+# and real_input.h switch it off inside their own functions (a file-wide switch would reach the FFT passes behind the include)
+INCLUDED_fft_kernels="real_kernels"
 # demodulator, spectrum monitor and frame quality: no FMA contraction, so the fp32 recurrences round exactly like the plain-C oracle's,
 # the monitor's fp32 sums are what tests/spectrum_f64.py emulates term for term, and the quality figures are what the host build of
 # quality.h computes (quality_kernels rides in spectrum_kernels' object); the blanker's block power is what the host build of blanker.h adds

@@ -11,6 +11,7 @@ TAP_SPECTRUM, TAP_FILTER, TAP_CHAN_OUT, TAP_RESAMPLED, TAP_MF_OUT, TAP_SYMBOLS, 
 
 
 SFMT_CF32, SFMT_CS16, SFMT_CU8 = 0, 1, 2
+SFMT_RS16, SFMT_RF32 = 3, 4      # real samples, int16 / float32: a RealFrontend's formats (HFDL_GPU_SFMT_RS16 / _RF32)
 FCS_GOOD, FCS_BAD, FCS_TOO_SHORT = 0, 1, 2
 KIND_SPDU, KIND_MPDU_DOWNLINK, KIND_MPDU_UPLINK = 0, 1, 2
 
@@ -106,6 +107,7 @@ EXPORTS = [
     "hfdl_gpu_frontend_blanker_enable", "hfdl_gpu_frontend_blanker_stats", "hfdl_gpu_blank_block",
     "hfdl_gpu_frontend_notch_enable", "hfdl_gpu_frontend_notch_stats", "hfdl_gpu_notch_rows",
     "hfdl_gpu_frontend_iqbal_enable", "hfdl_gpu_frontend_iqbal_seed", "hfdl_gpu_frontend_iqbal_stats", "hfdl_gpu_iqbal_blocks",
+    "hfdl_gpu_frontend_create_real", "hfdl_gpu_frontend_real_input",
 ]
 
 
@@ -246,6 +248,8 @@ def _bind(L):
     L.hfdl_gpu_frontend_notch_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]
     L.hfdl_gpu_frontend_notch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(NotchStats)]
     L.hfdl_gpu_notch_rows.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    L.hfdl_gpu_frontend_create_real.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.hfdl_gpu_frontend_real_input.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     return L
 
 
@@ -663,6 +667,12 @@ class Frontend:
         """The canceller alone (module-level notch_rows)."""
         return notch_rows(x, mu, state, device)
 
+    def real_input(self):
+        """(is_real, sample_rate_real) as the library reports them (hfdl_gpu_frontend_real_input; (False, 0) for a complex front end)."""
+        a, b = C.c_int32(-1), C.c_int32(-1)
+        _check(self._L.hfdl_gpu_frontend_real_input(self._h, C.byref(a), C.byref(b)), self._L)
+        return bool(a.value), b.value
+
     def close(self):
         if self._h:
             self._L.hfdl_gpu_frontend_destroy(self._h)
@@ -741,6 +751,45 @@ class MultiFrontend(Frontend):
         for d in out:
             d["receiver"] = self._rx_of[d["channel"]]
         return out
+
+
+class RealFrontend(MultiFrontend):
+    """Receivers that deliver REAL samples (direct sampling) at sample_rate_real in one front end (hfdl_gpu_frontend_create_real):
+    receivers = [(base_freq, [freqs...]), ...], base_freq the RF frequency at 0 Hz of the samples.  The front end is MultiFrontend's for
+    the equivalent complex stream -- geometry.sample_rate = sample_rate_real / 2, receiver centres base + sample_rate_real / 4 --
+    and takes blocks of 2 * input_size real samples as SFMT_RS16 / SFMT_RF32 (push_real)."""
+
+    def __init__(self, sample_rate_real, receivers, device=0, lib=None):
+        L = self._L = lib or load()
+        self.sample_rate_real = int(sample_rate_real)
+        self.bases = [int(b) for b, _ in receivers]
+        self.receivers = [(int(b) + self.sample_rate_real // 4, [int(f) for f in fs]) for b, fs in receivers]
+        bases = np.ascontiguousarray(self.bases, dtype=np.int32)
+        counts = np.ascontiguousarray([len(fs) for _, fs in self.receivers], dtype=np.int32)
+        fr = np.ascontiguousarray([f for _, fs in self.receivers for f in fs], dtype=np.int32)
+        self._h = C.c_void_p()
+        _check(L.hfdl_gpu_frontend_create_real(C.byref(self._h), device, self.sample_rate_real, len(self.receivers), _p(bases), _p(fr), _p(counts)), L)
+        self.geometry = Geometry()
+        _check(L.hfdl_gpu_frontend_geometry(self._h, C.byref(self.geometry)), L)
+        self.freqs = [int(f) for f in fr]
+        self._spec_bins, self._spec_peak = 0, False
+        self._rx_of = [r for r, (_, fs) in enumerate(self.receivers) for _ in fs]
+
+    @property
+    def real_block(self):
+        """real samples of one block of one receiver"""
+        return 2 * self.geometry.input_size
+
+    def push_real(self, blocks, sample_format=SFMT_RS16, on_device=False):
+        """blocks[r]: receiver r's 2 * input_size real samples -- an int16 (SFMT_RS16) / float32 (SFMT_RF32) numpy array, or (on_device)
+        an int device pointer.  One call = one step."""
+        dt = {SFMT_RS16: np.int16, SFMT_RF32: np.float32}[sample_format]
+        keep = [b if isinstance(b, int) else np.ascontiguousarray(b, dtype=dt) for b in blocks]
+        ptrs = (C.c_void_p * max(1, len(keep)))(*[b if isinstance(b, int) else b.ctypes.data for b in keep])
+        lens = {len(b) for b in keep if not isinstance(b, int)} or {self.real_block}
+        if len(lens) != 1:
+            raise ValueError("the receivers' blocks differ in length: %s" % sorted(lens))
+        _check(self._L.hfdl_gpu_frontend_push_blocks_raw(self._h, ptrs, lens.pop(), sample_format, int(on_device)), self._L)
 
 
 BLANK_CHUNK = 4096         # samples per workgroup of the blanker's block power (dumphfdl_amd/csrc/blanker.h)

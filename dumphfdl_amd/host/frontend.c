@@ -30,6 +30,8 @@
 /* ... and the adaptive carrier canceller likewise */
 #pragma weak hfdl_gpu_frontend_notch_enable
 #pragma weak hfdl_gpu_frontend_notch_stats
+/* ... and real-sampled input likewise */
+#pragma weak hfdl_gpu_frontend_create_real
 
 /* The optional outputs of a front end.  Each is set for the NEXT front end by its setter and copied into the block when
  * fft_create() runs; every copy owns its memory (one deep copy, one free for all of them). */
@@ -84,6 +86,7 @@ struct gpu_fft_block {
 	float blanker_db;                        /* 0 = off */
 	float iq_alpha;                          /* 0 = off */
 	struct notch_settings notch;             /* mu 0 = off */
+	int32_t real_base_khz;                   /* -1 = off: the ring holds I/Q */
 };
 
 static int g_device = 0;
@@ -131,6 +134,14 @@ int hfdl_frontend_set_iq_correction(float alpha)
 {
 	if (!(alpha == 0.f || (alpha >= 1.f / 1024.f && alpha <= 1.f))) return -1;
 	g_iq_alpha = alpha;
+	return 0;
+}
+
+static int32_t g_real_base_khz = -1;
+int hfdl_frontend_set_real_input(int32_t base_khz)
+{
+	if (base_khz < -1 || base_khz > 2000000) return -1;
+	g_real_base_khz = base_khz;
 	return 0;
 }
 
@@ -504,6 +515,8 @@ struct fe_thread {
 	double fs, centerfreq;           /* of the receiver */
 	size_t need;                     /* samples of a block */
 	int gfmt;                        /* HFDL_GPU_SFMT_* of the ring's samples */
+	int bounce_fmt;                  /* ... and of the bounce buffer's: cf32, or with real input the same words as rf32 */
+	size_t push_n;                   /* what a push calls a block's samples: `need`, or with real input twice that (an element is two real samples) */
 	struct timeval t0;               /* wall clock at stream start */
 	hfdl_gpu_pdu *pdus;
 	hfdl_gpu_channel_stats *stats;
@@ -990,7 +1003,7 @@ static enum took take_block(struct fe_thread *t, const void **blk, bool *from_bo
  * Ring mutex: not held. */
 static bool push_block(struct fe_thread *t, const void *blk, bool from_bounce)
 {
-	if (hfdl_gpu_frontend_push_block_raw(t->fe, blk, t->need, from_bounce ? HFDL_GPU_SFMT_CF32 : t->gfmt, 0) != 0) {
+	if (hfdl_gpu_frontend_push_block_raw(t->fe, blk, t->push_n, from_bounce ? t->bounce_fmt : t->gfmt, 0) != 0) {
 		fail(t, hfdl_gpu_last_error());
 		(void)hfdl_gpu_frontend_prefetch_cancel(t->fe);
 		(void)hfdl_gpu_frontend_input_done(t->fe);
@@ -1012,7 +1025,7 @@ static void upload_ahead(struct fe_thread *t)
 		pthread_mutex_lock(t->ring->mutex);
 		const void *next = next_block_is_there(t) ? hfdl_ring_peek(t->ring->buf, uploads_next_offset(&t->up, t->need), t->need) : NULL;
 		pthread_mutex_unlock(t->ring->mutex);
-		if (next == NULL || hfdl_gpu_frontend_prefetch_block_raw(t->fe, next, t->need, t->gfmt) != 0) break;
+		if (next == NULL || hfdl_gpu_frontend_prefetch_block_raw(t->fe, next, t->push_n, t->gfmt) != 0) break;
 		uploads_queued_ahead(&t->up, next);
 	}
 }
@@ -1035,7 +1048,12 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 	t->ok = true;
 	if (t->nch == 0) {
 		fail(t, "no channels connected");
-	} else if (hfdl_gpu_frontend_create(&t->fe, fb->device, slots[0]->sample_rate, slots[0]->centerfreq, t->freqs, (int32_t)t->nch) != 0) {
+	} else if (fb->real_base_khz >= 0 && hfdl_ring_format(t->ring->buf) == SFMT_CU8) {
+		fail(t, "real input: CS16 or CF32 samples only");
+	} else if (fb->real_base_khz >= 0
+			/* the blocks around this one are wired for the equivalent complex stream (include/hfdl_host.h): the receiver's rate is twice theirs */
+			? hfdl_gpu_frontend_create_real(&t->fe, fb->device, 2 * slots[0]->sample_rate, 1, &(int32_t){ 1000 * fb->real_base_khz }, t->freqs, &(int32_t){ (int32_t)t->nch }) != 0
+			: hfdl_gpu_frontend_create(&t->fe, fb->device, slots[0]->sample_rate, slots[0]->centerfreq, t->freqs, (int32_t)t->nch) != 0) {
 		fail(t, hfdl_gpu_last_error());
 	} else {
 		hfdl_gpu_frontend_geometry(t->fe, &fb->geo);
@@ -1053,6 +1071,13 @@ static void frontend_setup(struct fe_thread *t, struct block *block)
 	gettimeofday(&t->t0, NULL);
 	t->need = t->ok ? (size_t)fb->geo.input_size : 1;
 	t->gfmt = gpu_format_of(hfdl_ring_format(t->ring->buf));
+	t->bounce_fmt = HFDL_GPU_SFMT_CF32;
+	t->push_n = t->need;
+	if (fb->real_base_khz >= 0) {
+		t->gfmt = t->gfmt == HFDL_GPU_SFMT_CS16 ? HFDL_GPU_SFMT_RS16 : HFDL_GPU_SFMT_RF32;
+		t->bounce_fmt = HFDL_GPU_SFMT_RF32;
+		t->push_n = 2 * t->need;
+	}
 	if (t->ok && ((fb->spectrum.path != NULL && spectrum_csv_open(t) != 0)
 			|| (fb->iqx.dir != NULL && iq_export_open(t->fe, fb, slots, t->nch, &t->iqx) != 0)
 			|| (fb->frame_log != NULL && frame_log_open(t) != 0))) {
@@ -1220,6 +1245,13 @@ struct block *fft_create(int32_t decimation, float transition_bw)
 		free(fb);
 		return NULL;
 	}
+	if (g_real_base_khz >= 0 && (hfdl_gpu_frontend_create_real == NULL || g_iq_alpha != 0.f)) {
+		fputs(hfdl_gpu_frontend_create_real == NULL ? "real-input: this GPU library has no real-sampled input\n"
+		                                            : "real-input: real samples have no I/Q to correct (iq-correct)\n", stderr);
+		free(fb);
+		return NULL;
+	}
+	fb->real_base_khz = g_real_base_khz;
 	fb->blanker_db = g_blanker_db;
 	fb->iq_alpha = g_iq_alpha;
 	fb->notch = notch_settings_copy(&g_notch);

@@ -5,7 +5,7 @@
  *               [--statsd-print] [--noise-floor-stats-interval S] [--shard R/W] [--bench] [--loop N]
  *               [--spectrum-file PATH [--spectrum-bins N] [--spectrum-interval S] [--spectrum-hann]]
  *               [--iq-export-dir DIR [--iq-export-format cf32|cs16] [--iq-export-scale X]]
- *               [--frame-log FILE] [--blanker DB] [--iq-correct ALPHA] [--notch MU[:KHZ,...]] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
+ *               [--frame-log FILE] [--blanker DB] [--iq-correct ALPHA] [--real-input[=BASE_KHZ]] [--notch MU[:KHZ,...]] [--retune SECONDS:OLD_KHZ:NEW_KHZ]... FREQ_KHZ...
  *
  * --shard R/W   single-stream multi-GPU mode: this process decodes channels R, R+W, R+2W, ... of the list on
  *               its --device; W processes fed the same file cover all channels, no communication between them.
@@ -27,6 +27,10 @@
  * --iq-correct ALPHA    wideband I/Q imbalance and DC corrector (hfdl_frontend_set_iq_correction, include/hfdl_host.h): every block
  *               enters the forward FFT with the image and DC offset estimated from the blocks before it removed; ALPHA (2^-10 .. 1;
  *               0.125 is the tested one) is a block's weight in the estimate; one line per receiver on stderr at the end.
+ *
+ * --real-input[=BASE_KHZ]    the file holds REAL samples of a direct-sampling receiver (hfdl_frontend_set_real_input, include/hfdl_host.h):
+ *               its CS16 / CF32 words are consecutive real samples, --sample-rate is their rate (even, at least 21600), BASE_KHZ (default
+ *               0) the frequency at 0 Hz in them, and --centerfreq is not taken; the receiver covers BASE_KHZ .. BASE_KHZ + rate / 2.
  *
  * --notch MU[:KHZ,KHZ,...]   adaptive carrier canceller (hfdl_frontend_set_notch, include/hfdl_host.h) with step MU (1e-5 .. 0.05; 0.002
  *               is the tested one) in front of the demodulator of the listed channels, or of every channel; one line per cancelled
@@ -110,6 +114,7 @@ int main(int argc, char **argv)
 	const char *iqx_dir = NULL, *frame_log = NULL;
 	int iqx_format = 0;                  /* 0 = cf32, 1 = cs16 */
 	float iqx_scale = 32767.f;
+	int32_t real_base_khz = -1;          /* --real-input: the file's words are real samples */
 	for (int i = 1; i < argc; i++) {
 		if (!strcmp(argv[i], "--iq-file") && i + 1 < argc) cfg->source = argv[++i];
 		else if (!strcmp(argv[i], "--sample-rate") && i + 1 < argc) cfg->sample_rate = atoi(argv[++i]);
@@ -136,6 +141,17 @@ int main(int argc, char **argv)
 		}
 		else if (!strcmp(argv[i], "--iq-correct") && i + 1 < argc) {
 			if (hfdl_frontend_set_iq_correction((float)atof(argv[++i])) != 0) { fprintf(stderr, "--iq-correct wants an alpha of 1/1024 to 1 (or 0 = off)\n"); return 1; }
+		}
+		else if (!strncmp(argv[i], "--real-input", 12) && (argv[i][12] == '\0' || argv[i][12] == '=')) {
+			/* --real-input or --real-input=BASE_KHZ ('=': a bare number after the option would read as a channel frequency) */
+			char *end = NULL;
+			const double b = argv[i][12] == '=' ? strtod(argv[i] + 13, &end) : 0.0;
+			/* (the range before the cast: a huge BASE_KHZ is no int32) */
+			if ((argv[i][12] == '=' && (end == argv[i] + 13 || *end != '\0')) || !(b >= 0.0 && b <= 2000000.0) || hfdl_frontend_set_real_input((int32_t)lround(b)) != 0) {
+				fprintf(stderr, "--real-input[=BASE_KHZ] wants the frequency at 0 Hz of the samples, 0 to 2000000 kHz\n");
+				return 1;
+			}
+			real_base_khz = (int32_t)lround(b);
 		}
 		else if (!strcmp(argv[i], "--notch") && i + 1 < argc) {
 			/* MU[:KHZ,KHZ,...] */
@@ -181,7 +197,17 @@ int main(int argc, char **argv)
 		fprintf(stderr, "usage: %s --iq-file F --sample-rate HZ --sample-format FMT [--centerfreq KHZ] freq_khz...\n", argv[0]);
 		return 1;
 	}
-	if (centerfreq_khz < 0) {        /* midpoint of the outermost channels, src/main.c:228-239 */
+	if (real_base_khz >= 0) {
+		/* real samples: everything from here on is wired for the equivalent complex stream (include/hfdl_host.h) -- a CS16 / CF32
+		 * element of the file is two real samples, so the elements come at half the real rate, centred a quarter of it above the base */
+		if (centerfreq_khz >= 0 || (cfg->sample_rate & 1) || cfg->sample_rate < 4 * HFDL_SYMBOL_RATE * SPS || cfg->sfmt == SFMT_CU8
+				|| 1000LL * real_base_khz + cfg->sample_rate / 2 + 1440 > INT32_MAX) {       /* (the span's top is an int32 of hertz) */
+			fprintf(stderr, "--real-input takes no --centerfreq, an even --sample-rate of at least %d and CS16 or CF32 words\n", 4 * HFDL_SYMBOL_RATE * SPS);
+			return 1;
+		}
+		cfg->centerfreq = 1000 * real_base_khz + cfg->sample_rate / 4;
+		cfg->sample_rate /= 2;
+	} else if (centerfreq_khz < 0) {        /* midpoint of the outermost channels, src/main.c:228-239 */
 		int32_t lo = freqs[0], hi = freqs[0];
 		for (int i = 1; i < nfreq; i++) { if (freqs[i] < lo) lo = freqs[i]; if (freqs[i] > hi) hi = freqs[i]; }
 		cfg->centerfreq = lo + (hi - lo) / 2;

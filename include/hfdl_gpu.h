@@ -194,6 +194,39 @@ int  hfdl_gpu_frontend_create_multi(hfdl_gpu_frontend **out, int device, int32_t
  * on_device / host-buffer rules as hfdl_gpu_frontend_push_block_raw (page-locked buffers reusable after input_done / sync / poll).
  * Works on any front end, nrx = 1 included. */
 int  hfdl_gpu_frontend_push_blocks_raw(hfdl_gpu_frontend *fe, const void *const *raw, size_t nsamples, int sample_format, int on_device);
+/* ---- real-sampled input: direct-sampling receivers ----
+ * nrx receivers that deliver REAL samples at sample_rate_real; base_freqs[r] is the RF frequency that appears at 0 Hz in receiver r's
+ * samples (0 for direct sampling), so receiver r covers base .. base + sample_rate_real / 2.  The call mirrors
+ * hfdl_gpu_frontend_create_multi (nrx = 1 is the ordinary case) and the front end is that call's for the EQUIVALENT COMPLEX STREAM of
+ * half the rate: sample rate sample_rate_real / 2, centre base + sample_rate_real / 4.  hfdl_gpu_frontend_geometry() and
+ * hfdl_gpu_frontend_channel_receiver() report that stream; hfdl_gpu_frontend_real_input() says the rest.  A block of 2 fft_size real
+ * samples goes through the fft_size-point complex transform of its sample pairs and one small launch behind it, the channel filters are
+ * designed at the real rate with 2 overlap_length + 1 taps and stored for the non-negative frequencies alone (half the taps, half the
+ * fold's work of a zero-imaginary stream): what a channel receives is (h * x_a) / 2 with x_a the block's analytic signal -- the mirror
+ * image is rejected outright, not through the filter's stop band.
+ * Checked before a device is selected (HFDL_GPU_EINVAL): null pointers, sample_rate_real even and >= 21 600, every base >= -2^30 with its
+ * span base .. base + sample_rate_real / 2 + 1440 inside an int32 of hertz (checked in 64 bits before the centre is formed), every channel within +- a quarter of
+ * sample_rate_real of its receiver's base + sample_rate_real / 4, the rest as hfdl_gpu_frontend_create_multi.
+ * Rules:
+ *   - input: hfdl_gpu_frontend_push_block_raw, _push_blocks_raw and _prefetch_block_raw with HFDL_GPU_SFMT_RS16 (int16, the full scale
+ *     of CS16) or HFDL_GPU_SFMT_RF32 (float32) and nsamples = 2 * geometry.input_size real samples.  A complex format on a real front
+ *     end, or a real one on a complex front end, is HFDL_GPU_EINVAL and enqueues nothing; hfdl_gpu_frontend_push_block and
+ *     _channelize_block (cf32 I/Q) are therefore refused.  hfdl_gpu_frontend_push_baseband works: it starts behind the channelizer
+ *   - the spectrum monitor works unchanged on the equivalent stream: its bands span base .. base + sample_rate_real / 2
+ *   - the blanker works unchanged, on the PAIRS it reads: a pair (x[2n], x[2n + 1]) whose power x[2n]^2 + x[2n + 1]^2 exceeds the
+ *     threshold goes as a whole, and the mean is over pairs
+ *   - hfdl_gpu_frontend_iqbal_enable and _iqbal_seed are HFDL_GPU_EINVAL: there is no I/Q to balance
+ *   - carrier canceller, export, frame quality records and retune are per channel and unchanged; a retuned channel's filter is a
+ *     fresh create's, bit for bit
+ *   - HFDL_GPU_FOLD_SPECTRUM=0 and HFDL_GPU_FOLD_PRUNE are ignored, as the prune is with nrx > 1
+ *   - HFDL_GPU_TAP_SPECTRUM returns the fft_size bins of the block's 2 fft_size-point real transform from 0 Hz up (bin k is
+ *     base + k sample_rate_real / (2 fft_size)); HFDL_GPU_TAP_FILTER the stored words, the factor 1/2 included */
+#define HFDL_GPU_SFMT_RS16 3
+#define HFDL_GPU_SFMT_RF32 4
+int  hfdl_gpu_frontend_create_real(hfdl_gpu_frontend **out, int device, int32_t sample_rate_real, int32_t nrx,
+		const int32_t *base_freqs, const int32_t *freqs, const int32_t *nch_per_rx);
+/* *is_real = 1 and *real_rate = sample_rate_real for a front end made by hfdl_gpu_frontend_create_real, 0 and 0 otherwise */
+int  hfdl_gpu_frontend_real_input(const hfdl_gpu_frontend *fe, int32_t *is_real, int32_t *real_rate);
 /* receiver and centre frequency of a channel */
 int  hfdl_gpu_frontend_channel_receiver(const hfdl_gpu_frontend *fe, int32_t channel, int32_t *rx, int32_t *centerfreq);
 int  hfdl_gpu_frontend_geometry(const hfdl_gpu_frontend *fe, hfdl_gpu_geometry *g);

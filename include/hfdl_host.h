@@ -236,6 +236,15 @@ int           hfdl_frontend_set_blanker(float threshold_db);
  * line per receiver on stderr gives kappa, the DC offset and the blocks refused.  Returns 0, or -1 for any other alpha (NaN included).
  * With a GPU library that lacks the corrector, fft_create() fails with a message on stderr. */
 int           hfdl_frontend_set_iq_correction(float alpha);
+/* Real-sampled input of the front end created by the next fft_create() (include/hfdl_gpu.h, "real-sampled input"); not in the reference,
+ * which takes I/Q alone.  base_khz 0 .. 2 000 000: the samples in the ring are REAL -- direct sampling; a CS16 or CF32 ring element is
+ * two consecutive real samples -- and base_khz is the RF frequency at 0 Hz in them; -1: off (the default).  The blocks around the front
+ * end are wired for the EQUIVALENT COMPLEX STREAM: for a receiver of fs_r real samples a second, compute_fft_decimation_rate(),
+ * compute_filter_relative_transition_bw(), fft_create() and hfdl_channel_create() take fs_r / 2 as the sample rate and
+ * 1000 base_khz + fs_r / 4 as the centre frequency, and a ring element lasts 2 / fs_r.  Returns 0, or -1 for any other base_khz.
+ * fft_create() fails with a message on stderr with a GPU library that lacks real input, and together with
+ * hfdl_frontend_set_iq_correction(): there is no I/Q to balance.  A CU8 ring stops the front end with a message when it starts. */
+int           hfdl_frontend_set_real_input(int32_t base_khz);
 /* Adaptive carrier canceller of the front end created by the next fft_create() (include/hfdl_gpu.h, "Adaptive carrier canceller"); not
  * in the reference, whose users notch in the SDR.  mu 1e-5 .. 0.05: the channels on freqs_khz[0 .. n - 1] (n = 0: every channel) run a
  * 32-tap normalised-LMS line canceller with that step in front of their demodulator; 0: off (the default).  When the front end stops,
