@@ -1,6 +1,7 @@
 // frontend.h -- internal: the front end behind the opaque hfdl_gpu_frontend of include/hfdl_gpu.h and what the translation units of the
 // shim share (namespace hfdl; the launch ledger and the done events are launch_timers.h's).  hfdl_gpu.cpp is the pipeline,
-// frontend_create.cpp builds a front end, frontend_query.cpp reads one, demod_host.cpp owns its demodulator state and a closed half's
+// frontend_create.cpp builds a front end, frontend_query.cpp reads one, frontend_options.cpp holds the opt-in stages (switch, pipeline
+// hook and reader of each; their state is declared here), demod_host.cpp owns its demodulator state and a closed half's
 // way through demodulator and burst decoder (demod.h), stages.cpp holds the one-shot stage entry points (checks, staging
 // and read-back; the kernels' launchers are beside the kernels), lab.cpp the laboratory build's switches, probes and stage.
 #pragma once
@@ -123,15 +124,11 @@ struct ChannelExport {
 	hipEvent_t newest = nullptr;        // what the newest launch carried (null: no launch yet)
 };
 
-// Impulse-noise blanker (hfdl_gpu_frontend_blanker_enable; blanker.h): never enabled = none, no launch.  Two launches per step in front of
-// the forward FFT's first pass, on that block's FFT stream: they leave the step's blocks, blanked, as cf32 in `scratch`, and the first
-// pass reads them there.  Forward FFTs run one after the other whichever stream they are on (they share d_work and the overlap
-// history: planner.h FftOrder), so one scratch buffer serves them all.  `ev` rides on the second launch's dispatch: a read of the
-// record waits for the newest launch without a packet of its own on the stream.  Turned off again (k2 = 0) the buffers stay until the
-// front end goes: the forward FFT queued last may still be reading them.
+// Impulse-noise blanker (hfdl_gpu_frontend_blanker_enable; blanker.h): never enabled = none, no launch.  The first stage of the input
+// chain (frontend_options.cpp condition_input): two launches per step, `ev` on the second one's dispatch.  Turned off again (k2 = 0)
+// the buffers stay until the front end goes.
 struct Blanker {
 	float k2 = 0.f;                     // (float)10^(threshold_db / 10); 0: off
-	DevBuf scratch;                     // [nrx][input_size] float2
 	DevBuf partial;                     // [nrx][blank_chunks(input_size)] float
 	DevBuf rec;                         // [nrx] BlankRecord
 	PinnedBuf<BlankRecord> host;        // bounce buffer of a read: one record
@@ -139,17 +136,13 @@ struct Blanker {
 	uint64_t blocks = 0;                // steps blanked so far
 };
 
-// I/Q imbalance and DC corrector (hfdl_gpu_frontend_iqbal_enable; iqbal.h): never enabled = none, no launch.  One launch per step behind
-// the blanker's and in front of the forward FFT's first pass, on that block's FFT stream: it leaves the step's blocks, corrected, as cf32
-// in `scratch` -- or where the blanker left them, in place -- and the first pass reads them there.  One scratch serves every forward FFT,
-// as the blanker's does.  State and chunk sums live in two slots, written in turn (`step` counts the launches).  `ev` rides on the
-// launch's dispatch: a read of the record, and a seed, wait for the newest launch without a packet of their own on the stream.  Turned
-// off again the buffers stay until the front end goes.
+// I/Q imbalance and DC corrector (hfdl_gpu_frontend_iqbal_enable; iqbal.h): never enabled = none, no launch.  The second stage of the
+// input chain: one launch per step, `ev` on its dispatch -- what a read of the record, and a seed, wait for.  State and chunk sums live
+// in two slots, written in turn (`step` counts the launches).  Turned off again the buffers stay until the front end goes.
 struct Iqbal {
 	std::vector<float> alpha;           // [nrx] 0: off
 	bool any_on = false;
 	uint64_t restart = 0;               // receivers whose next block is the first after an enable
-	DevBuf scratch;                     // [nrx][input_size] float2
 	DevBuf partial;                     // [2][nrx][5][blank_chunks(input_size)] float
 	DevBuf state;                       // [2][nrx] IqbalState
 	DevBuf seed;                        // [nrx] IqbalSeed
@@ -160,12 +153,11 @@ struct Iqbal {
 };
 
 // Adaptive carrier canceller (hfdl_gpu_frontend_notch_enable; notch.h): never enabled = none, no launch.  One launch per closed half on
-// stream B, in the half's hand-over to the demodulator (hfdl_gpu.cpp launch_demod): it reads the half's rows of d_chan_all and leaves
+// stream B, in the half's hand-over to the demodulator (launch_canceller): it reads the half's rows of d_chan_all and leaves
 // what the demodulator reads in `out`, a second buffer of d_chan_all's shape -- the channel export and stage tap 3 keep reading the
 // channelizer's own output.  Stream order is the only ordering: the canceller of half h + 2 overwrites `out` behind the demodulators of
 // half h, and the inverse FFT into a half waits for that half's last demodulator, which is queued behind the canceller that read it.
-// `ev` rides on the launch's dispatch: a read of a record waits for the newest launch without a packet of its own on the stream.
-// Turned off again (mu = 0) the buffers stay until the front end goes.
+// `ev` rides on the launch's dispatch.  Turned off again (mu = 0) the buffers stay until the front end goes.
 struct Notch {
 	float mu = 0.f;                     // 0: off
 	int nsel = 0;
@@ -209,6 +201,15 @@ bool design_channel(const hfdl_gpu_frontend *fe, int rx, int32_t freq, hfdl::Cha
 // and `work` into eo[0 .. N') and eo[N' .. 2N') -- and the combine into padded slot `slot` of the tap buffer.  `host` is read by the two
 // copies; `staged` (may be null) rides on the pass that reads `pad` last.  build_taps() and a retune both call it.
 int queue_real_taps(hfdl_gpu_frontend *fe, const float2 *host, float2 *pad, float2 *work, float2 *eo, int slot, hipStream_t st, hipEvent_t staged);
+
+// hfdl_gpu.cpp, for a change of setting: everything pushed so far goes on under the present one
+int close_boundary(hfdl_gpu_frontend *fe);
+// the opt-in stages' hooks (frontend_options.cpp): each one line of the pipeline, and nothing where its stage is off
+void condition_input(hfdl_gpu_frontend *fe, hfdl::FftInputs &in, int &fmt, hipStream_t st);       // enqueue_fft: the input chain in front of pass 1
+void launch_monitor(hfdl_gpu_frontend *fe, const float2 *spectrum, hipStream_t st);               // enqueue_fft: behind the forward FFT's last launch
+const float2 *launch_canceller(hfdl_gpu_frontend *fe, int slot0, int nblk, hipEvent_t ready);     // launch_demod: the rows the demodulators read; null: off
+int canceller_retuned(hfdl_gpu_frontend *fe, int channel);                                        // retune: the channel's canceller starts afresh
+void launch_export(hfdl_gpu_frontend *fe, int slot0, int nblk);                                   // close_half: behind the inverse FFT
 
 // Members are destroyed in reverse order of declaration: events first, then memory, then the streams (the destructor has synchronised
 // them).  So: streams, then memory, then events.
@@ -266,11 +267,15 @@ struct hfdl_gpu_frontend {
 	hfdl::NcoState *d_nco_snap = nullptr;     // [half_blocks][nch] the state each block of the half starts from
 	float2 *d_ph = nullptr, *d_ph_cont = nullptr;      // [half_blocks] NCO phasor tables [outs][nch] and the riders' segment hand-over [nch]
 	std::unique_ptr<hfdl::SpectrumMonitor> mon;        // null: off
+	float2 *monitor_scratch() const { return mon ? mon->scratch.as<float2>() : nullptr; }      // mixed domain: where pass 3 runs for the monitor alone (null: it does not run)
 	std::unique_ptr<hfdl::ChannelExport> exp;          // null: off
 	std::unique_ptr<hfdl::Retune> retune;              // null: no channel has been retuned
 	std::unique_ptr<hfdl::Blanker> blank;              // null: never enabled
 	std::unique_ptr<hfdl::Notch> notch;                // null: never enabled
 	std::unique_ptr<hfdl::Iqbal> iqbal;                // null: never enabled
+	// the input chain's one scratch, [nrx][input_size] cf32 (frontend_options.cpp condition_input has the rule): allocated by the first
+	// enable of either stage, kept until the front end goes -- the forward FFT queued last may still be reading it
+	hfdl::DevBuf chain_scratch;
 
 	// ---- events
 	hfdl::DoneEvent chan[2];            // channelizer output of this half ready (rides on the inverse FFT)

@@ -1,7 +1,7 @@
 // hfdl_gpu.cpp -- C-ABI shim of libhfdl_gpu.so, the pipeline: input staging, the forward FFT of a pushed block, the fold / inverse FFT
-// of a closed half, the carrier canceller's switch, the demodulator launches, sync and poll.  (frontend.h names the other translation units of the shim.)
+// of a closed half, the demodulator launches, retune, sync and poll.  The opt-in stages (input chain, spectrum monitor, carrier canceller,
+// channel export) are frontend_options.cpp's: the pipeline calls each through one hook.  (frontend.h names the other translation units of the shim.)
 // The only C++ a C host ever sees is through include/hfdl_gpu.h (extern "C", plain pointers).
-#include <algorithm>
 #include "frontend.h"
 
 using namespace hfdl;
@@ -223,23 +223,12 @@ extern "C" int hfdl_gpu_frontend_prefetch_cancel(hfdl_gpu_frontend *fe)
 static int launch_demod(hfdl_gpu_frontend *fe, int buf, int nblk, hipEvent_t ready)
 {
 	const int slot0 = buf * fe->half_blocks;
-	if (Notch *n = fe->notch.get(); n && n->mu > 0.f) {
-		// the carrier canceller: stream B waits for the half here, the canceller leaves the half's rows in its own buffer -- the selected
-		// channels' cancelled, the others' word for word -- and the demodulators read that buffer, behind it on the stream
-		const Geometry &g = fe->geo;
-		const size_t at = (size_t)slot0 * (size_t)g.nch * (size_t)g.outs;
-		float2 *out = n->out.as<float2>() + at;
-		if (ready) HIP_TRY(hipStreamWaitEvent(fe->stream_b, ready, 0));
-		if (n->nsel < g.nch) HIP_TRY(hipMemcpyAsync(out, fe->chan_slot(slot0), sizeof(float2) * (size_t)nblk * (size_t)g.nch * (size_t)g.outs, hipMemcpyDeviceToDevice, fe->stream_b));
-		NotchJob j;
-		j.in = fe->chan_slot(slot0); j.out = out; j.cnt = fe->cnt_slot(slot0); j.sel = n->sel.as<int32_t>();
-		j.state = n->state.as<float>(); j.rec = n->rec.as<NotchRecord>();
-		j.nch = g.nch; j.outs = g.outs; j.nblk = nblk; j.nsel = n->nsel; j.mu = n->mu;
-		launch_notch(j, fe->stream_b, n->ev);
-		n->launched = true;
-		return fe->demod.launch_half(out, fe->cnt_slot(slot0), nblk, buf, nullptr, fe->stream_b, fe->stream_d, fe->timers);
-	}
-	return fe->demod.launch_half(fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, buf, ready, fe->stream_b, fe->stream_d, fe->timers);
+	const float2 *rows = launch_canceller(fe, slot0, nblk, ready);
+	if (rows) {
+		HIP_TRY(hipGetLastError());
+		ready = nullptr;                    // the demodulators follow the canceller on stream B, and it has waited
+	} else rows = fe->chan_slot(slot0);
+	return fe->demod.launch_half(rows, fe->cnt_slot(slot0), nblk, buf, ready, fe->stream_b, fe->stream_d, fe->timers);
 }
 
 // The half being filled is left with `nblk` blocks in it: its last block is the newest channelized one, the other half is filled next.
@@ -301,46 +290,17 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		if (int rc = fe->timers.arm(ST_FFT, 1, done, fft_start)) return rc;
 		fft_done = done.event();
 	} else if (int rc = fe->timers.arm(ST_FFT, 1, fft_start, fft_done)) return rc;
-	if (Blanker *b = fe->blank.get(); b && b->k2 > 0.f) {
-		// the blanker: two launches in front of the first pass, which then reads the blanked cf32 blocks they leave.  The timed pair and
-		// every event other streams wait for stay on the three passes; the staging buffer's input_read event still rides on pass 1,
-		// which runs behind the blanker's last read of the input
-		BlankJob j;
-		for (int r = 0; r < fe->nrx; r++) j.fresh[r] = in.fresh[r];
-		j.out = b->scratch.as<float2>(); j.out_stride = g.input_size; j.partial = b->partial.as<float>(); j.rec = b->rec.as<BlankRecord>();
-		j.n = g.input_size; j.nrx = fe->nrx; j.fmt = fmt; j.k2 = b->k2;
-		launch_blanker(j, st, b->ev);
-		for (int r = 0; r < fe->nrx; r++) in.fresh[r] = j.out + (size_t)r * (size_t)g.input_size;
-		fmt = SFMT_CF32;
-		b->blocks++;
-	}
-	if (Iqbal *q = fe->iqbal.get(); q && q->any_on) {
-		// the I/Q corrector: one launch behind the blanker's and in front of the first pass, which then reads the cf32 blocks it leaves --
-		// in the blanker's scratch, in place, where the blanker ran, in its own otherwise.  The timed pair and every event other streams
-		// wait for stay on the passes, as with the blanker
-		IqbalJob j;
-		const bool in_place = fmt == SFMT_CF32 && fe->blank && in.fresh[0] == fe->blank->scratch.p;
-		for (int r = 0; r < fe->nrx; r++) { j.fresh[r] = in.fresh[r]; j.alpha[r] = q->alpha[(size_t)r]; }
-		j.out = in_place ? fe->blank->scratch.as<float2>() : q->scratch.as<float2>(); j.out_stride = g.input_size;
-		j.partial = q->partial.as<float>(); j.state = q->state.as<IqbalState>(); j.seed = q->seed.as<IqbalSeed>();
-		j.restart = q->restart; j.n = g.input_size; j.nrx = fe->nrx; j.fmt = fmt; j.slot = (int)(q->step & 1);
-		launch_iqbal(j, st, q->ev);
-		for (int r = 0; r < fe->nrx; r++) in.fresh[r] = j.out + (size_t)r * (size_t)g.input_size;
-		fmt = SFMT_CF32;
-		q->restart = 0;
-		q->step++;
-	}
+	condition_input(fe, in, fmt, st);           // the opt-in input chain: what it leaves is what pass 1 reads
 	// one three-pass sequence for every receiver of the step (kernels.h FftInputs)
 	in.nrx = fe->nrx; in.hist_stride = g.overlap; in.out_stride = g.n;
 	// The mixed domain: pass 2 leaves the fold's operand in the block's slot and carries fft_done; pass 3 runs for the spectrum monitor
 	// alone, behind it, into the monitor's one-block scratch (forward FFTs run one after the other: one scratch serves them all)
-	SpectrumMonitor *mon = fe->mon.get();
 	FftVariant var;
 	float2 *spectrum = fe->spec_slot(set, i);
 	if (g.mix_l1) {
 		var.mix_out = spectrum; var.mix_q = g.mix_q; var.mix_rx_stride = g.n;
-		var.passes = mon ? FFT_PASSES_ALL : FFT_PASSES_12;
-		spectrum = mon ? mon->scratch.as<float2>() : nullptr;
+		spectrum = fe->monitor_scratch();
+		var.passes = spectrum ? FFT_PASSES_ALL : FFT_PASSES_12;
 	}
 	// Real input: the block's pairs are transformed as they are, pass 3 stores unshifted into the scratch, and one more launch untangles
 	// that into the slot, in natural order -- the equivalent stream's shifted order (real_input.h).  `done` and the timed stop ride on
@@ -355,40 +315,9 @@ static int enqueue_fft(hfdl_gpu_frontend *fe, FftInputs &in, int fmt, int stage_
 		u.in = fe->d_real; u.out = spectrum; u.in_stride = u.out_stride = g.n; u.n = g.n; u.logn = fe->fft.p.logn; u.nrx = fe->nrx;
 		launch_real_untangle(u, st, fft_done);
 	}
-	if (mon) {
-		// the spectrum monitor: one launch behind the last pass; the timed pair and the events other streams wait for stay on that pass
-		SpecmonJob m;
-		m.spec = spectrum; m.rx_stride = g.n; m.n = g.n; m.bins = mon->bins; m.nrx = fe->nrx; m.flags = mon->flags;
-		m.scale = (float)(1.0 / ((double)g.n * (double)g.n * ((mon->flags & SPECMON_HANN) ? 0.375 : 1.0)));
-		m.fresh = mon->fresh; m.acc = mon->acc.as<float2>(); m.peak = mon->peak.as<float>();
-		SpectrumHistory *h = mon->hist.get();
-		hipEvent_t done = mon->ev;
-		if (h) {
-			// The open row's slot is the launch's second target and its event the one this dispatch carries: row i + rows overwrites
-			// the slot of row i in stream order.  One thread drives a front end (include/hfdl_gpu.h), and a collection returns only
-			// when its copies are done, so no copy of a slot is in flight while a push re-targets it.
-			const size_t slot = (size_t)(h->open % (uint64_t)h->rows), set = (size_t)fe->nrx * (size_t)mon->bins;
-			m.row_acc = h->acc.as<float2>() + slot * set;
-			if (mon->flags & SPECMON_MAXHOLD) m.row_peak = h->peak.as<float>() + slot * set;
-			m.row_fresh = h->open_blocks == 0;
-			done = h->ev[slot];
-		}
-		launch_spectrum_monitor(m, st, done);
-		mon->last = done;
-		for (int r = 0; r < fe->nrx; r++) {
-			if ((mon->fresh >> r) & 1) { mon->blocks[(size_t)r] = 0; mon->first[(size_t)r] = fe->blocks; }
-			mon->blocks[(size_t)r]++;
-		}
-		if (h) {
-			if (h->open_blocks++ == 0) h->open_first = fe->blocks;
-			if (h->interval > 0 && h->open_blocks == (uint32_t)h->interval) h->close();
-		}
-		mon->fresh = 0;
-	}
-	if (plan.hold_after) {
-		int rc = flush_pending_demod(fe, true);
-		if (rc) return rc;
-	}
+	launch_monitor(fe, spectrum, st);
+	if (plan.hold_after)
+		if (int rc = flush_pending_demod(fe, true)) return rc;
 	HIP_TRY(hipGetLastError());
 	fe->blocks++;
 	fe->batch_fill++;
@@ -431,20 +360,7 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	if (int rc = fe->timers.arm(ST_IFFT, nblk, fe->chan[half], ifft_start)) return rc;
 	launch_ifft_nco(g, fe->d_partial, fe->partial_stride(), fe->d_cc, fe->snap_slot(half, 0), fe->ph_slot(half, 0), fe->ph_stride(), fe->d_tw_m,
 			fe->chan_slot(slot0), fe->cnt_slot(slot0), nblk, fe->stream, fe->chan[half].event(), ifft_start);
-	if (ChannelExport *x = fe->exp.get()) {
-		// the channel export: one launch behind the inverse FFT, whose timed pair and done event stay where they are.  Stream order alone
-		// makes its read safe: the next inverse FFT into this half is behind it on this stream.  The half's blocks are the newest nblk.
-		const uint32_t skip = x->ring.skip_of_half(fe->blocks - (uint64_t)nblk, (uint32_t)nblk);
-		if (skip < (uint32_t)nblk) {
-			ExportJob e;
-			e.chan = fe->chan_slot(slot0 + (int)skip); e.cnt = fe->cnt_slot(slot0 + (int)skip); e.channels = x->channels.as<int32_t>();
-			e.nch = g.nch; e.outs = g.outs; e.P = g.outs - 1; e.nsel = x->nsel; e.nblk = nblk - (int)skip; e.format = x->format; e.scale = x->scale;
-			e.slot0 = x->ring.slot(fe->blocks - (uint64_t)e.nblk); e.R = x->ring.R;
-			e.samples = x->samples.p; e.counts = x->counts.as<int32_t>(); e.power = x->power.as<float>(); e.clipped = x->clipped.as<uint32_t>();
-			x->newest = x->ev[x->ring.push_launch(x->last_of.data(), fe->blocks - 1)];
-			launch_export_pack(e, fe->stream, x->newest);
-		}
-	}
+	launch_export(fe, slot0, nblk);
 	HIP_TRY(hipGetLastError());
 	fe->last_set = half;
 	fe->batch_fill = 0;
@@ -457,6 +373,14 @@ static int close_half(hfdl_gpu_frontend *fe, bool launch_now, bool with_demod = 
 	return 0;
 }
 
+// The boundary in front of a change of setting: everything pushed so far goes on under the old one -- a held-back half is launched, the half
+// being filled is closed as a sync closes it, without the sync's waits.
+int close_boundary(hfdl_gpu_frontend *fe)
+{
+	if (int rc = flush_pending_demod(fe, false)) return rc;
+	return close_half(fe, true);
+}
+
 extern "C" int hfdl_gpu_frontend_channelize_block(hfdl_gpu_frontend *fe, const float *iq, size_t nsamples, int on_device)
 {
 	FftInputs in;
@@ -466,8 +390,7 @@ extern "C" int hfdl_gpu_frontend_channelize_block(hfdl_gpu_frontend *fe, const f
 	const void *one[1] = { iq };
 	int fmt = SFMT_CF32;                                    // (cf32 I/Q: a real front end refuses it)
 	if ((rc = stage_input(fe, one, nsamples, fmt, on_device, in, &sidx))) return rc;
-	if ((rc = flush_pending_demod(fe, false))) return rc;
-	if ((rc = close_half(fe, true))) return rc;             // blocks pushed for the demodulator and not yet handed to it
+	if ((rc = close_boundary(fe))) return rc;               // blocks pushed for the demodulator and not yet handed to it
 	if ((rc = enqueue_fft(fe, in, SFMT_CF32, sidx, on_device))) return rc;
 	return close_half(fe, false, false);                    // this block is never demodulated
 }
@@ -577,9 +500,8 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	// the time-domain taps, designed on the host (exact reference arithmetic) straight into the page-locked buffer the copy reads
 	static_assert(sizeof(std::complex<float>) == sizeof(float2), "taps are copied as cf32");
 	design_channel(fe, rx, new_freq_hz, k, (std::complex<float> *)r.stage[sb].p, r.lp, r.lp_cut);
-	// the boundary: what was pushed so far is folded and demodulated on the old frequency (a held-back half first, as a device push does)
-	if (int rc = flush_pending_demod(fe, false)) return rc;
-	if (int rc = close_half(fe, true)) return rc;
+	// the boundary: what was pushed so far is folded and demodulated on the old frequency
+	if (int rc = close_boundary(fe)) return rc;
 	const int slot = fe->slot_of(channel);
 	if (!fe->real_rate) HIP_TRY(hipMemcpyAsync(r.pad.p, r.stage[sb].p, sizeof(float2) * ntaps, hipMemcpyHostToDevice, fe->stream));
 	FftOutLayout lay = fe->tap_layout;
@@ -596,66 +518,12 @@ extern "C" int hfdl_gpu_frontend_retune_channel(hfdl_gpu_frontend *fe, int32_t c
 	} else launch_fft_forward(fe->fft.p, nullptr, r.pad.p, SFMT_CF32, 0, nullptr, r.work.as<float2>(), dst, true, fe->stream, lay, nullptr, NcoJob(), r.staged[sb]);
 	launch_retune_channelizer(fe->d_cc, fe->d_nco, fe->d_ph_cont, channel, k, fe->stream, r.done.signal());
 	fe->demod.enqueue_retune(channel, new_freq_hz, fe->stream_b, fe->stream_d);
-	// the retuned channel meets a fresh canceller: its taps and delay line go where its demodulator state goes, behind the closed half on B
-	if (Notch *n = fe->notch.get()) HIP_TRY(hipMemsetAsync(n->state.as<float>() + (size_t)channel * NOTCH_STATE_FLOATS, 0, sizeof(float) * NOTCH_STATE_FLOATS, fe->stream_b));
+	if (int rc = canceller_retuned(fe, channel)) return rc;
 	HIP_TRY(hipGetLastError());
 	fe->order.retune();
 	fe->freqs[(size_t)channel] = new_freq_hz;
 	fe->cc[(size_t)channel] = k;
 	r.calls++;
-	return 0;
-}
-
-// ---------------------------------------------------------------- carrier canceller
-
-// From this call on the selected channels are cancelled with step `mu`, each from zero state; blocks pushed before it are handed over
-// as they would have been.  The half being filled is closed as a retune closes it; the new selection and the cleared state follow the
-// closed half's canceller and demodulators on stream B.  Everything is checked and allocated before the first launch.
-extern "C" int hfdl_gpu_frontend_notch_enable(hfdl_gpu_frontend *fe, const int32_t *channels, int32_t nsel, float mu)
-{
-	if (!(mu == 0.f || notch_mu_valid(mu))) return fail(HFDL_GPU_EINVAL, "canceller step %g: 0 (off) or %g .. %g", (double)mu, (double)NOTCH_MU_MIN, (double)NOTCH_MU_MAX);
-	if (!fe || nsel < 0 || (nsel > 0 && !channels)) return fail(HFDL_GPU_EINVAL, "null argument");
-	const int nch = fe->geo.nch;
-	std::vector<int32_t> sel;
-	std::vector<bool> seen((size_t)nch, channels == nullptr || nsel == 0);
-	if (channels && nsel > 0) {
-		for (int i = 0; i < nsel; i++) {
-			if (channels[i] < 0 || channels[i] >= nch || seen[(size_t)channels[i]]) return fail(HFDL_GPU_EINVAL, "canceller: channel %d out of range or listed twice", channels[i]);
-			seen[(size_t)channels[i]] = true;
-		}
-		sel.assign(channels, channels + nsel);
-	} else for (int c = 0; c < nch; c++) sel.push_back(c);
-	if (!fe->notch && mu == 0.f) return 0;
-	HIP_TRY(hipSetDevice(fe->device));
-	if (!fe->notch) {
-		auto n = std::make_unique<Notch>();
-		hipError_t e = n->out.alloc(sizeof(float2) * 2 * (size_t)fe->half_blocks * (size_t)nch * (size_t)fe->geo.outs);
-		if (e == hipSuccess) e = n->sel.alloc(sizeof(int32_t) * (size_t)nch);
-		if (e == hipSuccess) e = n->state.alloc(sizeof(float) * NOTCH_STATE_FLOATS * (size_t)nch);
-		if (e == hipSuccess) e = n->rec.alloc(sizeof(NotchRecord) * (size_t)nch);
-		if (e == hipSuccess) e = n->host.alloc(1);
-		if (e == hipSuccess) e = n->host_sel.alloc((size_t)nch);
-		if (e == hipSuccess) e = n->staged.create(EV_NO_TIMING);
-		if (e == hipSuccess) e = n->ev.create(EV_NO_TIMING);
-		if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HFDL_GPU_ENOMEM : HFDL_GPU_EHIP, "canceller buffers: %s", hipGetErrorString(e));
-		fe->notch = std::move(n);
-	}
-	// the boundary: what was pushed so far goes to the demodulator under the old setting (a held-back half first, as a retune does)
-	if (int rc = flush_pending_demod(fe, false)) return rc;
-	if (int rc = close_half(fe, true)) return rc;
-	Notch &n = *fe->notch;
-	n.mu = mu;
-	if (mu == 0.f) return 0;
-	if (n.staging) HIP_TRY(hipEventSynchronize(n.staged));       // the upload of the enable before this one has read the page-locked list
-	std::copy(sel.begin(), sel.end(), n.host_sel.p);
-	HIP_TRY(hipMemcpyAsync(n.sel.p, n.host_sel.p, sizeof(int32_t) * sel.size(), hipMemcpyHostToDevice, fe->stream_b));
-	HIP_TRY(hipEventRecord(n.staged, fe->stream_b));
-	n.staging = true;
-	HIP_TRY(hipMemsetAsync(n.state.p, 0, sizeof(float) * NOTCH_STATE_FLOATS * (size_t)nch, fe->stream_b));
-	HIP_TRY(hipMemsetAsync(n.rec.p, 0, sizeof(NotchRecord) * (size_t)nch, fe->stream_b));
-	n.nsel = (int)sel.size();
-	n.selected = seen;
-	n.launched = false;
 	return 0;
 }
 
@@ -665,8 +533,7 @@ extern "C" int hfdl_gpu_frontend_sync(hfdl_gpu_frontend *fe)
 {
 	if (!fe) return fail(HFDL_GPU_EINVAL, "null argument");
 	HIP_TRY(hipSetDevice(fe->device));
-	{ int rc = flush_pending_demod(fe, false); if (rc) return rc; }
-	{ int rc = close_half(fe, true); if (rc) return rc; }           // blocks waiting for their half to fill: folded and demodulated now
+	if (int rc = close_boundary(fe)) return rc;                     // blocks waiting for their half to fill: folded and demodulated now
 	fe->half_target = fe->half_first;                               // a drain: the pipeline starts over with a short first half
 	for (const Stream *s : { &fe->stream_c, &fe->stream_f, &fe->stream, &fe->stream_b, &fe->stream_d }) HIP_TRY(s->sync());      // (an alias is its owner's to synchronise)
 	fe->order.drained();

@@ -3,7 +3,7 @@
 # demodulator state), stages (the one-shot stage entry points) and lab are the shim's: they meet the demodulator's kernels through
 # demod_launch.h alone, so the strict builds' kernel object links with them as the product's does.
 KERNEL_OBJS="fft_kernels fold_kernels demod_kernels spectrum_kernels"
-SHIM_OBJS="hfdl_gpu frontend_create frontend_query frontend_quality demod_host stages lab"
+SHIM_OBJS="hfdl_gpu frontend_create frontend_query frontend_options frontend_quality demod_host stages lab"
 # Kernel files compiled INTO another file's object (hipcc --include=<name>.hip: in front of it): the opt-in features share ONE code object
 # -- the library's count of code objects and its size are pinned (tests/test_retune_device_cpu.py, tests/test_host_logic_cpu.py), and a
 # code object of its own costs 14 KB of headers and padding around 6 KB of code.  INCLUDED_<object>="<names>".

@@ -5,7 +5,8 @@ tests/test_iqbal_cpu.py sets against the float64 model of tests/iqbal_f64.py.
   1. the stage alone: output and records equal the host build's word for word;
   2. a front end with the corrector on, fed impaired input, equals -- spectrum tap and HFDL_GPU_TAP_CHAN_OUT of every block and channel as
      uint32, the PDUs -- a front end that never enables it, fed the host-build-corrected stream as cf32: every input path, both forms of the
-     forward FFT's first pass;  3. two receivers, each with its own estimate;  4. blanker and corrector together;
+     forward FFT's first pass;  3. two receivers, each with its own estimate;  4. blanker and corrector together, and the blanker
+     switched under a running corrector;
   5. the decode scenario through the device;  6. off is off;  7. hfdl_replay --iq-correct."""
 import ctypes
 import os
@@ -136,12 +137,12 @@ def pdu_key(pdus):
     return sorted((p["freq"], p["sample_index"], bytes(p["octets"])) for p in pdus)
 
 
-def reference_run(make, blocks):
+def reference_run(make, blocks, push=lambda fe, b: fe.push_block(b)):
     """a front end that never enables the corrector, fed `blocks` (complex64) one by one with a sync after each: ([taps] per block, PDUs)"""
     fe = make()
     out = []
     for b in blocks:
-        fe.push_block(b)
+        push(fe, b)
         out.append(taps(fe))
     pdus = pdu_key(fe.poll_pdus())
     fe.close()
@@ -347,6 +348,66 @@ def test_blanker_and_corrector_together(gpu, host):
         assert fe.blanker_stats()["samples_blanked"] == sum(counts)
         assert pdu_key(fe.poll_pdus()) == ref_pdus
         fe.close()
+
+
+SWITCHED_ON = (0, 1, 4, 5)              # of six blocks: the blanker is on for these, off for 2 and 3
+
+
+def switched_reference(host, x, nblk):
+    """one receiver's converted stream x: (the model's blanking of the blocks of SWITCHED_ON alone followed by the host build's correction
+    of the whole stream, the host build's records, the model's count of blanked samples) -- with the conditions on the input asserted"""
+    z = x.copy()
+    blanked = 0
+    for b in range(nblk):
+        blk = x[b * N:(b + 1) * N]
+        if b in SWITCHED_ON:
+            z[b * N:(b + 1) * N], mask, _ = bf.blank(blk, bf.THRESHOLD_DB)
+            blanked += int(mask.sum())
+        else:
+            mask, _, T, p = bf.model(blk, bf.THRESHOLD_DB)
+            bf.assert_guard_band(p, T)
+        assert mask.sum() > 0, b                                         # on: something is blanked; off: "off" is observable
+    y, recs, _, _ = host(z, N)
+    return y, recs, blanked
+
+
+@pytest.mark.parametrize("nrx,fmt", [(1, F.SFMT_CF32), (2, F.SFMT_CS16)])
+def test_blanker_switched_under_a_running_corrector(gpu, host, nrx, fmt):
+    """The corrector on throughout, the blanker on for blocks 0 - 1, off for 2 - 3 and on again for 4 - 5: the block that reaches the
+    transform is made by the blanker and then the corrector, or by the corrector alone, from block to block.  Every block equals the
+    model's blanking of blocks 0, 1, 4, 5 followed by the host build's correction of the whole stream, fed to a front end that never
+    enables either stage.  The scenario's first six blocks (receiver 1 of the two-receiver case: blocks 7 - 12, through another kappa and
+    DC) meet the conditions on the input -- every block holds samples the model blanks, none inside its guard band.  One receiver pushed
+    as cf32; two receivers pushed as cs16, where the first stage reads an integer format and the second sees the receiver stride (the
+    reference starts from the quantised streams)."""
+    nblk = 6
+    imp = bf.scenario()["impulsive"]
+    scale = np.float32(1.0 if fmt == F.SFMT_CF32 else 0.35)             # (the integer formats clip at 1)
+    sent = [iq.impair(imp[:nblk * N], iq.KAPPA, iq.DC), iq.impair(imp[7 * N:(7 + nblk) * N], -0.05 + 0.02j, -0.03 + 0.04j)][:nrx]
+    raws = [to_raw(s * scale, fmt).reshape(nblk, -1) for s in sent]
+    fixed = [switched_reference(host, bf.convert(r.reshape(-1), fmt), nblk) for r in raws]
+    if nrx == 1:
+        make = lambda: gpu.Frontend(iq.FS, iq.CF, iq.FREQS)
+        push = lambda fe, blocks, f=F.SFMT_CF32: fe.push_block_raw(blocks[0], f)
+    else:
+        make = lambda: gpu.MultiFrontend(iq.FS, [(iq.CF, iq.FREQS[:2]), (iq.CF, iq.FREQS[1:])])
+        push = lambda fe, blocks, f=F.SFMT_CF32: fe.push_blocks_raw(blocks, f)
+    ref_out, ref_pdus = reference_run(make, [[to_raw(y[b * N:(b + 1) * N], F.SFMT_CF32) for y, _, _ in fixed] for b in range(nblk)], push)
+    fe = make()
+    fe.iqbal_enable(ALPHA)
+    for b in range(nblk):
+        if b in (0, 2, 4):
+            fe.blanker_enable(bf.THRESHOLD_DB if b in SWITCHED_ON else 0.0)
+        push(fe, [r[b] for r in raws], fmt)
+        assert same(taps(fe), ref_out[b]), b
+        for r in range(nrx):
+            assert same_estimate(fe.iqbal_stats(r), fixed[r][1][b]), (b, r)
+    for r in range(nrx):
+        st = fe.blanker_stats(r)
+        print("receiver %d: %d samples blanked in %d blocks" % (r, st["samples_blanked"], st["blocks"]))
+        assert st["samples_blanked"] == fixed[r][2]
+    assert pdu_key(fe.poll_pdus()) == ref_pdus
+    fe.close()
 
 
 # ---------------------------------------------------------------- 5. decode

@@ -143,7 +143,7 @@ def test_library_and_host_build_design_their_taps_with_one_function():
     for name, src in (("frontend_create.cpp", lib), ("real_input_check.cpp", sim)):
         assert src.count("real_design_taps(") == 1, name
         assert "real_split_taps(" not in src and src.count("design_bandpass(") == (1 if name == "frontend_create.cpp" else 0), name       # (the library's one call is the complex path's)
-    for other in ("hfdl_gpu.cpp", "frontend_query.cpp", "stages.cpp"):
+    for other in ("hfdl_gpu.cpp", "frontend_query.cpp", "frontend_options.cpp", "stages.cpp"):
         assert "design_bandpass(" not in open(os.path.join(ROOT, "dumphfdl_amd", "csrc", other)).read(), other
 
 
